@@ -2,7 +2,8 @@
 """Benchmark of the GAN training hot path on MI355X: training samples/s for one full G+D iteration.
 
     python bench.py --gpus N --steps K --warmup W [--workload simnn|mmgan] [--batch B] [--dtype bf16|fp32]
-                    [--mode faithful|elided] [--no-cpu-baseline]
+                    [--mode faithful|elided] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-roofline]
+                    [--no-secondary]]
 
 Default workload = BASELINE.json configs[1]: model 1 (GAN_DES/SIMNN.py) G+D iteration, 128x256 synthetic spectrogram
 windows, batch 256 per GPU, bf16 MFMA, reference-faithful iteration (1 G forward, 3 D forwards, 2 D backwards, Adam).
@@ -10,10 +11,16 @@ N > 1: one process per GPU (torchrun env), per-GPU batch fixed (weak scaling), o
 discriminator-gradient bucket per iteration.  Rank 0 prints ONE JSON line.
 
 Timing: W warm-up iterations, then exactly K iterations between barrier + device-synchronize brackets, wall clock,
-MAX over ranks.  Inputs are resident in HBM before the timed region.  A second, instrumented pass of K iterations
-brackets every launch of the dominant kernel with HIP events (on the launch stream) for the `roofline` object; the
-CPU oracle (oracle/, this repo's restatement of the reference loop) is timed on the host cores for `cpu_baseline`
-(rank 0, N == 1 only).
+MAX over ranks.  Inputs are resident in HBM before the timed region.  A plain run does only that (set-up, warm-up, the
+K timed steps, the result line).  --dump-outputs DIR then writes what the timed path handed its caller after its last
+step (losses, generator output, model state) as DIR/<name>.npy; the inputs and weights are seeded, so two builds run
+with the same arguments can be compared array for array.
+
+--full adds what the headline figure does not need: a second, instrumented pass of K iterations brackets every
+launch of the dominant kernel with HIP events (on the launch stream) for the `roofline` object; short secondary
+measurements of the other configurations (`secondary`); the whole-step HBM traffic ratio from profiles/traffic.json;
+the CPU oracle (oracle/, this repo's restatement of the reference loop) timed on the host cores for `cpu_baseline` and
+the loss parity of a fresh trainer against it (`loss_parity`; rank 0, N == 1 only).
 """
 import argparse
 import json
@@ -74,10 +81,16 @@ def parse():
     ap.add_argument("--mode", default="faithful", choices=["faithful", "elided"])
     ap.add_argument("--width", type=int, default=256, help="spectrogram window width (simnn)")
     ap.add_argument("--seq", type=int, default=50, help="piano-roll length T (mmgan)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: roofline pass, secondary "
+                         "configurations, step traffic ratio, CPU baseline and loss parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline / loss parity")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline pass")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the short secondary measurements (model 2 at B=256 / B=16, model 1 in exact fp32)")
+                    help="--full without the short secondary measurements (model 2 at B=256 / B=16, model 1 in exact "
+                         "fp32)")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="model 1: run the generator half of an iteration inside the same call (SimnnTrainer.step)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
@@ -316,6 +329,49 @@ def launch_description(args, world, tr):
     return "hipGraph replay"
 
 
+DUMP_BUDGET_BYTES = 60 << 20     # all of --dump-outputs' arrays together (npy headers included: well under 64 MB)
+
+
+def timed_outputs(args, tr, losses):
+    """What a caller of the timed path has after its last step: the two losses (global-batch means), the generator
+    output(s) of that step and the models' state (the discriminator's parameters as Adam left them, the generators'
+    BatchNorm statistics)."""
+    out = {"disc_loss": torch.tensor([losses[0]], dtype=torch.float64),
+           "gen_loss": torch.tensor([losses[1]], dtype=torch.float64)}
+    if args.workload == "simnn":
+        out["generated"] = tr.last_generated
+        modules = {"gen": tr.gen, "disc": tr.disc}
+    else:
+        out["generated_g1"], out["generated_g2"] = tr.last_g1, tr.last_g2
+        modules = {"mmgan": tr.mm}
+    for prefix, m in modules.items():
+        for k, v in m.state_dict().items():
+            out[f"{prefix}.{k}"] = v
+    return out
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy: float32 (float64 for float64 and integer data), DUMP_BUDGET_BYTES in all.  Smallest first, an
+    array is written whole while it fits its share of what is left, otherwise as DIR/<name>_sample.npy: a fixed
+    (seed 0) sample of its flattened elements, in index order."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    items = []
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64
+        items.append((name, t.to("cpu", dt).numpy()))
+    items.sort(key=lambda kv: (kv[1].nbytes, kv[0]))
+    left = DUMP_BUDGET_BYTES
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share // a.itemsize, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def measure(args, rank, world, dev, barrier, dist):
     """Warm up, time exactly args.steps iterations between barriers, then (optionally) the per-launch timing passes of
     the dominant kernel.  Returns a dict."""
@@ -364,9 +420,12 @@ def measure(args, rank, world, dev, barrier, dist):
     if hasattr(tr, "flush"):
         tr.flush()       # pipelined schedule: the last iteration's generator half (its twin ran before the timed region)
     losses = (tr.disc_loss_value(), tr.gen_loss_global())      # global-batch means (gen_loss: one tiny collective)
+    if args.dump_outputs and rank == 0:
+        # before the roofline pass below, whose iterations move the state on
+        dump_outputs(args.dump_outputs, timed_outputs(args, tr, losses))
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         dk = dominant_kernel(args.workload, args.dtype, (128, args.width), args.seq)
 
         def time_kernel(fn):
@@ -442,6 +501,7 @@ def secondary_lines(args, rank, dev, barrier):
         for k, v in over.items():
             setattr(a, k, v)
         a.steps, a.warmup, a.prime = 50, 10, 20
+        a.dump_outputs = None
         torch.cuda.empty_cache()
         r = measure(a, rank, 1, dev, barrier, None)
         out[name] = {"ms_per_step": round(1e3 * r["elapsed"] / a.steps, 4),
@@ -502,7 +562,7 @@ def main():
             out["roofline"] = roofline
         tfile = os.path.join(ROOT, "profiles", "traffic.json")
         try:
-            st = json.load(open(tfile)).get(f"{args.workload}_{args.dtype}_step")
+            st = json.load(open(tfile)).get(f"{args.workload}_{args.dtype}_step") if args.full else None
             if st:
                 # whole-iteration HBM bytes (rocprofv3 --pmc, separate passes) over SURVEY.md 8d's algorithmic bytes
                 out["step_traffic_ratio"] = {"measured_bytes_per_step": st["measured_bytes_per_step"],
@@ -511,9 +571,9 @@ def main():
                                              "source": st.get("source", "profiles/traffic.json")}
         except Exception:
             pass
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             out["secondary"] = secondary_lines(args, rank, dev, barrier)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"], parity = cpu_baseline(args)
             out["loss_parity"] = loss_parity(args, parity, dev)
             if not out["loss_parity"]["pass"]:

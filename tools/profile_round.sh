@@ -6,5 +6,7 @@ python tools/pmc_traffic_summary.py gpurun_out/pmc_fetch gpurun_out/pmc_write gp
 python tools/step_breakdown.py gpurun_out/final_simnn_eager > gpurun_out/step_breakdown.txt
 bash tools/pmc_simnn.sh > /dev/null 2>&1
 python tools/pmc_summary.py gpurun_out/pmc_a gpurun_out/pmc_b > gpurun_out/pmc_sq.txt
-python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
-python bench.py --workload mmgan > gpurun_out/bench_mmgan.json 2>> gpurun_out/bench_default.err
+# default bench lines with everything they carried before (roofline, secondary, CPU baseline, loss parity): --full
+out=$(dirname "$(ls -t */pmc_sq.txt | head -n 1)")       # the folder the passes above wrote to
+python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"
+python bench.py --full --workload mmgan > "$out/bench_mmgan.json" 2>> "$out/bench_default.err"
