@@ -277,6 +277,9 @@ extern "C" int gdm_linear_bn_act_max_rows(void) { return LB_M; }
 namespace {
 int launch_jobs(const gdm_linear_bn_job* jobs, int n_jobs, float momentum, float eps, int act, int training,
                 hipStream_t s, const char* who) {
+  // the ABI carries no LeakyReLU slope, so GDM_ACT_LEAKY would quietly compute ReLU (checked before the pointers)
+  GDM_REQUIRE(act == GDM_ACT_NONE || act == GDM_ACT_RELU || act == GDM_ACT_SIGMOID,
+              "%s: act=%d is not offered here (NONE, RELU or SIGMOID; LEAKY has no slope argument)", who, act);
   LbJobs lj{};
   bool vec = true;
   int gp = 1, tiles = 0;

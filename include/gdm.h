@@ -241,7 +241,8 @@ int gdm_simnn_head(const float* h1, const float* w2, const float* b2, int n, int
  * groups >= 1: x, y_out, out hold `groups` batches of M rows one after the other (save_mean / save_invstd: groups x N);
  * every batch is normalised with its own statistics and the running statistics take the updates in batch order -- the
  * two forwards a generator makes per training iteration (network_tests.py:294, 312) in one launch.  stat_repeats >= 1
- * applies each running-statistics update that many times (a forward repeated on identical inputs).                  */
+ * applies each running-statistics update that many times (a forward repeated on identical inputs).  act: NONE, RELU or
+ * SIGMOID (LEAKY is not offered here: there is no slope argument; GDM_EINVAL).                                       */
 typedef struct gdm_linear_bn_job {      /* the arguments of gdm_linear_bn_act_fwd that differ between blocks */
   const float *x, *w, *bias, *gamma, *beta;
   float *running_mean, *running_var;

@@ -73,3 +73,19 @@ def test_build_stamp_covers_flags_and_compiler(monkeypatch):
         importlib.reload(build)
     from gan_des_midi_music_gen_amd import _lib
     assert _lib.load().gdm_build_flavor() == 0
+
+
+def test_linear_bn_refuses_leaky(lib_path):
+    """GDM_ACT_LEAKY has no slope argument in the generator-block ABI (it would compute ReLU): both entry points refuse
+    it on the host, before the pointer checks and before any launch."""
+    from gan_des_midi_music_gen_amd import _lib
+    lib = _lib.load()
+    rc = lib.gdm_linear_bn_act_fwd(None, None, None, None, None, None, None, None, 0.1, 1e-5, _lib.ACT_LEAKY, 1, 16, 8, 8,
+                                   None, None, None, None, 1, 1, None)
+    assert rc == -1 and b"LEAKY" in lib.gdm_last_error()
+    jobs = (_lib.LinearBnJob * 1)()
+    rc = lib.gdm_linear_bn_act_fwd_multi(ctypes.cast(jobs, ctypes.c_void_p), 1, 0.1, 1e-5, _lib.ACT_LEAKY, 1, None)
+    assert rc == -1 and b"LEAKY" in lib.gdm_last_error()
+    rc = lib.gdm_linear_bn_act_fwd(None, None, None, None, None, None, None, None, 0.1, 1e-5, _lib.ACT_SIGMOID, 1, 16, 8,
+                                   8, None, None, None, None, 1, 1, None)
+    assert rc == -1 and b"null pointer" in lib.gdm_last_error()
