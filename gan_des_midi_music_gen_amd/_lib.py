@@ -60,6 +60,7 @@ SIGNATURES = {
     "gdm_simnn_gen_convt_chunks": (_I, [_I, _I]),
     "gdm_simnn_gen_convt_bn": (_I, [_I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "gdm_simnn_gen_last": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "gdm_simnn_gen_eval": (_I, [_P, _I, _I, _P, _P] + [_P] * 12 + [_F, _P, _P, _P, _P, _P, _P]),
     "gdm_bias_act_fwd": (_I, [_P, _P, _I, _I, _I, _F, _P, _I, _P]),
     "gdm_act_bwd": (_I, [_P, _P, _I, _L, _I, _F, _P, _P]),
     "gdm_colsum": (_I, [_P, _I, _I, _I, _P, _P, _Z, _P]),

@@ -336,6 +336,181 @@ __global__ __launch_bounds__(512) void convt_k5_bn_sigmoid_kernel(const float* _
   }
 }
 
+// ---- eval-mode forward in one launch (GAN_DES/SIMNN.py:201-216, generate_song: gen.eval(), gen(noise)) ------------------
+// With running statistics BatchNorm is a per-channel affine map known before the launch, so no sample depends on another:
+// a 512-thread workgroup carries ONE sample from its noise vector to its 20x20 matrix and its activations (16x128, 64x64,
+// 256x32 values) never leave the CU.  One sample per workgroup because the chain is serial per sample (layer 4 is fp32
+// VALU, one output pixel per thread): B workgroups spread it over the CUs, and the MFMA shapes lose nothing by it from layer 2
+// on (a parity class of layer 2 has exactly 16 pixels per sample = one MFMA column tile; layer 3 has four).  Only layer 1
+// leaves 15 of 16 columns empty (512 MFMAs per sample: noise is the B operand, column 0).
+// Weights (832 KB of bf16 per sample) do not fit in LDS: every wave reads the A fragments of ITS output rows straight from
+// L2 into registers, 16 bytes per lane, each weight byte once per workgroup -- no wave shares a weight row with another
+// (layer 1: wave = 16 of the 128 row tiles; layers 2, 3: wave = (parity class, half of the output channels)), so an LDS
+// image of the weights would only add a barrier.  Rounding points are those of the training chain above.
+// LDS: a1 bf16 [6][6][136] (zero halo), a2 bf16 [10][10][72] (zero halo), a3 fp32 [256][36] over a1 (dead after layer 2);
+// the record paddings are those of convt_s2_bn_kernel / convt_k5_bn_sigmoid_kernel (fragment reads off one bank).
+struct gen_eval_params {
+  const float* noise;
+  int B, noise_dim;
+  const __bf16* pack;
+  const float* w4;
+  const float *gamma1, *beta1, *rmean1, *rvar1, *gamma2, *beta2, *rmean2, *rvar2, *gamma3, *beta3, *rmean3, *rvar3;
+  float eps;
+  float* out;
+  float *tap_y1, *tap_y2, *tap_y3, *tap_invstd;
+};
+
+template <bool TAPS>
+__global__ __launch_bounds__(512) void gen_eval_kernel(const gen_eval_params p) {
+  constexpr int S1 = 128 + 8, S2 = 64 + 8, S3 = 32 + 4, NC = 128 + 64 + 32;
+  __shared__ __attribute__((aligned(16))) unsigned char r0[256 * S3 * 4];  // a1, then a3
+  __shared__ __attribute__((aligned(16))) __bf16 a2[10 * 10 * S2];
+  __shared__ __attribute__((aligned(16))) float w_s[25 * 32];
+  __shared__ float sm[NC], sc[NC], sh[NC];                                 // channels of layer 1 | 2 | 3
+  static_assert(6 * 6 * S1 * 2 <= (int)sizeof(r0) && (6 * 6 * S1 * 2) % 16 == 0 && (10 * 10 * S2 * 2) % 16 == 0, "LDS images");
+  __bf16* a1 = (__bf16*)r0;
+  float* a3 = (float*)r0;
+  const int t = threadIdx.x, l = t & 63, wv = t >> 6, lr = l & 15, lg = l >> 4;
+  const int b = blockIdx.x;
+  if (t < NC) {
+    const int c = t < 128 ? t : (t < 192 ? t - 128 : t - 192);
+    const float* gamma = t < 128 ? p.gamma1 : (t < 192 ? p.gamma2 : p.gamma3);
+    const float* beta = t < 128 ? p.beta1 : (t < 192 ? p.beta2 : p.beta3);
+    const float* rmean = t < 128 ? p.rmean1 : (t < 192 ? p.rmean2 : p.rmean3);
+    const float* rvar = t < 128 ? p.rvar1 : (t < 192 ? p.rvar2 : p.rvar3);
+    const float invstd = 1.0f / sqrtf(rvar[c] + p.eps);
+    sm[t] = rmean[c];
+    sc[t] = invstd * gamma[c];
+    sh[t] = beta[c];
+    if (TAPS && b == 0 && p.tap_invstd) p.tap_invstd[t] = invstd;
+  }
+  for (int i = t; i < 25 * 32; i += 512) w_s[i] = p.w4[(i % 32) * 25 + i / 32];   // (Cin, 1, 5, 5) -> [tap][ci]
+  for (int i = t; i < 6 * 6 * S1 / 8; i += 512) ((f32x4*)a1)[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int i = t; i < 10 * 10 * S2 / 8; i += 512) ((f32x4*)a2)[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  // layer 1's B operand: the sample's noise in column 0 (lanes lr == 0), K zero padded to 128
+  bf16x8 nf[L1_K / 32];
+#pragma unroll
+  for (int ks = 0; ks < L1_K / 32; ++ks)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int k = ks * 32 + 8 * lg + j;
+      nf[ks][j] = (__bf16)((lr == 0 && k < p.noise_dim) ? p.noise[(size_t)b * p.noise_dim + k] : 0.f);
+    }
+  __syncthreads();                                  // images cleared, BatchNorm scale / shift and w4 visible
+  // the staged operand of the next layer: bf16(max(fma(x - mean, invstd * gamma, beta), 0)) of 4 consecutive channels
+  auto stage4 = [&](const f32x4& v, int ch) {
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = fmaxf(__builtin_fmaf(v[e] - sm[ch + e], sc[ch + e], sh[ch + e]), 0.f);
+    return r;
+  };
+  auto to_bf16x4 = [](const f32x4& v) {
+    bf16x4 h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) h[e] = (__bf16)v[e];
+    return h;
+  };
+  // ---- layer 1: rows n = pos * 128 + co of the packed conv1 image, 128 row tiles, 16 per wave
+  {
+    const __bf16* w1p = p.pack + GP_W2 + GP_W3;
+#pragma unroll 8
+    for (int q = 0; q < 16; ++q) {
+      const int tile = wv * 16 + q;
+      const __bf16* row = w1p + (size_t)(tile * 16 + lr) * L1_K + 8 * lg;
+      bf16x8 af[L1_K / 32];
+#pragma unroll
+      for (int ks = 0; ks < L1_K / 32; ++ks) af[ks] = *(const bf16x8*)(row + ks * 32);
+      f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < L1_K / 32; ++ks) acc = mfma16(af[ks], nf[ks], acc);
+      // C: column lr = 0 is the sample; rows 4 * lg + r = channels (tile & 7) * 16 + 4 * lg + r of pixel pos = tile >> 3
+      if (lr == 0) {
+        const int pos = tile >> 3, co = (tile & 7) * 16 + 4 * lg;
+        if (TAPS && p.tap_y1) *(f32x4*)&p.tap_y1[((size_t)b * 16 + pos) * 128 + co] = acc;
+        *(bf16x4*)&a1[(((pos >> 2) + 1) * 6 + (pos & 3) + 1) * S1 + co] = to_bf16x4(stage4(acc, co));
+      }
+    }
+  }
+  __syncthreads();
+  const int cl = wv & 3, mh = wv >> 2, qy = cl >> 1, qx = cl & 1;        // layers 2, 3: wave = (parity class, channel half)
+  // ---- layer 2: ConvT(128 -> 64, k4, s2, p1) 4x4 -> 8x8; per class M = 64 (2 tiles per wave), N = 16 pixels, K = 512
+  {
+    const int i = lr >> 2, j = lr & 3;
+    const int boff = ((i + qy + 1) * 6 + j + qx + 1) * S1 + 8 * lg;
+    const __bf16* wrow = p.pack + ((size_t)cl * 64 + mh * 32 + lr) * 512 + 8 * lg;
+    f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {
+      const int tap = ks >> 2, ci0 = (ks & 3) * 32, ta = tap >> 1, tb = tap & 1;
+      const bf16x8 bf = *(const bf16x8*)&a1[boff - (ta * 6 + tb) * S1 + ci0];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) acc[c] = mfma16(*(const bf16x8*)(wrow + c * 16 * 512 + ks * 32), bf, acc[c]);
+    }
+    const int oy = 2 * i + qy, ox = 2 * j + qx;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int co = mh * 32 + c * 16 + 4 * lg;
+      if (TAPS && p.tap_y2) *(f32x4*)&p.tap_y2[((size_t)b * 64 + oy * 8 + ox) * 64 + co] = acc[c];
+      *(bf16x4*)&a2[((oy + 1) * 10 + ox + 1) * S2 + co] = to_bf16x4(stage4(acc[c], 128 + co));
+    }
+  }
+  __syncthreads();                                  // a2 complete; a1 is dead from here on (a3 overlays it)
+  // ---- layer 3: ConvT(64 -> 32, k4, s2, p1) 8x8 -> 16x16; per class M = 32 (1 tile per wave), N = 64 pixels, K = 256
+  {
+    int boff[4];
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt) {
+      const int px = pt * 16 + lr, i = px >> 3, j = px & 7;
+      boff[pt] = ((i + qy + 1) * 10 + j + qx + 1) * S2 + 8 * lg;
+    }
+    const __bf16* wrow = p.pack + GP_W2 + ((size_t)cl * 32 + mh * 16 + lr) * 256 + 8 * lg;
+    f32x4 acc[4];
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt) acc[pt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      const int tap = ks >> 1, ci0 = (ks & 1) * 32, ta = tap >> 1, tb = tap & 1;
+      const bf16x8 af = *(const bf16x8*)(wrow + ks * 32);
+#pragma unroll
+      for (int pt = 0; pt < 4; ++pt)
+        acc[pt] = mfma16(af, *(const bf16x8*)&a2[boff[pt] - (ta * 10 + tb) * S2 + ci0], acc[pt]);
+    }
+    const int co = mh * 16 + 4 * lg;
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt) {
+      const int px = pt * 16 + lr, oy = 2 * (px >> 3) + qy, ox = 2 * (px & 7) + qx;
+      if (TAPS && p.tap_y3) *(f32x4*)&p.tap_y3[((size_t)b * 256 + oy * 16 + ox) * 32 + co] = acc[pt];
+      *(f32x4*)&a3[(oy * 16 + ox) * S3 + co] = stage4(acc[pt], 192 + co);
+    }
+  }
+  __syncthreads();
+  // ---- layer 4: ConvT(32 -> 1, k5, s1, p0) 16x16 -> 20x20 in fp32, sigmoid: convt_k5_bn_sigmoid_kernel's loop (one
+  // output pixel per thread, tap loops not unrolled: see there)
+  if (t < 400) {
+    const int oy = t / 20, ox = t % 20;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll 1
+    for (int kh = 0; kh < 5; ++kh) {
+      const int iy = oy - kh;
+      if ((unsigned)iy >= 16u) continue;
+#pragma unroll 1
+      for (int kw = 0; kw < 5; ++kw) {
+        const int ix = ox - kw;
+        if ((unsigned)ix >= 16u) continue;
+        const f32x4* xp = (const f32x4*)&a3[(iy * 16 + ix) * S3];
+        const f32x4* wq = (const f32x4*)&w_s[(kh * 5 + kw) * 32];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const f32x4 xv = xp[q], wq4 = wq[q];
+          s0 = fmaf(xv[0], wq4[0], s0); s1 = fmaf(xv[1], wq4[1], s1);
+          s2 = fmaf(xv[2], wq4[2], s2); s3 = fmaf(xv[3], wq4[3], s3);
+        }
+      }
+    }
+    p.out[(size_t)b * 400 + t] = sigmoid_f((s0 + s1) + (s2 + s3));
+  }
+}
+
 template <typename K>
 inline void allow_dyn_lds(K kernel, size_t bytes) {
   static const void* done[4];
@@ -408,5 +583,35 @@ extern "C" int gdm_simnn_gen_last(const float* yin, const float* mean, const flo
   hipLaunchKernelGGL(convt_k5_bn_sigmoid_kernel, dim3(B), dim3(512), 0, (hipStream_t)stream, yin, mean, invstd, gamma,
                      beta, w4, out);
   GDM_LAUNCH_OK("gdm_simnn_gen_last");
+  return GDM_OK;
+}
+
+extern "C" int gdm_simnn_gen_eval(const float* noise, int B, int noise_dim, const void* pack, const float* w4,
+                                  const float* gamma1, const float* beta1, const float* rmean1, const float* rvar1,
+                                  const float* gamma2, const float* beta2, const float* rmean2, const float* rvar2,
+                                  const float* gamma3, const float* beta3, const float* rmean3, const float* rvar3,
+                                  float eps, float* out, float* tap_y1, float* tap_y2, float* tap_y3, float* tap_invstd,
+                                  void* stream) {
+  GDM_REQUIRE(noise && pack && w4 && out, "gdm_simnn_gen_eval: null pointer");
+  GDM_REQUIRE(gamma1 && beta1 && rmean1 && rvar1 && gamma2 && beta2 && rmean2 && rvar2 && gamma3 && beta3 && rmean3 && rvar3,
+              "gdm_simnn_gen_eval: null BatchNorm vector");
+  GDM_REQUIRE(B >= 1 && noise_dim >= 1 && noise_dim <= L1_K, "gdm_simnn_gen_eval: batch %d < 1 or noise_dim %d outside 1..%d",
+              B, noise_dim, L1_K);
+  GDM_REQUIRE(eps >= 0.f, "gdm_simnn_gen_eval: eps < 0");
+  GDM_REQUIRE(((uintptr_t)pack & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)noise & 3) == 0 &&
+                  (((uintptr_t)tap_y1 | (uintptr_t)tap_y2 | (uintptr_t)tap_y3) & 15) == 0 && ((uintptr_t)tap_invstd & 3) == 0,
+              "gdm_simnn_gen_eval: alignment (pack, out and the taps 16 bytes, noise 4)");
+  gen_eval_params p;
+  p.noise = noise; p.B = B; p.noise_dim = noise_dim; p.pack = (const __bf16*)pack; p.w4 = w4;
+  p.gamma1 = gamma1; p.beta1 = beta1; p.rmean1 = rmean1; p.rvar1 = rvar1;
+  p.gamma2 = gamma2; p.beta2 = beta2; p.rmean2 = rmean2; p.rvar2 = rvar2;
+  p.gamma3 = gamma3; p.beta3 = beta3; p.rmean3 = rmean3; p.rvar3 = rvar3;
+  p.eps = eps; p.out = out;
+  p.tap_y1 = tap_y1; p.tap_y2 = tap_y2; p.tap_y3 = tap_y3; p.tap_invstd = tap_invstd;
+  if (tap_y1 || tap_y2 || tap_y3 || tap_invstd)
+    hipLaunchKernelGGL(gen_eval_kernel<true>, dim3(B), dim3(512), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(gen_eval_kernel<false>, dim3(B), dim3(512), 0, (hipStream_t)stream, p);
+  GDM_LAUNCH_OK("gdm_simnn_gen_eval");
   return GDM_OK;
 }

@@ -266,6 +266,8 @@ def _gen_pack(ws, cache):
     key = "gen_pack"
     ver = tuple(v for w in ws[:3] for v in (w.data_ptr(), w._version))
     hit = cache.get(key) if cache is not None else None
+    if hit is not None and hit[1].device != ws[0].device:       # the owner moved to another device
+        hit = None
     if hit is not None and hit[0] == ver:
         return hit[1]
     if hit is None and cache is not None and torch.cuda.is_current_stream_capturing():
@@ -299,11 +301,28 @@ def simnn_gen_forward_fused(noise, ws, bns, dt, cache=None):
     return ops.simnn_gen_last(y3, mean, invstd, g3, be3, ws[3].contiguous(), b)
 
 
-def _gen_fused_ok(noise, ws, training, dt, need_backward):
-    return (training and not need_backward and dt == BF16 and noise.shape[0] > 1 and tuple(ws[0].shape[1:]) == (128, 4, 4)
-            and ws[0].shape[0] <= 128
+def _gen_reference_geometry(ws):
+    return (tuple(ws[0].shape[1:]) == (128, 4, 4) and ws[0].shape[0] <= 128
             and tuple(ws[1].shape) == (128, 64, 4, 4) and tuple(ws[2].shape) == (64, 32, 4, 4)
             and tuple(ws[3].shape) == (32, 1, 5, 5))
+
+
+def _gen_fused_ok(noise, ws, training, dt, need_backward):
+    return (training and not need_backward and dt == BF16 and noise.shape[0] > 1 and _gen_reference_geometry(ws))
+
+
+def _gen_eval_ok(ws, training, dt):
+    """Eval mode in bf16 on the reference geometry: one launch for any batch (eval mode has no backward)."""
+    return not training and dt == BF16 and _gen_reference_geometry(ws)
+
+
+def simnn_gen_forward_eval(noise, ws, bns, cache=None):
+    """Eval-mode generator forward (SIMNN.py:201-216: gen.eval(), gen(noise)): BatchNorm on its running statistics, one
+    kernel launch, a sample's activations never leave the CU (csrc/simnn_gen.hip, gen_eval_kernel).  Any B >= 1; the
+    running statistics and num_batches_tracked are read only."""
+    b = noise.shape[0]
+    return ops.simnn_gen_eval(_f32c(noise).view(b, -1), _gen_pack(ws, cache), ws[3].contiguous(),
+                              [tuple(v.contiguous() for v in bn[:4]) for bn in bns])
 
 
 def simnn_gen_forward(noise, ws, bns, training, dt, cache=None, need_backward=True):
@@ -311,8 +330,11 @@ def simnn_gen_forward(noise, ws, bns, training, dt, cache=None, need_backward=Tr
 
     Returns (out (B,1,20,20) fp32, saved).  Activations are channels-last 2-D matrices (B*H*W, C).
     need_backward=False (the trainers: no gradient ever reaches a generator) takes the fused
-    forward-only kernels when the geometry is the reference's; ``saved`` is then None.
+    forward-only kernels when the geometry is the reference's; ``saved`` is then None.  Eval mode (training=False) in
+    bf16 on that geometry takes the one-launch eval kernel whatever need_backward says; ``saved`` is None as well.
     """
+    if _gen_eval_ok(ws, training, dt):
+        return simnn_gen_forward_eval(noise, ws, bns, cache), None
     if _gen_fused_ok(noise, ws, training, dt, need_backward):
         return simnn_gen_forward_fused(noise, ws, bns, dt, cache), None
     b = noise.shape[0]
@@ -366,13 +388,15 @@ def simnn_gen_backward(saved, dimg, ws, bns, dt, need_dnoise=True):
 
 @_anomaly_guard
 class SimnnGenFn(torch.autograd.Function):
-    """args: noise, w1..w4, (gamma,beta) x3, then non-differentiable: buffers tuple, training flag, dtype."""
+    """args: noise, w1..w4, (gamma,beta) x3, then non-differentiable: buffers tuple, training flag, dtype, and
+    the owning module's cache dict or None (used by the eval-mode kernel's weight pack only)."""
 
     @staticmethod
-    def forward(ctx, noise, w1, w2, w3, w4, g1, be1, g2, be2, g3, be3, buffers, training, dt):
+    def forward(ctx, noise, w1, w2, w3, w4, g1, be1, g2, be2, g3, be3, buffers, training, dt, cache):
         ws = [w.detach() for w in (w1, w2, w3, w4)]
         bns = [(g.detach(), be.detach(), *buf) for (g, be), buf in zip(((g1, be1), (g2, be2), (g3, be3)), buffers)]
-        img, saved = simnn_gen_forward(noise, ws, bns, training, dt)
+        img, saved = simnn_gen_forward(noise, ws, bns, training, dt,
+                                       cache=cache if _gen_eval_ok(ws, training, dt) else None)
         if not training:
             ctx.eval_mode = True
         ctx.saved, ctx.ws, ctx.bns, ctx.dt = saved, ws, bns, dt
@@ -385,7 +409,7 @@ class SimnnGenFn(torch.autograd.Function):
         if not ctx.training:
             raise NotImplementedError("backward through eval-mode BatchNorm is not on the reference's path")
         dnoise, dws, dbn = simnn_gen_backward(ctx.saved, dimg, ctx.ws, ctx.bns, ctx.dt, ctx.need_dnoise)
-        return (dnoise, *dws, dbn[0][0], dbn[0][1], dbn[1][0], dbn[1][1], dbn[2][0], dbn[2][1], None, None, None)
+        return (dnoise, *dws, dbn[0][0], dbn[0][1], dbn[1][0], dbn[1][1], dbn[2][0], dbn[2][1], None, None, None, None)
 
 
 # ======================================================================================================================

@@ -337,6 +337,27 @@ def simnn_gen_last(yin, mean, invstd, gamma, beta, w4, b):
     return out
 
 
+def simnn_gen_eval(noise2d, pack, w4, bns, *, eps=1e-5, taps=False):
+    """The whole generator in eval mode in one launch: noise (B, noise_dim) -> (B, 1, 20, 20), BatchNorm on its running
+    statistics (read, never written).  bns = 3 x (gamma, beta, running_mean, running_var[, ...]); pack from
+    simnn_gen_pack.  taps=True also returns the raw pre-BatchNorm accumulators and the three invstd vectors:
+    (out, y1 (B*16, 128), y2 (B*64, 64), y3 (B*256, 32), invstd (224,))."""
+    vecs = [v for bn in bns for v in bn[:4]]
+    _need_gpu(noise2d, pack, w4, *vecs)
+    b, nd = noise2d.shape
+    assert noise2d.dtype == torch.float32 and noise2d.is_contiguous() and w4.shape == (32, 1, 5, 5) and w4.is_contiguous()
+    assert len(vecs) == 12 and all(v.dtype == torch.float32 and v.is_contiguous() for v in vecs)
+    assert [v.numel() for v in vecs] == [128] * 4 + [64] * 4 + [32] * 4 and w4.dtype == torch.float32
+    assert pack.numel() == _lib.load().gdm_simnn_gen_pack_bytes()
+    dev = noise2d.device
+    out = torch.empty((b, 1, 20, 20), dtype=torch.float32, device=dev)
+    tap = [torch.empty(s, dtype=torch.float32, device=dev) for s in ((b * 16, 128), (b * 64, 64), (b * 256, 32), (224,))] \
+        if taps else [None] * 4
+    _call("gdm_simnn_gen_eval", _p(noise2d), b, nd, _p(pack), _p(w4), *[_p(v) for v in vecs], float(eps), _p(out),
+          *[_p(t) for t in tap], _stream())
+    return (out, *tap) if taps else out
+
+
 def bn_act_bwd(dout, out, y, gamma, mean, invstd, *, act):
     _need_gpu(dout, out, y, gamma, mean, invstd)
     rows, c = y.shape

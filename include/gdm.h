@@ -134,6 +134,22 @@ int gdm_simnn_gen_convt_bn(int layer, const float* yin, const float* mean, const
                            const float* beta, int B, const void* pack, float* yout, float* ws_partials, void* stream);
 int gdm_simnn_gen_last(const float* yin, const float* mean, const float* invstd, const float* gamma, const float* beta,
                        const float* w4, int B, float* out, void* stream);
+/* The whole generator in eval mode, one launch (GAN_DES/SIMNN.py:201-216, generate_song: gen.eval(), gen(noise); the
+ * ATen chain of SIMNN.py:97-112 with BatchNorm on its running statistics).  Reference geometry, noise (B, noise_dim)
+ * fp32 with 1 <= noise_dim <= 128, any B >= 1; `pack` is gdm_simnn_gen_pack's image.  A workgroup carries one sample
+ * through all four layers with its activations in LDS; the rounding points are those of the three training-mode calls
+ * above (bf16 noise, weights of layers 1..3 and staged operands bf16(max(fma(x - running_mean, invstd * gamma, beta), 0)),
+ * fp32 MFMA accumulation, layer 4 and the sigmoid in fp32), invstd = 1 / sqrtf(running_var + eps) computed in the kernel.
+ * Running statistics are only read.  A sample's result does not depend on B or on its row.  Optional taps (NULL = off,
+ * a kernel variant without them is launched when all four are NULL): the raw pre-BatchNorm accumulators tap_y1
+ * (B*16, 128), tap_y2 (B*64, 64), tap_y3 (B*256, 32), channels-last fp32, and tap_invstd (128 + 64 + 32 floats).
+ * pack, out and the y taps are 16-byte aligned.                                                                      */
+int gdm_simnn_gen_eval(const float* noise, int B, int noise_dim, const void* pack, const float* w4,
+                       const float* gamma1, const float* beta1, const float* rmean1, const float* rvar1,
+                       const float* gamma2, const float* beta2, const float* rmean2, const float* rvar2,
+                       const float* gamma3, const float* beta3, const float* rmean3, const float* rvar3,
+                       float eps, float* out, float* tap_y1, float* tap_y2, float* tap_y3, float* tap_invstd,
+                       void* stream);
 
 
 /* ---- elementwise helpers ---------------------------------------------------------------------------------------*/
