@@ -7,9 +7,10 @@
 
 Both reference functions do, per generated sample, (1) a block of numpy arithmetic that turns the generator's matrix
 into the constructor arguments of the discrete-event simulator and (2) the simulation / MIDI / audio rendering.  Part
-(2) -- simulation_v3.Sim, log parsing, FluidSynth -- is CPU / file / wall-clock bound and out of scope (SURVEY.md
-section 2 rows 3, 5-7, 9): it is INJECTED here as ``simulate`` (a callable), exactly where the reference constructs
-``Sim``.  Part (1) runs batched on the device (``ops.des_scan`` / ``ops.des_routing``, csrc/des_prologue.hip): the
+(2) is INJECTED here as ``simulate``, exactly where the reference constructs ``Sim``: a callable, or -- for
+matrix_to_midi -- the string "des" for the built-in back end (simulation_v3's deterministic DES core on the host, then
+one batched log -> MIDI -> piano-roll launch, sim_log_to_midi.py / csrc/des_midi.hip).  FluidSynth rendering
+(matrix_to_wav) stays outside.  Part (1) runs batched on the device (``ops.des_scan`` / ``ops.des_routing``, csrc/des_prologue.hip): the
 generator output never leaves HBM as a whole; what crosses to the host is the per-row masks the RNG bookkeeping needs
 and the final float64 routing matrices the simulator consumes.
 
@@ -150,14 +151,33 @@ def midi_prologue(gen1_output, gen2_output, adj_size=(32, 32), instrument=None):
 
 
 def matrix_to_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None, start=0, end=150, count=0,
-                   generate=False, simulate=None):
-    """Reference signature + ``simulate``: ``simulate(spec, count=..., start=..., end=..., generate=...,
-    gen2_tail=...)`` stands in for Sim + process_adjsim_log and returns (roll, durations) as (128, end-start) arrays, or
-    None for a failed / timed-out simulation.  Returns (list of (2,128,end-start) float64 arrays, failed_simulations)."""
+                   generate=False, simulate=None, *, return_tensor=False, midi_path=None, max_events=200000):
+    """Reference signature + ``simulate``.
+
+    simulate=callable: ``simulate(spec, count=..., start=..., end=..., generate=..., gen2_tail=...)`` stands in for Sim +
+    process_adjsim_log and returns (roll, durations) as (128, end-start) arrays, or None for a failed / timed-out
+    simulation.
+    simulate="des": the built-in back end.  Per sample, in the reference's order: draws, routing, ``run_spec`` (the
+    deterministic DES core; it consumes numpy's global stream like upstream's Sim, so the next sample's draws start
+    where the reference's do); then ONE ``des_log_to_roll`` launch turns all B event logs into the planes
+    (sim_log_to_midi.log_to_rolls).  A sample whose simulation raises counts as failed and keeps a zero roll.  With
+    ``generate`` the last sample's track is also written to ``midi_path`` (default adj_sim_outputs/midi/generation.mid,
+    the file upstream overwrites per sample).  The reference's 2.5 s wall-clock timeout has no counterpart: the core
+    stops after ``max_events`` events instead.
+
+    Returns (list of (2,128,end-start) float64 arrays, failed_simulations); with ``return_tensor`` (built-in back end)
+    the rolls stay on the device as one (B,2,128,end-start) fp32 tensor."""
     if simulate is None:
-        raise ops.GdmError("matrix_to_midi: the DES / MIDI back end is outside this package; pass simulate=callable "
-                           "(it receives the DesSpec the reference would construct Sim from)")
+        raise ops.GdmError("matrix_to_midi: pass simulate=\"des\" for the built-in DES / MIDI back end or "
+                           "simulate=callable (it receives the DesSpec the reference would construct Sim from)")
     start, end = int(start), int(end)
+    if isinstance(simulate, str):
+        if simulate != "des":
+            raise ops.GdmError(f"matrix_to_midi: unknown back end {simulate!r} (the built-in one is \"des\")")
+        return _matrix_to_midi_des(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor,
+                                   midi_path, max_events)
+    if return_tensor:
+        raise ops.GdmError("matrix_to_midi: return_tensor needs the built-in back end (simulate=\"des\")")
     h = _midi_scan(gen1_output, gen2_output, adj_size)
     g2 = h["g2"]
     midi_rolls, failed = [], 0
@@ -172,6 +192,44 @@ def matrix_to_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None,
             output[0], output[1] = res[0], res[1]
         midi_rolls.append(output)
     return midi_rolls, failed
+
+
+def _matrix_to_midi_des(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor, midi_path,
+                        max_events):
+    from . import sim_log_to_midi, simulation_v3
+    if end - start <= 0:
+        raise ValueError("negative dimensions are not allowed")          # np.zeros((2, 128, end - start)) upstream
+    if ops.des_roll_width(start, end) != end - start:
+        # generate_piano_roll's `[:, start:end]` of planes that are only end - start wide: upstream's assignment
+        # into the (2, 128, end - start) output fails to broadcast and the bare except re-raises ValueError
+        raise ValueError("Error in simulation thread, using blank piano roll instead. (start/end: the reference's "
+                         "final slice does not leave end - start columns; use start == 0 or end >= 128)")
+    h = _midi_scan(gen1_output, gen2_output, adj_size)
+    if h["g2"].shape[1] < 16:
+        raise ops.GdmError("matrix_to_midi: gen2_output needs at least 16 columns (gen2_output[10:16] drive the MIDI)")
+    specs = _interleaved_specs(h, _midi_draws, lambda h_, i, r, src, sd: _midi_spec(h_, i, r, src, sd, instrument))
+    logs, ok, insts, notes = [], [], [], []
+    for spec in specs:
+        try:
+            log, _reason = simulation_v3.run_spec(spec, max_events=max_events)
+            ok.append(True)
+        except (ValueError, KeyError):
+            log = np.zeros(0, dtype=simulation_v3.EVENT_DTYPE)
+            ok.append(False)
+        logs.append(log)
+        insts.append(spec.instruments)
+        notes.append(spec.note_levels)
+    save = [good and (bool(generate) or sim_log_to_midi.lines_read(len(lg)) % 100 == 0) for good, lg in zip(ok, logs)]
+    rolls, tracks = sim_log_to_midi.log_to_rolls(logs, h["g2"][:, 10:], insts, notes, start=start, end=end, save=save,
+                                                 device=h["g1"].device)
+    failed = len(ok) - sum(ok)
+    if generate:
+        done = [i for i, sv in enumerate(save) if sv]
+        if done:
+            sim_log_to_midi.write_midi(tracks[done[-1]], midi_path or "adj_sim_outputs/midi/generation.mid")
+    if return_tensor:
+        return rolls, failed
+    return [r for r in rolls.double().cpu().numpy()], failed
 
 
 def _wav_scan(matrices, size):

@@ -14,8 +14,10 @@ Module trees and state_dict keys equal the reference's (``gen.{i}.0`` = Linear, 
 ``conv1/conv2/fc``), so the committed ``mmgan_64_64_epoch_*.pth`` files load with ``strict=True``.  The nn children
 are parameter containers only; every forward runs through the HIP kernels of include/gdm.h.
 
-The DES bridge ``matrix_to_midi`` (network_tests.py:189) is outside this build's scope: ``MultiModalGAN`` takes it as
-an injected ``fake_provider(gen_output1, gen_output2, count) -> (rolls (B,2,128,T) tensor, failed_sim_count)``.
+The DES bridge ``matrix_to_midi`` (network_tests.py:189) is opt-in: ``MultiModalGAN`` takes ``fake_provider="des"`` for
+the built-in bridge (matrix_sim_process.matrix_to_midi(simulate="des"): DES core + one batched log -> MIDI -> piano-roll
+launch) or an injected ``fake_provider(gen_output1, gen_output2, count) -> (rolls (B,2,128,T) tensor,
+failed_sim_count)``; without one, forward raises.
 """
 import os
 import pickle
@@ -160,9 +162,21 @@ def _no_bridge(*_a, **_k):
                        "fake_provider=callable(gen_output1, gen_output2, count) -> (rolls, failed_sim_count)")
 
 
+def des_fake_provider(adj_size, instrument, start, end, generate=False, midi_path=None):
+    """The built-in bridge as a fake_provider: the reference's matrix_to_midi call (network_tests.py:189 / :204) with
+    the DES core and the batched log -> MIDI -> piano-roll kernel behind it; the rolls stay on the device."""
+    from .matrix_sim_process import matrix_to_midi
+
+    def provider(gen_output1, gen_output2, count):
+        return matrix_to_midi(gen_output1, gen_output2, adj_size=adj_size, instrument=instrument, start=start, end=end,
+                              count=0 if count is None else count, generate=generate, simulate="des",
+                              return_tensor=True, midi_path=midi_path)
+    return provider
+
+
 class MultiModalGAN(nn.Module):
     def __init__(self, z_dim=100, hidden_dim=64, adj_size=(28, 28), roll_size=(2, 128, 50), input_dim=50,
-                 output_dim=16, instrument=None, start=30, end=80, device="cpu", fake_provider=None):
+                 output_dim=16, instrument=None, start=30, end=80, device="cpu", fake_provider=None, midi_path=None):
         super().__init__()
         self.z_dim = z_dim
         self.generator1 = Generator(z_dim, hidden_dim=hidden_dim, adj_size=adj_size, device=device).to(device)
@@ -174,6 +188,14 @@ class MultiModalGAN(nn.Module):
         self.end = end
         self.adj_size = adj_size
         self.device = device
+        self.midi_path = midi_path          # where generate_midi's built-in bridge writes (default: upstream's path)
+        self.generate_provider = None
+        if isinstance(fake_provider, str):
+            if fake_provider != "des":
+                raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridge is \"des\")")
+            fake_provider = des_fake_provider(adj_size, instrument, start, end)
+            self.generate_provider = des_fake_provider(adj_size, instrument, start, end, generate=True,
+                                                       midi_path=midi_path)
         self.fake_provider = fake_provider if fake_provider is not None else _no_bridge
 
     def forward(self, noise1, noise2, input_tensor, count, make_dot_png=True):
@@ -193,7 +215,8 @@ class MultiModalGAN(nn.Module):
         with torch.no_grad():
             gen_output1 = self.generator1(noise1)
             gen_output2 = self.generator2(noise2, input_tensor)
-        sim_output, _failed = self.fake_provider(gen_output1.detach(), gen_output2.detach(), None)
+        provider = self.generate_provider if self.generate_provider is not None else self.fake_provider
+        sim_output, _failed = provider(gen_output1.detach(), gen_output2.detach(), None)
         return sim_output
 
 
@@ -205,7 +228,8 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
 
     train_loader: iterable of (piano_roll, durations, beats) batches (the reference's MaestroDatasetPickle loader,
         batch_size, drop_last); None -> seeded MAESTRO-shaped synthetic batches (``steps_per_epoch``, default 8).
-    fake_provider(g1_out, g2_out, count) -> ((B,2,128,T) tensor, failed): the DES bridge; None -> synthetic rolls.
+    fake_provider(g1_out, g2_out, count) -> ((B,2,128,T) tensor, failed): the DES bridge; "des" -> the built-in one
+        (DES core + batched log -> MIDI -> piano-roll kernel); None -> synthetic rolls.
     save_dir: if given, per-epoch ``losses/*.pkl`` and ``models/mmgan_{a}_{b}_epoch_{e}.pth`` are written there with
         the reference's file names; model_path: state_dict to resume from (optimizer state is not saved, as upstream).
     Returns (disc_losses, gen_losses) of the last epoch, like the reference.
@@ -216,6 +240,10 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
         torch.manual_seed(seed)
     roll_size = (2, 128, sequence_length)
     start = 100
+    if isinstance(fake_provider, str):
+        if fake_provider != "des":
+            raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridge is \"des\")")
+        fake_provider = des_fake_provider(adj_size, 0, start, start + sequence_length)
     mmgan = MultiModalGAN(z_dim=noise_dim, adj_size=adj_size, roll_size=roll_size, input_dim=max_beat_length,
                           output_dim=gen2_output_dim, instrument=0, start=start, end=start + sequence_length,
                           device=device, fake_provider=fake_provider)

@@ -875,6 +875,59 @@ def piano_roll_raster(row_ptr, ev_step, ev_vel, n_files, width):
     return roll, dur
 
 
+DES_MIDI_TRACK_CAP = 512        # GDM_DES_MIDI_TRACK_CAP
+DES_MIDI_ERRORS = {1: "MIDI parameters (gen2 tail) not finite or out of range", 2: "arrival at a node without "
+                   "instrument / note level", 3: "program or note outside 0..127", 4: "base + var == 0 (modulo by zero)"}
+
+
+def des_roll_width(start, end):
+    """Columns the reference's generate_piano_roll returns for (start, end): ``[:, start:end]`` of the end - start wide
+    planes when end < 128 (its test compares with the number of rows), else ``[:, :end]``."""
+    width = end - start
+    col0 = min(start, width) if end < 128 else 0
+    return min(end, width) - col0
+
+
+def des_log_to_roll(value, event_id, node, kind, rec_ptr, tails, instruments, note_levels, save, start, end,
+                    sequence_length=100):
+    """Event records of B samples (CSR: rec_ptr (B+1) i64) -> (planes (B,2,128,W) fp32, track (B,512,4) i32, track_len
+    (B) i32, status (B) i32), all device tensors; one launch (gdm_des_log_to_roll, include/gdm.h)."""
+    _need_gpu(value, event_id, node, kind, rec_ptr, tails, instruments, note_levels, save)
+    n = value.numel()
+    b = rec_ptr.numel() - 1
+    for t, dt in ((value, torch.float64), (event_id, torch.int64), (node, torch.int32), (kind, torch.int32)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise GdmError("des_log_to_roll: records must be contiguous f64 / i64 / i32 / i32 arrays of one length")
+    if rec_ptr.dtype != torch.int64 or b < 1 or not rec_ptr.is_contiguous():
+        raise GdmError("des_log_to_roll: rec_ptr must be a contiguous int64 tensor of B + 1 offsets")
+    if tails.dtype != torch.float32 or tails.dim() != 2 or tails.shape[0] != b or tails.shape[1] < 6 or \
+            tails.stride(1) != 1:
+        raise GdmError("des_log_to_roll: tails must be (B, >= 6) fp32")
+    dim = instruments.shape[-1]
+    for t in (instruments, note_levels):
+        if t.dtype != torch.int32 or t.shape != (b, dim) or not t.is_contiguous():
+            raise GdmError("des_log_to_roll: instruments / note_levels must be contiguous (B, dim) int32")
+    if save.dtype != torch.int32 or save.shape != (b,) or not save.is_contiguous():
+        raise GdmError("des_log_to_roll: save must be a contiguous (B,) int32 tensor")
+    # argument validation (one small reduction + sync), not arithmetic of the path: offsets must ascend within [0, n]
+    if bool(((rec_ptr[1:] < rec_ptr[:-1]).any() | (rec_ptr[0] < 0) | (rec_ptr[-1] > n)).item()):
+        raise GdmError(f"des_log_to_roll: rec_ptr must ascend within [0, {n}] (the number of records)")
+    start, end = int(start), int(end)
+    w = des_roll_width(start, end)
+    if end - start <= 0 or w <= 0:
+        raise GdmError(f"des_log_to_roll: start={start}, end={end} leave no columns")
+    dev = value.device
+    planes = torch.empty((b, 2, 128, w), dtype=torch.float32, device=dev)
+    track = torch.zeros((b, DES_MIDI_TRACK_CAP, 4), dtype=torch.int32, device=dev)
+    track_len = torch.empty(b, dtype=torch.int32, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    _call("gdm_des_log_to_roll", _p(value), _p(event_id), _p(node), _p(kind), _p(rec_ptr), n, _p(tails),
+          tails.stride(0) if b > 1 else tails.shape[1], _p(instruments), _p(note_levels), dim, _p(save), b, start, end,
+          int(sequence_length),
+          _p(planes), w, _p(track), DES_MIDI_TRACK_CAP, _p(track_len), _p(status), _stream())
+    return planes, track, track_len, status
+
+
 # ---- mel-spectrogram featuriser kernels (GAN_DES/util.py:37-61) -------------------------------------------------------
 def stft_frames(x, hop, n_fft):
     """x (B, L) fp32 -> (B * frames, n_fft) centred, reflect-padded frames; frames = 1 + L // hop."""

@@ -392,6 +392,38 @@ int gdm_des_routing(const float* g, int64_t sample_stride, int B, int S, int dim
 int gdm_piano_roll_raster(const int32_t* row_ptr, const int32_t* ev_step, const int32_t* ev_vel, int n_files, int W,
                           float* roll, float* dur, void* stream);
 
+/* ---- DES log -> MIDI track -> piano-roll planes, batched over samples (process_adjsim_log / MidiGenerator,
+ * MMGAN_MIDI_DES/sim_log_to_midi.py:14-277, then generate_piano_roll on the file it builds, datasets.py:13-54).
+ * One launch, one workgroup per sample.  Records of sample s are value/event_id/node/kind[rec_ptr[s] .. rec_ptr[s+1])
+ * (the fields of the DES core's event log, gdm_des_run; rec_ptr has B + 1 entries, all clamped to [0, n_records]);
+ * only the first 5000 are looked at, as the reference's reader does.  tails (B, tail_stride) fp32: gen2_output[10:],
+ * six values used; instruments, note_levels (B, dim) i32; save (B) i32: non-zero = save_midi runs for this sample
+ * (the caller decides: `generate` or a line count that is a multiple of 100) -- otherwise the reference's MidiFile
+ * has no track and the planes stay zero.  start / end / sequence_length are generate_piano_roll's.
+ * Outputs (planes and track 16-byte aligned: checked): planes (B, 2, 128, W) fp32 = [roll, durations] with W = the width the reference's final slice leaves
+ * (checked); track (B, track_cap, 4) i32 = (kind, a, b, time) quadruples, kind one of GDM_MIDI_*, a/b = tempo,0 |
+ * numerator,denominator | key index,0 | program,0 | note,velocity | 0,0; track_len (B) i32; status (B) i32:
+ * bit 0 = the track is the saved one (after save_midi), bits 8.. = 0 or a GDM_DES_MIDI_E* code (the reference raises
+ * for such a sample; its track is empty and its planes are zero).                                                  */
+#define GDM_MIDI_SET_TEMPO 0
+#define GDM_MIDI_TIME_SIGNATURE 1
+#define GDM_MIDI_KEY_SIGNATURE 2
+#define GDM_MIDI_PROGRAM_CHANGE 3
+#define GDM_MIDI_NOTE_ON 4
+#define GDM_MIDI_NOTE_OFF 5
+#define GDM_MIDI_END_OF_TRACK 6
+#define GDM_DES_MIDI_TRACK_CAP 512 /* the reference stops appending at 500 messages (+ 1 + end_of_track) */
+#define GDM_DES_MIDI_MAX_NODES 256
+#define GDM_DES_MIDI_EPARAMS 1 /* a tail value is not finite, beyond int32 after scaling, or gives a negative tempo */
+#define GDM_DES_MIDI_ENODE 2   /* an arrival at a node without instrument / note level (KeyError upstream) */
+#define GDM_DES_MIDI_ERANGE 3  /* program or note outside 0..127 (mido refuses the message) */
+#define GDM_DES_MIDI_EMODULO 4 /* base + var == 0: customer_id % 0 */
+int gdm_des_log_to_roll(const double* value, const int64_t* event_id, const int32_t* node, const int32_t* kind,
+                        const int64_t* rec_ptr, int64_t n_records, const float* tails, int tail_stride,
+                        const int32_t* instruments, const int32_t* note_levels, int dim, const int32_t* save, int B,
+                        int start, int end, int sequence_length, float* planes, int W, int32_t* track, int track_cap,
+                        int32_t* track_len, int32_t* status, void* stream);
+
 /* ---- mel-spectrogram featuriser (GAN_DES/util.py:37-61: torchaudio MelSpectrogram + AmplitudeToDB) --------------
  * The producer of model 1's discriminator input.  DFT and mel filter bank are gdm_gemm calls in exact fp32 (window
  * folded into the [cos | sin] matrix); these three functions are the kernels around them.
