@@ -11,6 +11,8 @@ LIB_PATH = os.path.join(_PKG, "libgdm_hip" + (f"_{_TAG}" if _TAG else "") + ".so
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
+# model 2's criterion names -> GDM_CRIT_* (include/gdm.h; network_tests.py:248-250 of the reference)
+CRITERIA = {"bce": 0, "mse": 1, "l1": 2}
 
 _c = ctypes
 _P, _I, _L, _F, _Z = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_size_t
@@ -40,6 +42,7 @@ SIGNATURES = {
     "gdm_build_flavor": (_I, []),
     "gdm_gemm": (_I, [_P, _I, _L, _L, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _I, _F, _I, _I, _P, _Z, _P]),
     "gdm_bce_with_logits": (_I, [_P, _F, _I, _F, _P, _P, _I, _I, _P]),
+    "gdm_criterion_loss": (_I, [_P, _F, _I, _I, _F, _P, _P, _I, _P]),
     "gdm_adam_step": (_I, [_P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _P]),
     "gdm_adam_step_dev": (_I, [_P, _P, _P, _P, _L, _P, _P]),
     "gdm_adam_step_dev_pc": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P]),
@@ -94,6 +97,10 @@ SIGNATURES = {
     "gdm_dcnn_fused_workspace_bytes": (_Z, [_I, _I, _I]),
     "gdm_dcnn_fused": (_I, [_P, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "gdm_dcnn_fused_adam": (_I, [_P, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "gdm_dcnn_fused_crit": (_I, [_P, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _Z,
+                                 _P]),
+    "gdm_dcnn_fused_adam_crit": (_I, [_P, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P,
+                                      _Z, _P]),
     "gdm_im2col": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "gdm_col2im": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     "gdm_permute_pc": (_I, [_P, _I, _I, _I, _I, _P, _I, _P]),

@@ -1,11 +1,13 @@
 // Model 2's CNN discriminator (MMGAN_MIDI_DES/network_tests.py:147-160) as ONE persistent kernel: a 512-thread
 // workgroup keeps a whole piano-roll sample and every activation of it in LDS (160 KB per CU on MI355X) and runs
-//   conv1 k4 s2 p1 + LeakyReLU -> conv2 k4 s2 p1 + LeakyReLU -> fc -> BCE-with-logits        (forward + loss)
+//   conv1 k4 s2 p1 + LeakyReLU -> conv2 k4 s2 p1 + LeakyReLU -> fc -> criterion              (forward + loss)
 //   d fc, dW_fc, d conv2 (weights + data), LeakyReLU', d conv1 (weights)                      (backward)
 // on it, so HBM sees the input planes once (51 KB per sample at T = 50) and nothing else; weight gradients are
 // accumulated in registers across the samples a workgroup processes and leave as one slab per workgroup (summed in
 // fixed order afterwards: deterministic, no atomics).  bf16 operands (piano-roll velocities/durations are small
 // integers: exact), fp32 accumulation; the exact-fp32 parity path for this model stays on the GEMM + im2col lowering.
+// The criterion on the logit is one of the three the reference's loop offers (network_tests.py:248-250): BCE-with-logits,
+// MSE or L1 (GDM_CRIT_*), a run-time argument.
 //
 // All convolutions are implicit GEMMs on v_mfma_f32_16x16x32_bf16:
 //   conv1 fwd   M=16 oc,  N=16 pixels of a row, K=32  (kh,kw,ci)          B operand = 8 contiguous bf16 of the input row
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(NTHREADS) void dcnn_fused_kernel(const float* __res
                                                               const float* __restrict__ p1, int B, float ya,
                                                               float yb, const __bf16* __restrict__ pk,
                                                               float* __restrict__ logits, float* __restrict__ slabs,
-                                                              int slab_width, int want_grad) {
+                                                              int slab_width, int want_grad, int crit) {
   constexpr Dims d(T);
   DSTAMP_DECL;
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
@@ -329,10 +331,24 @@ __global__ __launch_bounds__(NTHREADS) void dcnn_fused_kernel(const float* __res
     for (int w = 0; w < NWAVES; ++w) z += red[w];
     const bool first = b < bsplit;
     const float y = first ? ya : yb, cnt = (float)(first ? bsplit : B - bsplit);
-    const float dl = (1.0f / (1.0f + expf(-z)) - y) / cnt;
+    // the criterion head (network_tests.py:248-250, applied at 304-305 and 313): d loss / d z of the half's mean, and
+    // on thread 0 the sample's loss term.  `crit` is a kernel argument (uniform: a scalar branch once per sample, no
+    // instance per criterion); the BCE branch holds the expressions this kernel has always used
+    float dl;
+    if (crit == GDM_CRIT_BCE_LOGITS) {
+      dl = (1.0f / (1.0f + expf(-z)) - y) / cnt;
+    } else {
+      const float r = z - y;
+      dl = (crit == GDM_CRIT_MSE ? 2.0f * r : (r > 0.f ? 1.0f : (r < 0.f ? -1.0f : 0.f))) / cnt;   // sign(0) = 0 as torch
+    }
     if (t == 0) {
       logits[b] = z;
-      loss_acc += (fmaxf(z, 0.f) - z * y + log1pf(expf(-fabsf(z)))) / cnt;
+      if (crit == GDM_CRIT_BCE_LOGITS) {
+        loss_acc += (fmaxf(z, 0.f) - z * y + log1pf(expf(-fabsf(z)))) / cnt;
+      } else {
+        const float r = z - y;
+        loss_acc += (crit == GDM_CRIT_MSE ? r * r : fabsf(r)) / cnt;
+      }
       dbfc_acc += dl;
     }
     DSTAMP(3);
@@ -670,14 +686,15 @@ __global__ __launch_bounds__(1024) void dcnn_slab_sum(const float* __restrict__ 
 
 template <int T>
 void launch_fused(int nb, size_t lds, hipStream_t s, const float* xa, int bsplit, const float* p0, const float* p1, int B,
-                  float ya, float yb, const __bf16* pack, float* logits, float* slabs, int width, int want_grad) {
+                  float ya, float yb, const __bf16* pack, float* logits, float* slabs, int width, int want_grad,
+                  int crit) {
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)dcnn_fused_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   hipLaunchKernelGGL((dcnn_fused_kernel<T>), dim3(nb), dim3(NTHREADS), lds, s, xa, bsplit, p0, p1, B, ya, yb, pack, logits,
-                     slabs, width, want_grad);
+                     slabs, width, want_grad, crit);
 }
 
 inline size_t lds_bytes(const Dims& d) {
@@ -740,8 +757,11 @@ extern "C" size_t gdm_dcnn_fused_workspace_bytes(int B, int T, int want_grad) {
 static int dcnn_fused_impl(const float* xa, int bsplit, const float* p0, const float* p1, int B, int T, float ya,
                            float yb, const void* pack, float* logits, float* loss, int accumulate_loss,
                            int want_grad, float* dw1, float* db1, float* dw2, float* db2, float* dwfc, float* dbfc,
-                           const DcnnUpdate* upd, void* workspace, size_t workspace_bytes, void* stream) {
+                           const DcnnUpdate* upd, int criterion, void* workspace, size_t workspace_bytes,
+                           void* stream) {
   GDM_REQUIRE(pack && logits && loss && B > 0, "gdm_dcnn_fused: null pointer / empty batch");
+  GDM_REQUIRE(criterion == GDM_CRIT_BCE_LOGITS || criterion == GDM_CRIT_MSE || criterion == GDM_CRIT_L1,
+              "gdm_dcnn_fused: unknown criterion %d (GDM_CRIT_BCE_LOGITS, GDM_CRIT_MSE or GDM_CRIT_L1)", criterion);
   GDM_REQUIRE(supported(T), "gdm_dcnn_fused: roll length T=%d is outside the fused kernel's range", T);
   GDM_REQUIRE(bsplit >= 0 && bsplit <= B && (bsplit == 0 || xa) && (bsplit == B || (p0 && p1)),
               "gdm_dcnn_fused: input pointers do not cover the batch");
@@ -759,7 +779,7 @@ static int dcnn_fused_impl(const float* xa, int bsplit, const float* p0, const f
 #define GDM_DCNN_CASE(TT)                                                                                               \
     case TT:                                                                                                            \
       launch_fused<TT>(nb, lds_bytes(d), s, xa, bsplit, p0, p1, B, ya, yb, (const __bf16*)pack, logits, slabs, width,     \
-                       want_grad);                                                                                      \
+                       want_grad, criterion);                                                                           \
       break;
     GDM_DCNN_CASE(16) GDM_DCNN_CASE(18) GDM_DCNN_CASE(32) GDM_DCNN_CASE(34) GDM_DCNN_CASE(48) GDM_DCNN_CASE(50)
 #undef GDM_DCNN_CASE
@@ -782,18 +802,28 @@ static int dcnn_fused_impl(const float* xa, int bsplit, const float* p0, const f
   return GDM_OK;
 }
 
+extern "C" int gdm_dcnn_fused_crit(const float* xa, int bsplit, const float* p0, const float* p1, int B, int T,
+                                   float ya, float yb, const void* pack, float* logits, float* loss,
+                                   int accumulate_loss, int want_grad, float* dw1, float* db1, float* dw2, float* db2,
+                                   float* dwfc, float* dbfc, int criterion, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+  return dcnn_fused_impl(xa, bsplit, p0, p1, B, T, ya, yb, pack, logits, loss, accumulate_loss, want_grad, dw1, db1, dw2,
+                         db2, dwfc, dbfc, nullptr, criterion, workspace, workspace_bytes, stream);
+}
+
 extern "C" int gdm_dcnn_fused(const float* xa, int bsplit, const float* p0, const float* p1, int B, int T, float ya,
                               float yb, const void* pack, float* logits, float* loss, int accumulate_loss,
                               int want_grad, float* dw1, float* db1, float* dw2, float* db2, float* dwfc, float* dbfc,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  return dcnn_fused_impl(xa, bsplit, p0, p1, B, T, ya, yb, pack, logits, loss, accumulate_loss, want_grad, dw1, db1, dw2,
-                         db2, dwfc, dbfc, nullptr, workspace, workspace_bytes, stream);
+  return gdm_dcnn_fused_crit(xa, bsplit, p0, p1, B, T, ya, yb, pack, logits, loss, accumulate_loss, want_grad, dw1, db1,
+                             dw2, db2, dwfc, dbfc, GDM_CRIT_BCE_LOGITS, workspace, workspace_bytes, stream);
 }
 
-extern "C" int gdm_dcnn_fused_adam(const float* xa, int bsplit, const float* p0, const float* p1, int B, int T, float ya,
-                                   float yb, void* pack, float* logits, float* loss, int accumulate_loss, float* dw1,
-                                   float* db1, float* dw2, float* db2, float* dwfc, float* dbfc,
-                                   const gdm_dcnn_adam* opt, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int gdm_dcnn_fused_adam_crit(const float* xa, int bsplit, const float* p0, const float* p1, int B, int T,
+                                        float ya, float yb, void* pack, float* logits, float* loss, int accumulate_loss,
+                                        float* dw1, float* db1, float* dw2, float* db2, float* dwfc, float* dbfc,
+                                        const gdm_dcnn_adam* opt, int criterion, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
   GDM_REQUIRE(opt && opt->hyper && opt->done, "gdm_dcnn_fused_adam: optimizer record missing");
   DcnnUpdate u{};
   for (int q = 0; q < 6; ++q) {
@@ -804,5 +834,13 @@ extern "C" int gdm_dcnn_fused_adam(const float* xa, int bsplit, const float* p0,
   u.done = opt->done;
   u.pack = (__bf16*)pack;
   return dcnn_fused_impl(xa, bsplit, p0, p1, B, T, ya, yb, pack, logits, loss, accumulate_loss, 1, dw1, db1, dw2, db2,
-                         dwfc, dbfc, &u, workspace, workspace_bytes, stream);
+                         dwfc, dbfc, &u, criterion, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gdm_dcnn_fused_adam(const float* xa, int bsplit, const float* p0, const float* p1, int B, int T, float ya,
+                                   float yb, void* pack, float* logits, float* loss, int accumulate_loss, float* dw1,
+                                   float* db1, float* dw2, float* db2, float* dwfc, float* dbfc,
+                                   const gdm_dcnn_adam* opt, void* workspace, size_t workspace_bytes, void* stream) {
+  return gdm_dcnn_fused_adam_crit(xa, bsplit, p0, p1, B, T, ya, yb, pack, logits, loss, accumulate_loss, dw1, db1, dw2,
+                                  db2, dwfc, dbfc, opt, GDM_CRIT_BCE_LOGITS, workspace, workspace_bytes, stream);
 }

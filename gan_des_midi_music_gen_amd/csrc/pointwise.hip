@@ -32,6 +32,30 @@ __global__ __launch_bounds__(1024) void bce_kernel(const float* __restrict__ x, 
   if (t == 0) loss[0] = (accumulate ? loss[0] : 0.f) + red[0] / (float)n;
 }
 
+// ---------------------------------------------------------------------------------------------------- MSE / L1 loss
+// The other two criteria of model 2's loop (nn.MSELoss() / nn.L1Loss(), network_tests.py:249-250) on n logits against
+// one label: mean_i (x-y)^2 with dx = 2 (x-y) / n, mean_i |x-y| with dx = sign(x-y) / n (sign(0) = 0 as torch).  Same
+// single-workgroup, fixed-order reduction as bce_kernel.
+template <int CRIT>
+__global__ __launch_bounds__(1024) void crit_kernel(const float* __restrict__ x, float target, int n, float gscale,
+                                                    float* __restrict__ loss, float* __restrict__ dx, int accumulate) {
+  __shared__ float red[1024];
+  const int t = threadIdx.x;
+  float s = 0.f;
+  for (int i = t; i < n; i += 1024) {
+    const float r = x[i] - target;
+    s += CRIT == GDM_CRIT_MSE ? r * r : fabsf(r);
+    if (dx) dx[i] = (CRIT == GDM_CRIT_MSE ? 2.0f * r : (r > 0.f ? 1.0f : (r < 0.f ? -1.0f : 0.f))) * gscale / (float)n;
+  }
+  red[t] = s;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if (t < o) red[t] += red[t + o];
+    __syncthreads();
+  }
+  if (t == 0) loss[0] = (accumulate ? loss[0] : 0.f) + red[0] / (float)n;
+}
+
 // ------------------------------------------------------------------------------------------------------------ Adam
 // torch.optim.Adam single-tensor update (lerp form of exp_avg, sqrt/bias-correction/eps order as torch).
 template <bool VEC>
@@ -371,6 +395,25 @@ extern "C" int gdm_bce_with_logits(const float* x, float target, int n, float gr
   hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, target, n, grad_scale, loss, dx,
                      fuse_sigmoid_backward, accumulate_loss);
   GDM_LAUNCH_OK("gdm_bce_with_logits");
+  return GDM_OK;
+}
+
+extern "C" int gdm_criterion_loss(const float* x, float target, int n, int criterion, float grad_scale, float* loss,
+                                  float* dx, int accumulate_loss, void* stream) {
+  GDM_REQUIRE(x && loss, "gdm_criterion_loss: null pointer");
+  GDM_REQUIRE(n > 0 && n <= 65536, "gdm_criterion_loss: n=%d out of range (1..65536)", n);
+  GDM_REQUIRE(criterion == GDM_CRIT_BCE_LOGITS || criterion == GDM_CRIT_MSE || criterion == GDM_CRIT_L1,
+              "gdm_criterion_loss: unknown criterion %d (GDM_CRIT_BCE_LOGITS, GDM_CRIT_MSE or GDM_CRIT_L1)", criterion);
+  hipStream_t s = (hipStream_t)stream;
+  if (criterion == GDM_CRIT_BCE_LOGITS)        // the kernel of gdm_bce_with_logits itself: bit-identical by construction
+    hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(1024), 0, s, x, target, n, grad_scale, loss, dx, 0, accumulate_loss);
+  else if (criterion == GDM_CRIT_MSE)
+    hipLaunchKernelGGL(crit_kernel<GDM_CRIT_MSE>, dim3(1), dim3(1024), 0, s, x, target, n, grad_scale, loss, dx,
+                       accumulate_loss);
+  else
+    hipLaunchKernelGGL(crit_kernel<GDM_CRIT_L1>, dim3(1), dim3(1024), 0, s, x, target, n, grad_scale, loss, dx,
+                       accumulate_loss);
+  GDM_LAUNCH_OK("gdm_criterion_loss");
   return GDM_OK;
 }
 

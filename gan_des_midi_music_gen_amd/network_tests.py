@@ -223,7 +223,8 @@ class MultiModalGAN(nn.Module):
 def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per_epoch=None, fake_provider=None,
                   device=None, noise_dim=50, gen2_output_dim=20, max_beat_length=50, adj_size=(64, 64),
                   sequence_length=50, lr=0.01, model_path=None, save_dir=None, compute_dtype=None,
-                  elide_dead_backward=False, print_interval=10, seed=None, epoch_sleep=0.0, log=print):
+                  elide_dead_backward=False, print_interval=10, seed=None, epoch_sleep=0.0, log=print,
+                  criterion="bce"):
     """The body of ``TestMultiModalGAN.test_training_loop`` (network_tests.py:209-350) on the fused MI355X step.
 
     train_loader: iterable of (piano_roll, durations, beats) batches (the reference's MaestroDatasetPickle loader,
@@ -232,6 +233,8 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
         (DES core + batched log -> MIDI -> piano-roll kernel); None -> synthetic rolls.
     save_dir: if given, per-epoch ``losses/*.pkl`` and ``models/mmgan_{a}_{b}_epoch_{e}.pth`` are written there with
         the reference's file names; model_path: state_dict to resume from (optimizer state is not saved, as upstream).
+    criterion: "bce" | "mse" | "l1" -- the reference picks one by moving a comment (network_tests.py:248-250:
+        nn.BCEWithLogitsLoss(), nn.MSELoss(), nn.L1Loss()).
     Returns (disc_losses, gen_losses) of the last epoch, like the reference.
     """
     from .train import MmganTrainer, StepLR
@@ -250,7 +253,8 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
     if model_path is not None and os.path.isfile(model_path):
         mmgan.load_state_dict(torch.load(model_path, map_location=device, weights_only=True))
         log(f"Loaded model from {model_path}")
-    trainer = MmganTrainer(mmgan, lr=lr, compute_dtype=compute_dtype, elide_dead_backward=elide_dead_backward)
+    trainer = MmganTrainer(mmgan, lr=lr, compute_dtype=compute_dtype, elide_dead_backward=elide_dead_backward,
+                           criterion=criterion)
     disc_scheduler = StepLR(trainer, step_size=30, gamma=0.1)   # the generator optimizer never has gradients
     count = total_failures = total_seen = 0
     disc_losses, gen_losses = [], []

@@ -10,7 +10,7 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, BF16, F32, GdmError, check  # noqa: F401
+from ._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, BF16, CRITERIA, F32, GdmError, check  # noqa: F401
 
 _TORCH_DT = {F32: torch.float32, BF16: torch.bfloat16}
 
@@ -165,6 +165,31 @@ def bce_with_logits(x, target, *, grad_scale=1.0, want_grad=True, fuse_sigmoid_b
     _call("gdm_bce_with_logits", _p(x), float(target), x.numel(), float(grad_scale), _p(loss), _p(dx),
                                            1 if fuse_sigmoid_backward else 0, 1 if accumulate_loss else 0, _stream())
     return loss, dx
+
+
+def criterion_id(criterion):
+    """GDM_CRIT_* of one of model 2's criterion names ("bce", "mse", "l1"); ValueError for anything else."""
+    try:
+        return CRITERIA[criterion]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown criterion {criterion!r}: one of {sorted(CRITERIA)}") from None
+
+
+def criterion_loss(x, target, criterion, *, loss_out, dx_out=None, accumulate_loss=False, want_grad=True,
+                   grad_scale=1.0):
+    """Mean loss of n logits against one label under model 2's criterion ("bce" | "mse" | "l1").  Fills ``loss_out``
+    (adds to it with ``accumulate_loss``); returns (loss_out, dx or None).  x: (n,) fp32 contiguous."""
+    crit = criterion_id(criterion)
+    _need_gpu(x, loss_out, dx_out)
+    x = x.reshape(-1)
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    assert loss_out.dtype == torch.float32 and loss_out.numel() >= 1
+    dx = dx_out if dx_out is not None else (torch.empty_like(x) if want_grad else None)
+    if dx is not None:
+        assert dx.is_contiguous() and dx.numel() == x.numel() and dx.dtype == torch.float32
+    _call("gdm_criterion_loss", _p(x), float(target), x.numel(), crit, float(grad_scale), _p(loss_out), _p(dx),
+          1 if accumulate_loss else 0, _stream())
+    return loss_out, dx
 
 
 def adam_step(p, g, m, v, step, lr, beta1, beta2, eps, grad_scale=1.0):
@@ -707,13 +732,15 @@ def dcnn_pack(w1, b1, w2, b2, wfc, bfc, t, out=None):
 
 
 def dcnn_fused(xa, planes, t, ya, yb, pack, *, loss_out, accumulate_loss=False, want_grad=True, grad_out=None,
-               adam=None):
-    """DiscriminatorCNN forward + BCE loss (+ backward) in one persistent kernel.
+               adam=None, criterion="bce"):
+    """DiscriminatorCNN forward + loss (+ backward) in one persistent kernel.  criterion: "bce" (with logits), "mse"
+    or "l1" on the logits -- the three criteria of the reference's loop.
 
     xa: (Ba,2,128,T) fp32 contiguous or None (label ya); planes: (p0, p1) each (Bb,128,T) or None (label yb).
     grad_out: 6 tensors (dw1, db1, dw2, db2, dwfc, dbfc) to fill.  Returns (logits (B,), grads or None).
     adam = dict(params=[6 tensors], exp_avg=[6], exp_avg_sq=[6], hyper=(8,) fp32, done=(1,) int32): the optimizer step
     and the refresh of ``pack`` ride the gradient's final summation (gdm_dcnn_fused_adam; one rank only)."""
+    crit = criterion_id(criterion)
     _need_gpu(xa, pack, loss_out)
     ba = 0 if xa is None else xa.shape[0]
     p0 = p1 = None
@@ -743,6 +770,10 @@ def dcnn_fused(xa, planes, t, ya, yb, pack, *, loss_out, accumulate_loss=False, 
     nb = lib.gdm_dcnn_fused_workspace_bytes(b, int(t), 1 if want_grad else 0)
     ws = workspace(nb, dev)
     gp = [_p(g) for g in grads] if grads else [None] * 6
+    # "bce" keeps the original entry points (they forward with GDM_CRIT_BCE_LOGITS; bench.py's roofline leg brackets
+    # them by name); the other criteria go through the *_crit ones
+    sel = () if crit == CRITERIA["bce"] else (crit,)
+    suffix = "_crit" if sel else ""
     if adam is not None:
         assert want_grad, "the fused optimizer step needs the gradient"
         rec = _lib.DcnnAdam()
@@ -757,11 +788,11 @@ def dcnn_fused(xa, planes, t, ya, yb, pack, *, loss_out, accumulate_loss=False, 
         _need_gpu(hyper, done)
         assert hyper.numel() == 8 and hyper.dtype == torch.float32 and done.numel() == 1 and done.dtype == torch.int32
         rec.hyper, rec.done = hyper.data_ptr(), done.data_ptr()
-        _call("gdm_dcnn_fused_adam", _p(xa), ba, _p(p0), _p(p1), b, int(t), float(ya), float(yb), _p(pack), _p(logits),
-              _p(loss_out), 1 if accumulate_loss else 0, *gp, ctypes.byref(rec), _p(ws), nb, _stream())
+        _call("gdm_dcnn_fused_adam" + suffix, _p(xa), ba, _p(p0), _p(p1), b, int(t), float(ya), float(yb), _p(pack),
+              _p(logits), _p(loss_out), 1 if accumulate_loss else 0, *gp, ctypes.byref(rec), *sel, _p(ws), nb, _stream())
         return logits, grads
-    _call("gdm_dcnn_fused", _p(xa), ba, _p(p0), _p(p1), b, int(t), float(ya), float(yb), _p(pack), _p(logits),
-          _p(loss_out), 1 if accumulate_loss else 0, 1 if want_grad else 0, *gp, _p(ws), nb, _stream())
+    _call("gdm_dcnn_fused" + suffix, _p(xa), ba, _p(p0), _p(p1), b, int(t), float(ya), float(yb), _p(pack), _p(logits),
+          _p(loss_out), 1 if accumulate_loss else 0, 1 if want_grad else 0, *gp, *sel, _p(ws), nb, _stream())
     return logits, grads
 
 

@@ -724,10 +724,15 @@ class MmganTrainer(_TrainerBase):
     bf16 mode (and a roll length the kernel supports, T = 50 does): the discriminator's forward, loss and backward run
     as ONE persistent kernel per pass that keeps a sample and all its activations in LDS (``ops.dcnn_fused``), and each
     generator block is one fused Linear+BatchNorm+Sigmoid launch.  fp32 mode: GEMM + im2col lowering (parity path).
+
+    ``criterion``: which of the reference's three criteria (network_tests.py:248-250) both steps apply to the logits --
+    "bce" (nn.BCEWithLogitsLoss(), the line that is active upstream), "mse" (nn.MSELoss()) or "l1" (nn.L1Loss()).
     """
 
     def __init__(self, mmgan, lr=0.01, betas=(0.9, 0.999), eps=1e-8, compute_dtype=None, elide_dead_backward=False,
-                 process_group=None, fuse_optimizer=True, exact_bn=False):
+                 process_group=None, fuse_optimizer=True, exact_bn=False, criterion="bce"):
+        ops.criterion_id(criterion)               # ValueError for a name the library does not know
+        self.criterion = criterion
         self.mm = mmgan
         self.fuse_optimizer = fuse_optimizer      # one rank, fused bf16 path: Adam + re-pack inside the gradient's slab sum
         # N > 1 ranks: generators' BatchNorm1d statistics over the GLOBAL batch (per-layer exchange of Welford partials)
@@ -793,6 +798,12 @@ class MmganTrainer(_TrainerBase):
 
     def _fused_ok(self, t):
         return self.dt == ops.BF16 and ops.dcnn_fused_supported(t)
+
+    def _criterion_loss(self, logits, target, **kw):
+        """The criterion on one label half of the unfused path (the fused kernel applies it itself)."""
+        if self.criterion == "bce":
+            return ops.bce_with_logits(logits, target, **kw)
+        return ops.criterion_loss(logits, target, self.criterion, **kw)
 
     def _fused_adam_record(self):
         """What ops.dcnn_fused needs to apply Adam itself (one rank): per-parameter views of the flat parameter / moment
@@ -953,7 +964,8 @@ class MmganTrainer(_TrainerBase):
             # One rank: disc_opt.step() (308) and the refresh of the packed weights ride the gradient's final summation
             # (slab sum -> adam_prep -> Adam -> re-pack were four launches on the iteration's critical chain).
             ops.dcnn_fused(fa, (Fn._f32c(piano_roll), Fn._f32c(durations)), t, 0.0, 1.0, self._pack,
-                           loss_out=self.loss_d, grad_out=gv, adam=self._fused_adam_record())
+                           loss_out=self.loss_d, grad_out=gv, adam=self._fused_adam_record(),
+                           criterion=self.criterion)
             if gen_late:
                 generators()
         else:
@@ -966,8 +978,8 @@ class MmganTrainer(_TrainerBase):
             logits, saved = Fn.dcnn_forward(x, w1, b1, w2, b2, wf, bf, dt)
             lg = logits.view(-1)
             dl = torch.empty(2 * b, dtype=torch.float32, device=dev)
-            ops.bce_with_logits(lg[:b], 0.0, loss_out=self.loss_d, dx_out=dl[:b])
-            ops.bce_with_logits(lg[b:], 1.0, loss_out=self.loss_d, dx_out=dl[b:], accumulate_loss=True)
+            self._criterion_loss(lg[:b], 0.0, loss_out=self.loss_d, dx_out=dl[:b])
+            self._criterion_loss(lg[b:], 1.0, loss_out=self.loss_d, dx_out=dl[b:], accumulate_loss=True)
             grads = Fn.dcnn_backward(saved, dl, w2, wf, dt)[:6]
             for gview, g in zip(gv, grads):
                 gview.copy_(g.view(gview.shape))
@@ -1001,18 +1013,19 @@ class MmganTrainer(_TrainerBase):
             fake_b = fake_b(*self._gen_b)      # the generators' second forward ran at the start of the iteration
         if fused:
             if self.elide:
-                ops.dcnn_fused(Fn._f32c(fake_b), None, t, 1.0, 1.0, self._pack, loss_out=self.loss_g, want_grad=False)
+                ops.dcnn_fused(Fn._f32c(fake_b), None, t, 1.0, 1.0, self._pack, loss_out=self.loss_g, want_grad=False,
+                               criterion=self.criterion)
             else:   # dead values (only D's .grad in the reference, wiped by the next zero_grad): scratch buffers
                 if getattr(self, "_scratch_grads", None) is None:
                     self._scratch_grads = [torch.empty_like(g) for g in gv]
                 ops.dcnn_fused(Fn._f32c(fake_b), None, t, 1.0, 1.0, self._pack, loss_out=self.loss_g,
-                               grad_out=self._scratch_grads)
+                               grad_out=self._scratch_grads, criterion=self.criterion)
         else:
             logits_g, saved_g = Fn.dcnn_forward(fake_b, w1, b1, w2, b2, wf, bf, dt)
             if self.elide:
-                ops.bce_with_logits(logits_g.view(-1), 1.0, loss_out=self.loss_g, want_grad=False)
+                self._criterion_loss(logits_g.view(-1), 1.0, loss_out=self.loss_g, want_grad=False)
             else:
-                _, dlg = ops.bce_with_logits(logits_g.view(-1), 1.0, loss_out=self.loss_g)
+                _, dlg = self._criterion_loss(logits_g.view(-1), 1.0, loss_out=self.loss_g)
                 Fn.dcnn_backward(saved_g, dlg, w2, wf, dt)     # dead values (only D's .grad in the reference)
         if getattr(self, "_gen_join_pending", False):
             main = torch.cuda.current_stream()

@@ -26,6 +26,8 @@ extern "C" {
 enum { GDM_F32 = 0, GDM_BF16 = 1 };
 enum { GDM_ACT_NONE = 0, GDM_ACT_RELU = 1, GDM_ACT_LEAKY = 2, GDM_ACT_SIGMOID = 3 };
 enum { GDM_OK = 0, GDM_EINVAL = -1, GDM_ELAUNCH = -2, GDM_EWORKSPACE = -3 };
+/* the three criteria of model 2's training loop (network_tests.py:248-250: BCEWithLogitsLoss, MSELoss, L1Loss) */
+enum { GDM_CRIT_BCE_LOGITS = 0, GDM_CRIT_MSE = 1, GDM_CRIT_L1 = 2 };
 
 /* ---- probes -------------------------------------------------------------------------------------------------- */
 const char* gdm_last_error(void);
@@ -55,6 +57,15 @@ int gdm_gemm(const void* A, int a_dtype, int64_t sam, int64_t sak,
  * SIMNN.py:314).  n <= 65536 (one workgroup, fixed-order reduction => deterministic).                              */
 int gdm_bce_with_logits(const float* x, float target, int n, float grad_scale, float* loss, float* dx,
                         int fuse_sigmoid_backward, int accumulate_loss, void* stream);
+
+/* The criterion of model 2's loop as a choice (network_tests.py:248-250, applied at 304-305 and 313; aten::mse_loss /
+ * aten::l1_loss, mean): the contract of gdm_bce_with_logits without the sigmoid-fusion flag.  On n logits x and one
+ * label y:  GDM_CRIT_MSE  loss = mean((x-y)^2), dx[i] = grad_scale * 2 (x[i]-y) / n;
+ *           GDM_CRIT_L1   loss = mean(|x-y|),   dx[i] = grad_scale * sign(x[i]-y) / n, sign(0) = 0 as torch;
+ *           GDM_CRIT_BCE_LOGITS  bit-identical to gdm_bce_with_logits(..., fuse_sigmoid_backward = 0, ...).
+ * One workgroup, fixed-order reduction, n <= 65536; an unknown criterion is GDM_EINVAL.                             */
+int gdm_criterion_loss(const float* x, float target, int n, int criterion, float grad_scale, float* loss, float* dx,
+                       int accumulate_loss, void* stream);
 
 /* ---- optimizer (torch.optim.Adam single-tensor step, SIMNN.py:258-259,316; network_tests.py:253-254,308) -------
  * One flat fp32 range: p, g, m (exp_avg), v (exp_avg_sq) of n elements; `step` is the 1-based step count.
@@ -316,6 +327,18 @@ int gdm_dcnn_fused_adam(const float* xa, int bsplit, const float* p0, const floa
                         void* pack, float* logits, float* loss, int accumulate_loss, float* dw1, float* db1, float* dw2,
                         float* db2, float* dwfc, float* dbfc, const gdm_dcnn_adam* opt, void* workspace,
                         size_t workspace_bytes, void* stream);
+/* Both passes with the criterion of network_tests.py:248-250 as an argument (GDM_CRIT_*; applied to each label half
+ * at 304-305 and to the generator step's logits at 313): per half of n logits with label y, MSE is mean((z-y)^2) with
+ * dz = 2 (z-y) / n, L1 is mean(|z-y|) with dz = sign(z-y) / n (sign(0) = 0 as torch).  gdm_dcnn_fused and
+ * gdm_dcnn_fused_adam are these with GDM_CRIT_BCE_LOGITS; an unknown criterion is GDM_EINVAL.                        */
+int gdm_dcnn_fused_crit(const float* xa, int bsplit, const float* p0, const float* p1, int B, int T, float ya, float yb,
+                        const void* pack, float* logits, float* loss, int accumulate_loss, int want_grad, float* dw1,
+                        float* db1, float* dw2, float* db2, float* dwfc, float* dbfc, int criterion, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int gdm_dcnn_fused_adam_crit(const float* xa, int bsplit, const float* p0, const float* p1, int B, int T, float ya,
+                             float yb, void* pack, float* logits, float* loss, int accumulate_loss, float* dw1,
+                             float* db1, float* dw2, float* db2, float* dwfc, float* dbfc, const gdm_dcnn_adam* opt,
+                             int criterion, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- deterministic discrete-event simulator core (host code; SIMULATOR/simulation_v3.py:25-74, 426-743) -------------
  * One run of Sim(adj, distributions, queue_list, seeds=[seed], logging_mode='Music').run(number_of_customers) for 'normal'
