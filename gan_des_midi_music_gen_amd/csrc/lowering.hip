@@ -110,6 +110,10 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const void* __restric
     if (v1 > m) { m = v1; pos = 1; }
     if (v2 > m) { m = v2; pos = 2; }
     if (v3 > m) { m = v3; pos = 3; }
+    // store the element idx names, bit for bit: without NaN semantics the compare-and-keep chain above becomes
+    // v_max_f32, which gives +0 for max(-0, +0) whichever came first (the comparisons themselves do not care)
+    const uint32_t b0 = __float_as_uint(v0), b1 = __float_as_uint(v1), b2 = __float_as_uint(v2), b3 = __float_as_uint(v3);
+    m = __uint_as_float(pos == 0 ? b0 : (pos == 1 ? b1 : (pos == 2 ? b2 : b3)));
     store_from_f32(dst, sd, i, m);
     if (idx) idx[i] = (uint8_t)pos;
   }

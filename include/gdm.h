@@ -381,7 +381,8 @@ int gdm_permute_pc(const void* src, int src_dtype, int B, int P, int C, void* ds
 
 /* aten::max_pool2d_with_indices / its backward, kernel 2 stride 2 (floor), channels-last (B,H,W,C) -> (B,H/2,W/2,C)
  * (F.max_pool2d(x, 2, 2) of the SimNN branch, GAN_DES/SIMNN.py:156,158).  idx: window position 0..3 of the first
- * maximum in scan order, one byte per output element (NULL: forward only).                                          */
+ * maximum in scan order, one byte per output element (NULL: forward only).  dst holds that very element, bit for bit
+ * (a window of -0.0 and +0.0 gives whichever comes first, like ATen).                                                */
 int gdm_maxpool2_fwd(const void* src, int dtype, int B, int H, int W, int C, void* dst, uint8_t* idx_or_null,
                      void* stream);
 int gdm_maxpool2_bwd(const void* dout, int dtype, const uint8_t* idx, int B, int H, int W, int C, void* dx,
