@@ -22,14 +22,17 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc",
          # no NaN handling in the arithmetic: without it every MFMA result that reaches an fmaxf is first
          # canonicalised (v_max_f32 x, x, x) -- 16 extra VALU per 16 pooled pixels in the issue-bound conv epilogues
          "-fno-honor-nans"]
-# per-source additions to FLAGS (experiments: GDM_HIPCC_FILE_FLAGS="gemm_bf16.hip:-mllvm,-amdgpu-sched-strategy=max-ilp")
+# per-source additions to FLAGS, keyed by file name (experiments:
+# GDM_HIPCC_FILE_FLAGS="gemm_bf16_kt64_bf16a.hip:-mllvm,-amdgpu-sched-strategy=max-ilp"; the gemm_bf16_fast kernels are
+# compiled in gemm_bf16_kt{32,64}_{bf16,f32}a.hip, the trunk's in simnn_conv1.hip, simnn_conv2_{fwd,bwd_data,bwd_weight}.hip)
 PER_FILE_FLAGS = {}
 for _spec in os.environ.get("GDM_HIPCC_FILE_FLAGS", "").split():
     _name, _, _fl = _spec.partition(":")
     PER_FILE_FLAGS[_name] = _fl.split(",")
 EXPERIMENT = os.environ.get("GDM_HIPCC_FLAGS", "").split()     # experiment switches (-D...), empty for the shipped build
-if EXPERIMENT:
-    # an instrumented / variant build says so: gdm_build_flavor() returns 1 and bench.py refuses to measure it
+if EXPERIMENT or PER_FILE_FLAGS:
+    # an instrumented / variant build says so: gdm_build_flavor() returns 1 and bench.py refuses to measure it; only
+    # such a build reads the GDM_*_CAP / GDM_BW_NSEG / GDM_GEMM_VARIANT overrides from the environment
     FLAGS += EXPERIMENT + ["-DGDM_EXPERIMENT_BUILD=1"]
 STAMP = os.path.join(OBJ, "flags.txt")
 

@@ -1,5 +1,5 @@
 // Adam with on-the-fly transposition for a parameter whose gradient / operand copy live in the (N, P, C) layout
-// (model 1's fc1.weight): the tile body shared by pointwise.hip's stand-alone kernel and simnn_disc.hip's one-launch
+// (model 1's fc1.weight): the tile body shared by pointwise.hip's stand-alone kernel and simnn_adam.hip's one-launch
 // optimizer step.
 #pragma once
 #include "gdm_common.h"

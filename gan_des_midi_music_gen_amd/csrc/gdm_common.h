@@ -34,6 +34,20 @@ void gdm_set_error(const char* fmt, ...);
     }                                                                              \
   } while (0)
 
+// A tuned constant that tools/ sweeps may override from the environment -- in experiment builds only (build.py:
+// GDM_HIPCC_FLAGS / GDM_HIPCC_FILE_FLAGS with a GDM_BUILD_TAG; never shipped or benchmarked).  The shipped library
+// uses the constant and reads no environment variable.
+#ifdef GDM_EXPERIMENT_BUILD
+#include <stdlib.h>
+static inline int gdm_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e && e[0] ? atoi(e) : dflt;
+}
+#define GDM_TUNABLE(env_name, dflt) gdm_env_int(env_name, dflt)
+#else
+#define GDM_TUNABLE(env_name, dflt) (dflt)
+#endif
+
 static inline bool gdm_dtype_ok(int d) { return d == GDM_F32 || d == GDM_BF16; }
 static inline size_t gdm_dtype_size(int d) { return d == GDM_BF16 ? 2 : 4; }
 

@@ -1,7 +1,7 @@
 // Mel-spectrogram featuriser (reference GAN_DES/util.py:37-61 -> torchaudio MelSpectrogram + AmplitudeToDB): the step
 // that produces model 1's discriminator input.  The two contractions (DFT and mel filter bank) are fp32 GEMMs
 // (gdm_gemm, exact-fp32 MFMA); this file holds the three data-movement / pointwise kernels around them.
-#include "gdm_common.h"
+#include "buffer_ops.h"
 
 namespace {
 
@@ -110,11 +110,7 @@ extern "C" int gdm_power_to_db(const float* mel, int B, int frames, int n_mels, 
   GDM_REQUIRE(mel && out && B > 0 && frames > 0 && n_mels > 0 && amin > 0.f, "gdm_power_to_db: bad arguments");
   const size_t sm = (size_t)n_mels * (frames + 1) * sizeof(float);
   GDM_REQUIRE(sm <= 150 * 1024, "gdm_power_to_db: a %d x %d window does not fit the LDS staging (150 KB)", n_mels, frames);
-  static bool attr_done = false;
-  if (!attr_done) {
-    attr_done = true;
-    (void)hipFuncSetAttribute((const void*)power_to_db_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-  }
+  allow_lds(power_to_db_kernel, 150 * 1024);
   hipLaunchKernelGGL(power_to_db_kernel, dim3(B), dim3(1024), sm, (hipStream_t)stream, mel, frames, n_mels, top_db, amin,
                      out);
   GDM_LAUNCH_OK("gdm_power_to_db");

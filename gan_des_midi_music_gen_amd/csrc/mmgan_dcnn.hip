@@ -15,8 +15,7 @@
 //   conv2 dW    M=32 oc,  N=16 ci per tap,      K=pixels                  both operands via ds_read_b64_tr_b16
 //   conv2 dX    M=16 ci,  N=16 same-parity pixels of a row, K=128 (2x2 taps of the parity class, 32 oc)
 //   conv1 dW    M=16 oc,  N=2x16 (kh,kw,ci),    K=pixels                  both operands via ds_read_b64_tr_b16
-#include <cstdlib>
-#include "gdm_common.h"
+#include "buffer_ops.h"
 
 namespace {
 
@@ -688,11 +687,7 @@ template <int T>
 void launch_fused(int nb, size_t lds, hipStream_t s, const float* xa, int bsplit, const float* p0, const float* p1, int B,
                   float ya, float yb, const __bf16* pack, float* logits, float* slabs, int width, int want_grad,
                   int crit) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)dcnn_fused_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_lds(dcnn_fused_kernel<T>, 160 * 1024);
   hipLaunchKernelGGL((dcnn_fused_kernel<T>), dim3(nb), dim3(NTHREADS), lds, s, xa, bsplit, p0, p1, B, ya, yb, pack, logits,
                      slabs, width, want_grad, crit);
 }
@@ -711,7 +706,7 @@ inline int n_blocks(int B) {
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       cus = 256;
     cap = cus * 7 / 8 > 0 ? cus * 7 / 8 : 1;
-    if (const char* e = getenv("GDM_DCNN_CAP")) { if (atoi(e) > 0) cap = atoi(e); }     // experiments only
+    cap = GDM_TUNABLE("GDM_DCNN_CAP", cap);
   }
   // the fewest workgroups that finish in the same number of sample rounds (512 samples on 224 workgroups take three
   // rounds; so do 171, which leaves 85 CUs instead of 32 to the kernels running beside this one)

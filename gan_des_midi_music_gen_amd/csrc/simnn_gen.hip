@@ -14,7 +14,7 @@
 // the GEMM + col2im path it replaces).  A workgroup = (class, group of S samples); it also leaves an exact two-pass
 // (mean, M2) partial per output channel, merged in fixed order by the existing bn_finalize.  Activations stay
 // channels-last fp32 in HBM between the kernels (8 MB at most).
-#include "gdm_common.h"
+#include "buffer_ops.h"
 
 namespace {
 
@@ -511,21 +511,11 @@ __global__ __launch_bounds__(512) void gen_eval_kernel(const gen_eval_params p) 
   }
 }
 
-template <typename K>
-inline void allow_dyn_lds(K kernel, size_t bytes) {
-  static const void* done[4];
-  static int n_done = 0;
-  for (int i = 0; i < n_done; ++i)
-    if (done[i] == (const void*)kernel) return;
-  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (n_done < 4) done[n_done++] = (const void*)kernel;
-}
-
 template <int CIN, int COUT, int IH, int S>
 int launch_convt_s2(const float* yin, const float* mean, const float* invstd, const float* gamma, const float* beta,
                     int B, const __bf16* wp, float* yout, float* ws, hipStream_t s) {
   const size_t sm = ((size_t)S * (IH + 2) * (IH + 2) * (CIN + 8) + (size_t)COUT * (4 * CIN + 8)) * 2 + (size_t)4 * COUT * 4;
-  allow_dyn_lds(convt_s2_bn_kernel<CIN, COUT, IH, S>, sm);
+  allow_lds(convt_s2_bn_kernel<CIN, COUT, IH, S>, sm);
   const int groups = (B + S - 1) / S;
   hipLaunchKernelGGL((convt_s2_bn_kernel<CIN, COUT, IH, S>), dim3(4 * groups), dim3(256), sm, s, yin, mean, invstd, gamma,
                      beta, B, wp, yout, ws);
@@ -553,7 +543,7 @@ extern "C" int gdm_simnn_gen_first(const float* noise, int B, int noise_dim, con
   GDM_REQUIRE(B > 1 && B <= 256 && noise_dim >= 1 && noise_dim <= L1_K && ((uintptr_t)y1 & 15) == 0,
               "gdm_simnn_gen_first: batch %d outside 2..256 (the workgroup owns the whole batch) or noise_dim > %d", B, L1_K);
   const size_t sm = (size_t)(256 + 16 * L1_CH) * (L1_K + 8) * 2;
-  allow_dyn_lds(gen_l1_kernel, sm);
+  allow_lds(gen_l1_kernel, sm);
   hipLaunchKernelGGL(gen_l1_kernel, dim3(128 / L1_CH), dim3(256), sm, (hipStream_t)stream, noise, B, noise_dim,
                      (const __bf16*)pack + GP_W2 + GP_W3, y1, momentum, eps, running_mean, running_var,
                      num_batches_tracked, save_mean, save_invstd);

@@ -52,9 +52,20 @@ def test_ops_refuse_cpu_tensors():
         ops.adam_step(torch.zeros(4), torch.zeros(4), torch.zeros(4), torch.zeros(4), 1, 1e-3, 0.9, 0.999, 1e-8)
 
 
+ENV_OVERRIDES = (b"GDM_BD_CAP", b"GDM_BW_CAP", b"GDM_BW_NSEG", b"GDM_C1_CAP", b"GDM_C2F_CAP", b"GDM_GEMM_VARIANT",
+                 b"GDM_DCNN_CAP")
+
+
+def test_shipped_library_reads_no_environment_override(lib_path):
+    """The grid-cap / variant overrides of tools/ sweeps exist only in experiment builds (GDM_TUNABLE, gdm_common.h):
+    the shipped library holds none of their names."""
+    blob = open(lib_path, "rb").read()
+    assert [n for n in ENV_OVERRIDES if n in blob] == []
+
+
 def test_build_stamp_covers_flags_and_compiler(monkeypatch):
     """build.py rebuilds every object when the flag set (or the compiler) differs from the one recorded beside the
-    objects, and an experiment flag set marks the library (gdm_build_flavor)."""
+    objects, and an experiment flag set -- global or for single files -- marks the library (gdm_build_flavor)."""
     import importlib
     from gan_des_midi_music_gen_amd import build
     shipped = build._flags_stamp(build._hipcc())
@@ -67,8 +78,14 @@ def test_build_stamp_covers_flags_and_compiler(monkeypatch):
         assert "-DGDM_STAMPS" in variant._flags_stamp(variant._hipcc()) and "-DGDM_EXPERIMENT_BUILD=1" in variant.FLAGS
         assert variant.LIB.endswith("libgdm_hip_stamp_test.so") and variant.OBJ.endswith("_obj_stamp_test")
         assert variant._flags_stamp(variant._hipcc()) != shipped
-    finally:
         monkeypatch.delenv("GDM_HIPCC_FLAGS")
+        monkeypatch.setenv("GDM_HIPCC_FILE_FLAGS", "gemm_bf16_kt64_bf16a.hip:-mllvm,-amdgpu-sched-strategy=max-ilp")
+        variant = importlib.reload(build)
+        assert variant.PER_FILE_FLAGS == {"gemm_bf16_kt64_bf16a.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
+        assert "-DGDM_EXPERIMENT_BUILD=1" in variant.FLAGS and variant._flags_stamp(variant._hipcc()) != shipped
+    finally:
+        monkeypatch.delenv("GDM_HIPCC_FLAGS", raising=False)
+        monkeypatch.delenv("GDM_HIPCC_FILE_FLAGS", raising=False)
         monkeypatch.delenv("GDM_BUILD_TAG")
         importlib.reload(build)
     from gan_des_midi_music_gen_amd import _lib

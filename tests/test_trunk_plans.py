@@ -26,7 +26,8 @@ def _plans(lib, b, h, w):
     h1, w1 = (h + 1) // 2, (w + 1) // 2
     fused = tr.bd_plan(b, h1, w1, True)
     bw = tr.bw_plan(b, h1, w1)
-    # the library's own plan: workgroups = workspace bytes / slab bytes - 65 (simnn_disc.hip:2118, :2164)
+    # the library's own plan: workgroups = workspace bytes / slab bytes - 65 (the *_workspace_bytes
+    # functions of simnn_conv2_bwd_data.hip, simnn_conv2_bwd_weight.hip and simnn_conv1.hip)
     assert lib.gdm_simnn_conv2_bwd_fused_workspace_bytes(b, h1, w1) // 320 - 65 == fused["blocks"]
     assert lib.gdm_simnn_conv2_bwd_weight_workspace_bytes(b, h1, w1) // 18560 - 65 == bw["blocks"]
     assert lib.gdm_simnn_conv1_bwd_weight_workspace_bytes(b, h, w) // 320 - 65 == tr.conv1_slabs(b, h, w)
@@ -81,9 +82,27 @@ def test_shape_table_reaches_every_regime(lib):
     assert "fp32" in tr.DTYPES and "bf16" in tr.DTYPES
 
 
+SWEEP_B = list(range(1, 41)) + [48, 64, 96, 100, 127, 128, 129, 192, 200, 255, 256, 257, 300, 384, 400, 511, 512, 513, 600]
+SWEEP_HW = [(128, 256), (128, 216), (128, 64), (40, 130), (5, 7), (4, 4)]
+
+
+def test_plan_sweep_library_equals_mirror(lib):
+    """The one segment plan of csrc/simnn_trunk.h (seg_plan, behind the three host-only *_workspace_bytes functions) and
+    conv1_slabs give the workgroup counts of trunk_ref's mirrors for every batch size up to 40, around 256 and 512 and
+    up to 600, at the production, reference, narrow, segmented and tiny geometries."""
+    for h, w in SWEEP_HW:
+        h1, w1 = (h + 1) // 2, (w + 1) // 2
+        for b in SWEEP_B:
+            got = (lib.gdm_simnn_conv2_bwd_fused_workspace_bytes(b, h1, w1) // 320 - 65,
+                   lib.gdm_simnn_conv2_bwd_weight_workspace_bytes(b, h1, w1) // 18560 - 65,
+                   lib.gdm_simnn_conv1_bwd_weight_workspace_bytes(b, h, w) // 320 - 65)
+            want = (tr.bd_plan(b, h1, w1, True)["blocks"], tr.bw_plan(b, h1, w1)["blocks"], tr.conv1_slabs(b, h, w))
+            assert got == want, (b, h, w, got, want)
+
+
 def test_fc1_gemm_paths():
     """The long-K fc1 products split K and take the deep variant; K = 55296 ends in a short slab (mirrors of
-    ops.default_split_k, gemm.hip:210-214, gemm_bf16.hip:418-422)."""
+    ops.default_split_k, gemm.hip:210-214, gemm_bf16.hip gdm_gemm_bf16_fast_launch)."""
     for m, k in ((512, 65536), (256, 65536), (256, 55296), (32, 55296)):
         p = gemm_path(m, 128, k, BF16)
         assert p["split"] > 1 and p["fast"] and p["variant"] == 1, (m, k, p)

@@ -1,4 +1,5 @@
-"""float64 references, code decoders and a per-element checker for model 1's convolution trunk (csrc/simnn_disc.hip).
+"""float64 references, code decoders and a per-element checker for model 1's convolution trunk (csrc/simnn_trunk.h and the
+simnn_conv*.hip / simnn_slab_sum.hip files it lists).
 
 A plain module next to helpers.py: the GPU tests of tests/test_simnn_trunk_batch_gpu.py and the CPU tests of
 tests/test_trunk_plans.py import it.
@@ -45,17 +46,17 @@ import math
 import torch
 import torch.nn.functional as F
 
-# ----------------------------------------------------------------------------------- plan mirrors (simnn_disc.hip)
-ROWS = 4                # simnn_disc.hip:484  conv-output rows per step / tile
-COLS = 64               # simnn_disc.hip:58   conv-output columns per tile (conv2 forward, backward weight)
-BD_COLS = 64            # simnn_disc.hip:974  columns per backward-data item
-BD_CAP_FUSE = 512       # simnn_disc.hip:1902 tuned_cap("GDM_BD_CAP", 512)
-BD_CAP = 768            # simnn_disc.hip:1903
-BW_CAP = 768            # simnn_disc.hip:1915 tuned_cap("GDM_BW_CAP", 768)
-C2F_CAP = 768           # simnn_disc.hip:2057 tuned_cap("GDM_C2F_CAP", 768)
-C1_CAP = 1536           # simnn_disc.hip:1959 tuned_cap("GDM_C1_CAP", 1536)
-C1_SLABS_CAP = 1024     # simnn_disc.hip:1877 conv1_slabs
-C1BD_CAP = 8192         # simnn_disc.hip:2005 conv1 input-gradient blocks
+# ----------------------------------------------------------------------------------- plan mirrors (csrc/simnn_trunk.h)
+ROWS = 4                # simnn_trunk.h ROWS: conv-output rows per step / tile
+COLS = 64               # simnn_trunk.h COLS: conv-output columns per tile (conv2 forward, backward weight)
+BD_COLS = 64            # simnn_conv2_bwd_data.hip BD_COLS: columns per backward-data item
+BD_CAP_FUSE = 512       # simnn_trunk.h cap::c2_bwd_fused
+BD_CAP = 768            # simnn_trunk.h cap::c2_bwd_data
+BW_CAP = 768            # simnn_trunk.h cap::c2_bwd_weight
+C2F_CAP = 768           # simnn_trunk.h cap::c2_fwd
+C1_CAP = 1536           # simnn_trunk.h cap::c1_fwd
+C1_SLABS_CAP = 1024     # simnn_trunk.h cap::c1_slabs (simnn_conv1.hip conv1_slabs)
+C1BD_CAP = 8192         # simnn_trunk.h cap::c1_bwd_data: conv1 input-gradient blocks
 PLAN_ENV = ("GDM_BD_CAP", "GDM_BW_CAP", "GDM_BW_NSEG", "GDM_C2F_CAP", "GDM_C1_CAP")
 
 # (B, H, W, bsplit, what) -- the shape table of tests/test_simnn_trunk_batch_gpu.py; tests/test_trunk_plans.py asserts which regime each one reaches
@@ -80,7 +81,7 @@ NEAR_TIE_FRAC = 2e-3
 
 
 def _seg_plan(B, H1, W1, target, cols, cap):
-    """bd_plan / bw_plan (simnn_disc.hip:1891-1931): items = (image, row segment, column tile)."""
+    """seg_plan (simnn_trunk.h): items = (image, row segment, column tile)."""
     nrq = (H1 + ROWS - 1) // ROWS
     n_ctiles = (W1 + cols - 1) // cols
     strips = B * n_ctiles
@@ -103,7 +104,7 @@ def bw_plan(B, H1, W1):
 
 
 def c2f_plan(B, H1, W1):
-    """gdm_simnn_conv2_fwd (simnn_disc.hip:2054-2058) and conv2_fwd_kernel's walk (:895-907)."""
+    """gdm_simnn_conv2_fwd and conv2_fwd_kernel's walk over its tiles (simnn_conv2_fwd.hip)."""
     H2, W2 = H1 // 2, W1 // 2
     n_ctiles = (2 * W2 + COLS - 1) // COLS
     nrq = (2 * H2 + ROWS - 1) // ROWS
@@ -115,7 +116,7 @@ def c2f_plan(B, H1, W1):
 
 
 def c2f_workgroup(u, G):
-    """The workgroup that runs conv2 forward tile u (inverse of the XCD remap at simnn_disc.hip:903)."""
+    """The workgroup that runs conv2 forward tile u (inverse of the XCD remap in simnn_conv2_fwd.hip's conv2_fwd_kernel)."""
     u0 = u % G
     if G % 8 == 0:
         return (u0 % (G // 8)) * 8 + u0 // (G // 8)
@@ -123,19 +124,19 @@ def c2f_workgroup(u, G):
 
 
 def conv1_fwd_blocks(B, H):
-    """gdm_simnn_conv1_fwd_pair (simnn_disc.hip:1956-1960): 4 pooled rows per workgroup, capped."""
+    """gdm_simnn_conv1_fwd_pair (simnn_conv1.hip): 4 pooled rows per workgroup, capped."""
     n_rows = B * ((H + 1) // 2)
     return dict(n_rows=n_rows, blocks=min((n_rows + 3) // 4, C1_CAP))
 
 
 def conv1_slabs(B, H, W):
-    """simnn_disc.hip:1877-1880"""
+    """conv1_slabs (simnn_conv1.hip)"""
     total = B * ((H + 1) // 2) * ((W + 1) // 2)
     return max(1, min((total + 2047) // 2048, C1_SLABS_CAP))
 
 
 def conv1_bwd_data_blocks(B, H, W):
-    """simnn_disc.hip:2004-2005"""
+    """gdm_simnn_conv1_bwd_data (simnn_conv1.hip)"""
     return min((B * H * W + 255) // 256, C1BD_CAP)
 
 
@@ -146,12 +147,12 @@ def plan_env_overrides():
 
 # -------------------------------------------------------------------------------------------- fc1's GEMM plan
 def _fast_ok(m, n):
-    """gdm_gemm_bf16_fast_ok for these contiguous operands: M * N >= 64 * 64 (gemm_bf16.hip:409)"""
+    """gdm_gemm_bf16_fast_ok for these contiguous operands: M * N >= 64 * 64 (gemm_bf16.hip, gdm_gemm_bf16_fast_ok)"""
     return m * n >= 64 * 64
 
 
 def gemm_path(m, n, k, compute):
-    """mirror of gdm_gemm's split (gemm.hip:210-214) and the deep-variant rule (gemm_bf16.hip:418-422).
+    """mirror of gdm_gemm's split (gemm.hip:210-214) and the deep-variant rule (gemm_bf16.hip, gdm_gemm_bf16_fast_launch).
 
     Assumptions of the mirror (true for fc1's contiguous operands today, NOT checked against the library): the fast
     path's gdm_gemm_bf16_fast_ok is reduced to M * N >= 64 * 64; operand_ok (bf16/fp32 operands with one unit stride),

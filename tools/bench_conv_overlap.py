@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """conv2's two backward kernels (weight gradient; fused data gradient + conv1 weight gradient) one after the other on
 one stream vs side by side on two streams, at the benchmark geometry.  Grid caps come from the environment
-(GDM_BD_CAP, GDM_BW_CAP: experiments only), so that co-residency on a CU (LDS: fused 54.8 KB, weight 34.8 KB per
+(GDM_BD_CAP, GDM_BW_CAP: read only by a tagged experiment build -- GDM_BUILD_TAG at build time, GDM_LIB_TAG here --
+the shipped library ignores them), so that co-residency on a CU (LDS: fused 54.8 KB, weight 34.8 KB per
 workgroup, 160 KB per CU) can be arranged."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

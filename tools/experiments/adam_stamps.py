@@ -11,9 +11,9 @@ from gan_des_midi_music_gen_amd.ops import BF16
 def read():
     lib = _lib.load()
     buf = (ctypes.c_ulonglong * (1024 * 8))()
-    lib.gdm_debug_read_stamps.restype = ctypes.c_int
-    lib.gdm_debug_read_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    assert lib.gdm_debug_read_stamps(buf, 1024 * 8) == 0
+    lib.gdm_debug_read_stamps_adam.restype = ctypes.c_int                # simnn_adam.hip's own stamp buffer
+    lib.gdm_debug_read_stamps_adam.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    assert lib.gdm_debug_read_stamps_adam(buf, 1024 * 8) == 0
     return np.array(buf, dtype=np.uint64).reshape(1024, 8).astype(np.float64)
 
 B, H, W = 256, 128, 256

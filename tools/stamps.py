@@ -11,12 +11,15 @@ import numpy as np, torch
 from gan_des_midi_music_gen_amd import ops, synthetic, _lib
 from gan_des_midi_music_gen_amd.ops import BF16
 
-def read(n_blocks):
+FAMILY = {"fwd": "conv2_fwd", "bwd": "conv2_bwd_data", "bww": "conv2_bwd_weight", "c1": "conv1"}
+
+def read(n_blocks, which):
     lib = _lib.load()
     buf = (ctypes.c_ulonglong * (1024 * 8))()
-    lib.gdm_debug_read_stamps.restype = ctypes.c_int
-    lib.gdm_debug_read_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    rc = lib.gdm_debug_read_stamps(buf, 1024 * 8)
+    reader = getattr(lib, "gdm_debug_read_stamps_" + FAMILY[which])      # every trunk file has its own stamp buffer
+    reader.restype = ctypes.c_int
+    reader.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    rc = reader(buf, 1024 * 8)
     assert rc == 0, rc
     return np.array(buf, dtype=np.uint64).reshape(1024, 8)[:n_blocks].astype(np.float64)
 
@@ -46,7 +49,7 @@ def main():
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record(); fn(); b.record(); torch.cuda.synchronize()
     n_blocks = int(os.environ.get("NB", 768))
-    st = read(n_blocks)
+    st = read(n_blocks, which)
     tot = st.sum(1)
     print(f"{which}: launch {a.elapsed_time(b) * 1e3:.1f} us; per-workgroup total cycles mean {tot.mean():.0f} "
           f"min {tot.min():.0f} max {tot.max():.0f}  (100 MHz-independent shader cycles)")

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Do two kernels on two HIP streams really run at the same time?  A 64-workgroup launch of conv2's weight-gradient
-kernel (GDM_BW_CAP=64: a quarter of the CUs, so two of them cannot compete for resources) alone, twice on one stream,
+kernel (GDM_BW_CAP=64: a quarter of the CUs, so two of them cannot compete for resources; the override is read only
+by a tagged experiment build -- GDM_BUILD_TAG at build time, GDM_LIB_TAG here -- the shipped library ignores it) alone, twice on one stream,
 and once on each stream of several stream pairs.  Concurrent = the time of one; serialised = the time of two."""
 import os, sys, statistics
 os.environ.setdefault("GDM_BW_CAP", "64")
