@@ -194,6 +194,8 @@ class _TrainerBase:
             d.step_count = int(step)
             if d._hyper is not None:
                 d._hyper.view(torch.int32)[0:1].copy_(torch.tensor([int(step)], dtype=torch.int32))
+                if d.derived_record is not None:
+                    d.derived_record.zero_()         # include/gdm.h: zeroed whenever the host rewrites `hyper`
         if params is not None:
             self._refresh_operands()
 

@@ -607,9 +607,42 @@ def test_one_launch_optimizer_step_equals_the_four_launch_chain(dtype):
                 tr.lr = 1e-5                       # a hyper-parameter change between steps (device record rewritten)
         torch.cuda.synchronize()
         runs.append((losses, tr.d.flat.clone(), tr.d.exp_avg.clone(), tr.d.exp_avg_sq.clone(), tr._prepared[0].clone(),
-                     tr._prepared[1].clone(), int(tr.d._hyper.view(torch.int32)[0].item()), tr.d.step_count))
+                     tr._prepared[1].clone(), int(tr.d._hyper.view(torch.int32)[0].item()), tr.d.step_count,
+                     tr.d._hyper.view(torch.int32).clone()))
     a, c = runs
     assert a[0] == c[0], (a[0], c[0])
     for k in range(1, 6):
         assert torch.equal(a[k], c[k]), k
     assert a[6] == c[6] == 4 and a[7] == c[7] == 4
+    assert torch.equal(a[8], c[8]), (a[8], c[8])         # all 8 floats of the device record, the derived terms included
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp32"])
+def test_one_launch_optimizer_step_follows_a_loaded_step_counter(dtype):
+    """load_discriminator_state(step=...) in mid-run rewrites the device step counter from the host (and zeroes the
+    one-launch step's record of cached terms, as include/gdm.h requires): the one-launch and the four-launch trainer stay
+    bit-identical over the following three steps, for a counter moved forward and one moved back."""
+    hw, b = (32, 40), 4
+    for loaded in (7, 1):
+        runs = []
+        for one in (True, False):
+            gen, disc = _build(11, True, input_hw=hw)
+            gen.to(DEV), disc.to(DEV)
+            tr = SimnnTrainer(gen, disc, compute_dtype=dtype, one_launch_optimizer=one)
+            losses = []
+            for it in range(5):
+                if it == 2:
+                    tr.load_discriminator_state(step=loaded)
+                    if one:
+                        assert int(tr.d.derived_record.abs().sum().item()) == 0
+                real, fake, noise = synthetic.simnn_inputs(b, hw, seed=60 + it, device=DEV)
+                dl, gl = tr.step(real, noise, fake)
+                losses.append((dl.item(), gl.item()))
+            torch.cuda.synchronize()
+            runs.append((losses, tr.d.flat.clone(), tr.d.exp_avg.clone(), tr.d.exp_avg_sq.clone(), tr._prepared[0].clone(),
+                         tr._prepared[1].clone(), tr.d._hyper.view(torch.int32).clone(), tr.d.step_count))
+        a, c = runs
+        assert a[0] == c[0], (a[0], c[0])
+        for k in range(1, 7):
+            assert torch.equal(a[k], c[k]), (loaded, k)
+        assert int(a[6][0].item()) == a[7] == c[7] == loaded + 3
