@@ -41,6 +41,7 @@ SIGNATURES = {
     "gdm_arch": (_c.c_char_p, []),
     "gdm_build_flavor": (_I, []),
     "gdm_gemm": (_I, [_P, _I, _L, _L, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _I, _F, _I, _I, _P, _Z, _P]),
+    "gdm_gemm_plan": (_I, [_P, _I, _L, _L, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _I, _I, _P]),
     "gdm_bce_with_logits": (_I, [_P, _F, _I, _F, _P, _P, _I, _I, _P]),
     "gdm_criterion_loss": (_I, [_P, _F, _I, _I, _F, _P, _P, _I, _P]),
     "gdm_adam_step": (_I, [_P, _P, _P, _P, _L, _I, _F, _F, _F, _F, _F, _P]),

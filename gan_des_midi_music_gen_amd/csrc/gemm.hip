@@ -169,10 +169,10 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce(GemmArgs g) {
   }
 }
 
-int launch_splitk_reduce(const GemmArgs& g, hipStream_t s) {
-  if (g.split_k > 1) {
+int launch_splitk_reduce(const GemmArgs& g, const GemmPlan& p, hipStream_t s) {
+  if (p.reduce != GDM_GEMM_REDUCE_NONE) {
     const int64_t total = (int64_t)g.M * g.N;
-    if (g.N % 4 == 0) {
+    if (p.reduce == GDM_GEMM_REDUCE_VECTOR) {
       hipLaunchKernelGGL(gemm_splitk_reduce<true>, dim3((unsigned)((total / 4 + 63) / 64)), dim3(256), 0, s, g);
     } else {
       hipLaunchKernelGGL(gemm_splitk_reduce<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g);
@@ -183,50 +183,90 @@ int launch_splitk_reduce(const GemmArgs& g, hipStream_t s) {
 }
 
 template <typename CT>
-int launch_gemm(const GemmArgs& g, int a_dtype, int b_dtype, hipStream_t s) {
+int launch_gemm(const GemmArgs& g, const GemmPlan& p, int a_dtype, int b_dtype, hipStream_t s) {
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, g.split_k), block(NT);
   if (a_dtype == GDM_F32 && b_dtype == GDM_F32) hipLaunchKernelGGL((gemm_kernel<CT, float, float>), grid, block, 0, s, g);
   else if (a_dtype == GDM_F32) hipLaunchKernelGGL((gemm_kernel<CT, float, __bf16>), grid, block, 0, s, g);
   else if (b_dtype == GDM_F32) hipLaunchKernelGGL((gemm_kernel<CT, __bf16, float>), grid, block, 0, s, g);
   else hipLaunchKernelGGL((gemm_kernel<CT, __bf16, __bf16>), grid, block, 0, s, g);
   GDM_LAUNCH_OK("gdm_gemm");
-  return launch_splitk_reduce(g, s);
+  return launch_splitk_reduce(g, p, s);
 }
 
-}  // namespace
-
-extern "C" int gdm_gemm(const void* A, int a_dtype, int64_t sam, int64_t sak, const void* B, int b_dtype, int64_t sbk,
-                        int64_t sbn, void* C, int c_dtype, int64_t scm, int64_t scn, int M, int N, int K,
-                        const float* bias_n, const float* bias_m, int act, float slope, int compute_dtype, int split_k,
-                        void* workspace, size_t workspace_bytes, void* stream) {
+// The one place where the path of a product is decided: which kernel, the operand layouts of the fast kernel, the
+// clamped split, the slab width, the reduce kernel and the workspace.  Host arithmetic on the operand description only
+// (the pointers count for their alignment): gdm_gemm launches what this returns and gdm_gemm_plan reports it.
+int gemm_plan(const void* A, int a_dtype, int64_t sam, int64_t sak, const void* B, int b_dtype, int64_t sbk, int64_t sbn,
+              const void* C, int c_dtype, int64_t scm, int64_t scn, int M, int N, int K, const float* bias_n,
+              int compute_dtype, int split_k, GemmPlan* p) {
   GDM_REQUIRE(A && B && C, "gdm_gemm: null operand");
   GDM_REQUIRE(M > 0 && N > 0 && K > 0, "gdm_gemm: bad dims M=%d N=%d K=%d", M, N, K);
   GDM_REQUIRE(gdm_dtype_ok(a_dtype) && gdm_dtype_ok(b_dtype) && gdm_dtype_ok(c_dtype) && gdm_dtype_ok(compute_dtype),
               "gdm_gemm: bad dtype");
-  GDM_REQUIRE(act >= GDM_ACT_NONE && act <= GDM_ACT_SIGMOID, "gdm_gemm: bad activation %d", act);
   GDM_REQUIRE(split_k >= 1 && split_k <= 65535, "gdm_gemm: bad split_k %d", split_k);
-  GemmArgs probe{A, sam, sak, B, sbk, sbn, C, c_dtype, scm, scn, M, N, K, bias_n, bias_m, act, slope, 1, K, nullptr};
-  const bool fast = compute_dtype == GDM_BF16 && gdm_gemm_bf16_fast_ok(probe, a_dtype, b_dtype);
+  GemmArgs probe{A, sam, sak, B, sbk, sbn, const_cast<void*>(C), c_dtype, scm, scn, M, N, K, bias_n, nullptr,
+                 GDM_ACT_NONE, 0.f, 1, K, nullptr};
+  p->a_kmaj = p->b_kmaj = false;
+  const bool fast = compute_dtype == GDM_BF16 && gdm_gemm_bf16_fast_ok(probe, a_dtype, b_dtype, &p->a_kmaj, &p->b_kmaj);
+  if (!fast) p->a_kmaj = p->b_kmaj = false;
   const int KT = fast ? GDM_GEMM_FAST_KT : (compute_dtype == GDM_BF16 ? GemmCfg<__bf16>::KT : GemmCfg<float>::KT);
   int tiles = (K + KT - 1) / KT;
   if (split_k > tiles) split_k = tiles;
   int per = (tiles + split_k - 1) / split_k;
   split_k = (tiles + per - 1) / per;  // no empty slab
-  if (split_k > 1) {
-    if (workspace == nullptr || workspace_bytes < (size_t)split_k * M * N * sizeof(float)) {
-      gdm_set_error("gdm_gemm: split_k=%d needs %zu workspace bytes, got %zu", split_k,
-                    (size_t)split_k * M * N * sizeof(float), workspace_bytes);
+  p->split_k = split_k;
+  p->k_per_split = per * KT;
+  p->ws_bytes = split_k > 1 ? (size_t)split_k * M * N * sizeof(float) : 0;
+  p->reduce = split_k > 1 ? (N % 4 == 0 ? GDM_GEMM_REDUCE_VECTOR : GDM_GEMM_REDUCE_SCALAR) : GDM_GEMM_REDUCE_NONE;
+  if (fast) p->kernel = gdm_gemm_bf16_fast_deep(M, N, split_k, p->k_per_split) ? GDM_GEMM_KERNEL_FAST_K64
+                                                                                 : GDM_GEMM_KERNEL_FAST_K32;
+  else p->kernel = compute_dtype == GDM_BF16 ? GDM_GEMM_KERNEL_BF16 : GDM_GEMM_KERNEL_F32;
+  return GDM_OK;
+}
+
+}  // namespace
+
+extern "C" int gdm_gemm_plan(const void* A, int a_dtype, int64_t sam, int64_t sak, const void* B, int b_dtype,
+                             int64_t sbk, int64_t sbn, const void* C, int c_dtype, int64_t scm, int64_t scn, int M, int N,
+                             int K, const float* bias_n, int compute_dtype, int split_k, int64_t* plan) {
+  GDM_REQUIRE(plan, "gdm_gemm_plan: null plan");
+  GemmPlan p;
+  int rc = gemm_plan(A, a_dtype, sam, sak, B, b_dtype, sbk, sbn, C, c_dtype, scm, scn, M, N, K, bias_n, compute_dtype,
+                     split_k, &p);
+  if (rc != GDM_OK) return rc;
+  plan[GDM_GEMM_PLAN_KERNEL] = p.kernel;
+  plan[GDM_GEMM_PLAN_A_KMAJOR] = p.a_kmaj;
+  plan[GDM_GEMM_PLAN_B_KMAJOR] = p.b_kmaj;
+  plan[GDM_GEMM_PLAN_SPLIT_K] = p.split_k;
+  plan[GDM_GEMM_PLAN_K_PER_SPLIT] = p.k_per_split;
+  plan[GDM_GEMM_PLAN_REDUCE] = p.reduce;
+  plan[GDM_GEMM_PLAN_WORKSPACE_BYTES] = (int64_t)p.ws_bytes;
+  return GDM_OK;
+}
+
+extern "C" int gdm_gemm(const void* A, int a_dtype, int64_t sam, int64_t sak, const void* B, int b_dtype, int64_t sbk,
+                        int64_t sbn, void* C, int c_dtype, int64_t scm, int64_t scn, int M, int N, int K,
+                        const float* bias_n, const float* bias_m, int act, float slope, int compute_dtype, int split_k,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  GemmPlan p;
+  int rc = gemm_plan(A, a_dtype, sam, sak, B, b_dtype, sbk, sbn, C, c_dtype, scm, scn, M, N, K, bias_n, compute_dtype,
+                     split_k, &p);
+  if (rc != GDM_OK) return rc;
+  GDM_REQUIRE(act >= GDM_ACT_NONE && act <= GDM_ACT_SIGMOID, "gdm_gemm: bad activation %d", act);
+  if (p.split_k > 1) {
+    if (workspace == nullptr || workspace_bytes < p.ws_bytes) {
+      gdm_set_error("gdm_gemm: split_k=%d needs %zu workspace bytes, got %zu", p.split_k, p.ws_bytes, workspace_bytes);
       return GDM_EWORKSPACE;
     }
   }
   GemmArgs g{A, sam, sak, B, sbk, sbn, C, c_dtype, scm, scn, M, N, K, bias_n, bias_m, act, slope,
-             split_k, per * KT, (float*)workspace};
+             p.split_k, p.k_per_split, (float*)workspace};
   hipStream_t s = (hipStream_t)stream;
-  if (fast) {
-    int rc = gdm_gemm_bf16_fast_launch(g, a_dtype, b_dtype, s);
+  if (p.kernel == GDM_GEMM_KERNEL_FAST_K32 || p.kernel == GDM_GEMM_KERNEL_FAST_K64) {
+    rc = gdm_gemm_bf16_fast_launch(g, a_dtype, b_dtype, p, s);
     if (rc != GDM_OK) return rc;
-    return launch_splitk_reduce(g, s);
+    return launch_splitk_reduce(g, p, s);
   }
-  return compute_dtype == GDM_BF16 ? launch_gemm<__bf16>(g, a_dtype, b_dtype, s)
-                                   : launch_gemm<float>(g, a_dtype, b_dtype, s);
+  return p.kernel == GDM_GEMM_KERNEL_BF16 ? launch_gemm<__bf16>(g, p, a_dtype, b_dtype, s)
+                                          : launch_gemm<float>(g, p, a_dtype, b_dtype, s);
 }

@@ -43,10 +43,9 @@ inline bool operand_ok(const void* p, int dtype, int64_t s_row, int64_t s_k, int
 
 }  // namespace
 
-bool gdm_gemm_bf16_fast_ok(const GemmArgs& g, int a_dtype, int b_dtype) {
-  bool ak, bk;
-  if (!operand_ok(g.A, a_dtype, g.sam, g.sak, g.M, g.K, &ak)) return false;
-  if (!operand_ok(g.B, b_dtype, g.sbn, g.sbk, g.N, g.K, &bk)) return false;
+bool gdm_gemm_bf16_fast_ok(const GemmArgs& g, int a_dtype, int b_dtype, bool* a_kmaj, bool* b_kmaj) {
+  if (!operand_ok(g.A, a_dtype, g.sam, g.sak, g.M, g.K, a_kmaj)) return false;
+  if (!operand_ok(g.B, b_dtype, g.sbn, g.sbk, g.N, g.K, b_kmaj)) return false;
   if (g.scn != 1) return false;
   const int64_t csz = g.c_dtype == GDM_BF16 ? 2 : 4;
   if (g.N % 4 == 0) {   // vector epilogue: rows of C and the bias must allow 4-element accesses
@@ -58,21 +57,25 @@ bool gdm_gemm_bf16_fast_ok(const GemmArgs& g, int a_dtype, int b_dtype) {
   return true;
 }
 
-int gdm_gemm_bf16_fast_launch(const GemmArgs& g, int a_dtype, int b_dtype, hipStream_t s) {
-  bool ak = true, bk = true;
-  operand_ok(g.A, a_dtype, g.sam, g.sak, g.M, g.K, &ak);
-  operand_ok(g.B, b_dtype, g.sbn, g.sbk, g.N, g.K, &bk);
+bool gdm_gemm_bf16_fast_deep(int M, int N, int split_k, int k_per_split) {
+  const int MT = (M + BM - 1) / BM, NTl = (N + BN - 1) / BN;
+  const int outer = NTl * split_k;
+  // split-K products (few workgroups per CU, long K loops): bytes in flight per workgroup decide -> deep variant
+  bool deep = split_k > 1 && (int64_t)outer * MT <= 512 && k_per_split >= 256;
+  static const int force = GDM_TUNABLE("GDM_GEMM_VARIANT", -1);
+  if (force >= 0) deep = force == 1;
+  return deep;
+}
+
+int gdm_gemm_bf16_fast_launch(const GemmArgs& g, int a_dtype, int b_dtype, const GemmPlan& p, hipStream_t s) {
   const int MT = (g.M + BM - 1) / BM, NTl = (g.N + BN - 1) / BN;
   const int outer = NTl * g.split_k;
   dim3 grid((unsigned)(((outer + 7) / 8) * 8 * MT));
-  // split-K products (few workgroups per CU, long K loops): bytes in flight per workgroup decide -> deep variant
-  int variant = (g.split_k > 1 && (int64_t)outer * MT <= 512 && g.k_per_split >= 256) ? 1 : 0;
-  static const int force = GDM_TUNABLE("GDM_GEMM_VARIANT", -1);
-  if (force >= 0) variant = force == 1;
-  // variant 0: K tile 32, one tile ahead, 16 KB LDS (many workgroups per CU); 1: K tile 64, two tiles ahead, 64 KB LDS
-  auto* launch = a_dtype == GDM_BF16 ? (variant == 1 ? gdm_gemm_bf16_kt64_bf16a : gdm_gemm_bf16_kt32_bf16a)
-                                     : (variant == 1 ? gdm_gemm_bf16_kt64_f32a : gdm_gemm_bf16_kt32_f32a);
-  launch(g, ak, b_dtype, bk, grid, s);
+  // K tile 32, one tile ahead, 16 KB LDS (many workgroups per CU); or K tile 64, two tiles ahead, 64 KB LDS
+  const bool deep = p.kernel == GDM_GEMM_KERNEL_FAST_K64;
+  auto* launch = a_dtype == GDM_BF16 ? (deep ? gdm_gemm_bf16_kt64_bf16a : gdm_gemm_bf16_kt32_bf16a)
+                                     : (deep ? gdm_gemm_bf16_kt64_f32a : gdm_gemm_bf16_kt32_f32a);
+  launch(g, p.a_kmaj, b_dtype, p.b_kmaj, grid, s);
   GDM_LAUNCH_OK("gdm_gemm(bf16 fast path)");
   return GDM_OK;
 }

@@ -18,10 +18,22 @@ __device__ __forceinline__ void gemm_epilogue_store(const GemmArgs& g, int m, in
   store_from_f32(g.C, g.c_dtype, (int64_t)m * g.scm + (int64_t)n * g.scn, v);
 }
 
-// true if the vectorised kernel can take this problem (layouts contiguous along k or along m/n, 16-byte aligned
-// rows, row-major C); launches it (and the split-K reduce is left to the caller).  Defined in gemm_bf16.hip.
-bool gdm_gemm_bf16_fast_ok(const GemmArgs& g, int a_dtype, int b_dtype);
-int gdm_gemm_bf16_fast_launch(const GemmArgs& g, int a_dtype, int b_dtype, hipStream_t s);
+// The path of one product, decided by gemm_plan() in gemm.hip and nowhere else: gdm_gemm launches from it and
+// gdm_gemm_plan reports it (kernel: GDM_GEMM_KERNEL_*, reduce: GDM_GEMM_REDUCE_* of include/gdm.h).
+struct GemmPlan {
+  int kernel;
+  bool a_kmaj, b_kmaj;        // operand layouts of the fast kernels (false on the generic path)
+  int split_k, k_per_split;   // the clamped split and the slab width in k
+  int reduce;
+  size_t ws_bytes;
+};
+
+// gemm_bf16.hip.  fast_ok: true if the vectorised kernel can take this problem (layouts contiguous along k or along
+// m/n, 16-byte aligned rows, row-major C), with the layout of each operand; fast_deep: the K-tile-64 variant for this
+// grid and slab width; fast_launch launches the instance the plan names (the split-K reduce is left to the caller).
+bool gdm_gemm_bf16_fast_ok(const GemmArgs& g, int a_dtype, int b_dtype, bool* a_kmaj, bool* b_kmaj);
+bool gdm_gemm_bf16_fast_deep(int M, int N, int split_k, int k_per_split);
+int gdm_gemm_bf16_fast_launch(const GemmArgs& g, int a_dtype, int b_dtype, const GemmPlan& p, hipStream_t s);
 // gemm_bf16_kt{32,64}_{bf16,f32}a.hip: the kernel instantiations of one variant (K tile) and A dtype
 void gdm_gemm_bf16_kt32_bf16a(const GemmArgs& g, bool a_kmaj, int b_dtype, bool b_kmaj, dim3 grid, hipStream_t s);
 void gdm_gemm_bf16_kt32_f32a(const GemmArgs& g, bool a_kmaj, int b_dtype, bool b_kmaj, dim3 grid, hipStream_t s);

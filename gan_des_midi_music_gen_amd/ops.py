@@ -152,6 +152,41 @@ def gemm(a, b, *, bias_n=None, bias_m=None, act=ACT_NONE, slope=0.0, out_dtype=N
     return out
 
 
+GEMM_KERNELS = ("generic_f32", "generic_bf16", "fast_k32", "fast_k64")      # GDM_GEMM_KERNEL_*
+GEMM_REDUCES = ("none", "vector", "scalar")                                  # GDM_GEMM_REDUCE_*
+
+
+def gemm_plan_raw(a_ptr, a_dtype, sam, sak, b_ptr, b_dtype, sbk, sbn, c_ptr, c_dtype, scm, scn, m, n, k, bias_n_ptr,
+                  compute, split_k):
+    """gdm_gemm_plan on a bare operand description (the addresses count for their alignment only; nothing is launched,
+    no GPU is needed) -> dict(kernel, a_kmajor, b_kmajor, split_k, k_per_split, reduce, workspace_bytes)."""
+    out = (ctypes.c_int64 * 7)()
+    lib = _lib.load()
+    check(lib.gdm_gemm_plan(a_ptr, a_dtype, sam, sak, b_ptr, b_dtype, sbk, sbn, c_ptr, c_dtype, scm, scn, m, n, k,
+                            bias_n_ptr or None, compute, split_k, ctypes.cast(out, ctypes.c_void_p)), "gdm_gemm_plan")
+    return dict(kernel=GEMM_KERNELS[out[0]], a_kmajor=bool(out[1]), b_kmajor=bool(out[2]), split_k=int(out[3]),
+                k_per_split=int(out[4]), reduce=GEMM_REDUCES[out[5]], workspace_bytes=int(out[6]))
+
+
+def gemm_plan(a, b, *, bias_n=None, bias_m=None, act=ACT_NONE, slope=0.0, out_dtype=None, compute=F32, split_k=None,
+              out=None):
+    """The path ``gemm`` takes with these arguments, as the library itself decides it (gdm_gemm_plan): nothing runs.
+    Without ``out`` the plan is that of the fresh contiguous tensor ``gemm`` would allocate."""
+    assert a.dim() == 2 and b.dim() == 2 and a.shape[1] == b.shape[0], (a.shape, b.shape)
+    m, k = a.shape
+    n = b.shape[1]
+    if split_k is None:
+        split_k = default_split_k(m, n, k, compute)
+    if out is None:
+        c_ptr, c_dtype, scm, scn = 1 << 12, (F32 if out_dtype is None else out_dtype), n, 1
+    else:
+        assert out.shape == (m, n)
+        c_ptr, c_dtype, scm, scn = out.data_ptr(), gdm_dtype(out), out.stride(0), out.stride(1)
+    return gemm_plan_raw(a.data_ptr(), gdm_dtype(a), a.stride(0), a.stride(1), b.data_ptr(), gdm_dtype(b), b.stride(0),
+                         b.stride(1), c_ptr, c_dtype, scm, scn, m, n, k,
+                         bias_n.data_ptr() if bias_n is not None else None, compute, split_k)
+
+
 def bce_with_logits(x, target, *, grad_scale=1.0, want_grad=True, fuse_sigmoid_backward=False, loss_out=None,
                     accumulate_loss=False, dx_out=None):
     """Returns (loss (1,) fp32 tensor, dx or None).  x: (n,) fp32 contiguous."""

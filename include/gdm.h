@@ -48,6 +48,21 @@ int gdm_gemm(const void* A, int a_dtype, int64_t sam, int64_t sak,
              const float* bias_n, const float* bias_m, int act, float slope,
              int compute_dtype, int split_k, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The path gdm_gemm takes for one operand description, from the same host function gdm_gemm launches from.  Nothing is
+ * launched and the GPU is not touched: the pointers count for their alignment only and are never dereferenced.  Fills
+ * plan[GDM_GEMM_PLAN_FIELDS]: the kernel (GDM_GEMM_KERNEL_*), whether A and B are read K-major (fast kernels; 0 on the
+ * generic path), the effective split_k (clamped so that no slab is empty), the slab width k_per_split, the reduce
+ * kernel (GDM_GEMM_REDUCE_*) and the workspace bytes gdm_gemm will ask for.  Argument errors are gdm_gemm's.         */
+enum { GDM_GEMM_KERNEL_F32 = 0, GDM_GEMM_KERNEL_BF16 = 1, GDM_GEMM_KERNEL_FAST_K32 = 2, GDM_GEMM_KERNEL_FAST_K64 = 3 };
+enum { GDM_GEMM_REDUCE_NONE = 0, GDM_GEMM_REDUCE_VECTOR = 1, GDM_GEMM_REDUCE_SCALAR = 2 };
+enum { GDM_GEMM_PLAN_KERNEL = 0, GDM_GEMM_PLAN_A_KMAJOR = 1, GDM_GEMM_PLAN_B_KMAJOR = 2, GDM_GEMM_PLAN_SPLIT_K = 3,
+       GDM_GEMM_PLAN_K_PER_SPLIT = 4, GDM_GEMM_PLAN_REDUCE = 5, GDM_GEMM_PLAN_WORKSPACE_BYTES = 6,
+       GDM_GEMM_PLAN_FIELDS = 7 };
+int gdm_gemm_plan(const void* A, int a_dtype, int64_t sam, int64_t sak,
+                  const void* B, int b_dtype, int64_t sbk, int64_t sbn,
+                  const void* C, int c_dtype, int64_t scm, int64_t scn,
+                  int M, int N, int K, const float* bias_n, int compute_dtype, int split_k, int64_t* plan);
+
 /* ---- loss (aten::binary_cross_entropy_with_logits, mean) --------------------------------------------------------
  * x: n fp32 values fed to BCEWithLogitsLoss (for model 1 these are already sigmoid outputs: SIMNN.py:141 + 289),
  * target: one label value for the whole batch (0.9/0.1/1.0 at SIMNN.py:284,308,326; 1/0 at network_tests.py:286-287).

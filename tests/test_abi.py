@@ -39,6 +39,12 @@ def test_probes_and_error_reporting(lib_path):
     # argument validation happens on the host before any launch: safe without a GPU
     rc = lib.gdm_gemm(None, 0, 0, 0, None, 0, 0, 0, None, 0, 0, 0, 4, 4, 4, None, None, 0, 0.0, 0, 1, None, 0, None)
     assert rc == -1 and b"null operand" in lib.gdm_last_error()
+    # gdm_gemm_plan validates through the same function: the same error for the same operands
+    message = lib.gdm_last_error()
+    plan = (ctypes.c_int64 * 7)()
+    rc = lib.gdm_gemm_plan(None, 0, 0, 0, None, 0, 0, 0, None, 0, 0, 0, 4, 4, 4, None, 0, 1,
+                           ctypes.cast(plan, ctypes.c_void_p))
+    assert rc == -1 and lib.gdm_last_error() == message
     rc = lib.gdm_bce_with_logits(None, 0.0, 4, 1.0, None, None, 0, 0, None)
     assert rc == -1
 

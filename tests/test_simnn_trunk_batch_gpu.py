@@ -205,6 +205,15 @@ def _gemm_check(name, got, a, bm, *, bias=None, relu=False, n_chain, out_dt):
     record(f"fc1 {name}", worst_ratio=r, rtol=rtol, worst_case_rtol=n_chain * 2.0 ** -24)
 
 
+def _mirror_is_the_library(mirror, plan, what):
+    """trunk_ref.gemm_path against gdm_gemm_plan on the tensors of the call: split, slab width, fast path, variant"""
+    lib = dict(split=plan["split_k"], k_per_split=plan["k_per_split"], fast=plan["kernel"].startswith("fast"),
+               variant={"fast_k32": 0, "fast_k64": 1}.get(plan["kernel"]))
+    mine = dict(split=mirror["split"], k_per_split=mirror["per_tiles"] * mirror["kt"], fast=mirror["fast"],
+                variant=mirror["variant"])
+    assert mine == lib, f"{what}: trunk_ref.gemm_path says {mine}, the library {lib}"
+
+
 @pytest.mark.parametrize("comp", [F32, BF16])
 @pytest.mark.parametrize("m,k", [(512, 65536), (256, 65536), (256, 55296), (32, 55296)])
 def test_fc1_gemms_at_their_real_shapes(comp, m, k):
@@ -226,16 +235,19 @@ def test_fc1_gemms_at_their_real_shapes(comp, m, k):
         assert pf["fast"] and pf["variant"] == 1, pf
     if (m, k, comp) == (256, 55296, BF16):
         assert pf["last_tiles"] < pf["per_tiles"], pf          # a short last split-K slab
+    _mirror_is_the_library(pf, ops.gemm_plan(fd, wd.t(), bias_n=bd, act=ops.ACT_RELU, compute=comp), f"forward {tag}")
     h1 = ops.gemm(fd, wd.t(), bias_n=bd, act=ops.ACT_RELU, compute=comp)
     _gemm_check(f"forward {tag}", h1.cpu(), rb(flat.float()), rb(wf1p).t(), bias=bf1, relu=True,
                 n_chain=pf["per_tiles"] * pf["kt"] + pf["split"] + 2, out_dt=torch.float32)
     # dW = dh^T (128, M) @ flat (functional.py:97, train.py:352)
     pw = gemm_path(n, k, m, comp)
+    _mirror_is_the_library(pw, ops.gemm_plan(dhd.t(), fd, compute=comp), f"dW {tag}")
     dw = ops.gemm(dhd.t(), fd, compute=comp)
     _gemm_check(f"dW {tag}", dw.cpu(), rb(dh).t(), rb(flat.float()), n_chain=pw["per_tiles"] * pw["kt"] + pw["split"] + 2,
                 out_dt=torch.float32)
     # dX = dh @ wf1p, stored in the compute dtype (functional.py:99, train.py:357)
     px = gemm_path(m, k, n, comp)
+    _mirror_is_the_library(px, ops.gemm_plan(dhd, wd, compute=comp, out_dtype=comp), f"dX {tag}")
     dxf = ops.gemm(dhd, wd, compute=comp, out_dtype=comp)
     _gemm_check(f"dX {tag}", dxf.float().cpu(), rb(dh), rb(wf1p), n_chain=px["per_tiles"] * px["kt"] + px["split"] + 2,
                 out_dt=tdt)

@@ -102,7 +102,7 @@ def test_plan_sweep_library_equals_mirror(lib):
 
 def test_fc1_gemm_paths():
     """The long-K fc1 products split K and take the deep variant; K = 55296 ends in a short slab (mirrors of
-    ops.default_split_k, gemm.hip:210-214, gemm_bf16.hip gdm_gemm_bf16_fast_launch)."""
+    ops.default_split_k, gemm.hip gemm_plan, gemm_bf16.hip gdm_gemm_bf16_fast_deep)."""
     for m, k in ((512, 65536), (256, 65536), (256, 55296), (32, 55296)):
         p = gemm_path(m, 128, k, BF16)
         assert p["split"] > 1 and p["fast"] and p["variant"] == 1, (m, k, p)

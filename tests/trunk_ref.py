@@ -152,12 +152,13 @@ def _fast_ok(m, n):
 
 
 def gemm_path(m, n, k, compute):
-    """mirror of gdm_gemm's split (gemm.hip:210-214) and the deep-variant rule (gemm_bf16.hip, gdm_gemm_bf16_fast_launch).
+    """mirror of gdm_gemm's plan (gemm_plan in gemm.hip, gdm_gemm_bf16_fast_deep in gemm_bf16.hip) for fc1's products.
 
-    Assumptions of the mirror (true for fc1's contiguous operands today, NOT checked against the library): the fast
-    path's gdm_gemm_bf16_fast_ok is reduced to M * N >= 64 * 64; operand_ok (bf16/fp32 operands with one unit stride),
-    the vector epilogue's row / pointer alignment (N % 4 == 0) and the 16-byte bias alignment are assumed to hold.  If
-    the library left the fast path for another reason, this mirror would still say "fast, variant 1"."""
+    Assumptions of the mirror (true for fc1's contiguous operands): the fast path's gdm_gemm_bf16_fast_ok is reduced to
+    M * N >= 64 * 64; operand_ok (bf16/fp32 operands with one unit stride), the vector epilogue's row / pointer
+    alignment (N % 4 == 0) and the 16-byte bias alignment hold.  test_fc1_gemms_at_their_real_shapes asserts that it
+    equals the library's own plan (ops.gemm_plan) on the device tensors of all three products; the dispatch itself is
+    covered by tests/test_gemm_ref.py."""
     from gan_des_midi_music_gen_amd import ops
     split = ops.default_split_k(m, n, k, compute)
     fast = compute == ops.BF16 and _fast_ok(m, n)
