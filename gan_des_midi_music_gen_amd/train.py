@@ -111,6 +111,16 @@ class FlatBuffers:
                 self.derived_record.zero_()          # terms cached on the device for the old lr / betas
         return want
 
+    def hyper_record(self, lr, betas, eps, grad_scale=1.0):
+        """What every optimizer step starts with: bring the device record up to date (``sync_hyper``), create it on
+        first use, count the step on the host.  Returns the record (the kernel that reads it advances its counter)."""
+        want = self.sync_hyper(lr, betas, eps, grad_scale)
+        if self._hyper is None:
+            self._hyper = ops.adam_hyper(self.flat.device, *want, step=self.step_count)
+            self._hyper_host = want
+        self.step_count += 1
+        return self._hyper
+
     def adam(self, lr, betas, eps, grad_scale=1.0, big_pc=None):
         """One fused Adam step over the flat buffer.  Step counter and hyper-parameters live in an 8-float device
         record (so a captured hipGraph replays correctly); the host only rewrites it when lr/scale change.
@@ -119,20 +129,16 @@ class FlatBuffers:
         (n, pix, c) "channels-last" layout its weight-gradient GEMM produces, and ``shadow`` (n, pix, c) receives the
         updated value as the GEMM operand copy (model 1's fc1.weight): the small parameters take the plain kernel, the
         big one the transposing kernel -- no separate permute passes."""
-        want = self.sync_hyper(lr, betas, eps, grad_scale)
-        if self._hyper is None:
-            self._hyper = ops.adam_hyper(self.flat.device, *want, step=self.step_count)
-            self._hyper_host = want
-        self.step_count += 1
+        hyper = self.hyper_record(lr, betas, eps, grad_scale)
         if big_pc is None:
-            ops.adam_step_dev(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self._hyper)
+            ops.adam_step_dev(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, hyper)
             return
         ns = self.n_small
         n, c, pix, shadow = big_pc
         assert n * c * pix == self.flat.numel() - ns and ns > 0
-        ops.adam_step_dev(self.flat[:ns], self.grad[:ns], self.exp_avg[:ns], self.exp_avg_sq[:ns], self._hyper)
+        ops.adam_step_dev(self.flat[:ns], self.grad[:ns], self.exp_avg[:ns], self.exp_avg_sq[:ns], hyper)
         ops.adam_step_dev_pc(self.flat[ns:], self.grad[ns:], self.exp_avg[ns:], self.exp_avg_sq[ns:], n, c, pix, shadow,
-                             self._hyper, advance_step=False)
+                             hyper, advance_step=False)
 
 
 class _TrainerBase:
@@ -149,6 +155,68 @@ class _TrainerBase:
         self.loss_g = self.d.extra[0:1]
         self.loss_d = self.d.extra[4:5]
         self.iterations = 0
+        self._pending = None             # handle of the big gradient's all-reduce while it is in flight
+        self._nf = None                  # device counter of non-finite values (made on first use)
+        self._scratch_grads = None       # where the generator step's dead backward writes (made on first use)
+        self._adam_done = None           # completion counters of a kernel that applies Adam itself (made on first use)
+        self._static = None              # the tensors a captured iteration reads
+        self._graph = None
+        self._graph_gen = None           # the generator work as a graph of its own (see capture)
+        self._gen_event = None           # recorded behind the last replay of that graph
+        self._gen_replay_stream = None   # the stream of the trainer's own it is replayed on
+
+    def _scratch(self):
+        """Gradient buffers for dead values: the generator step's backward only fills D's .grad, which the next
+        zero_grad() wipes (SIMNN.py:330, 282; network_tests.py:314, 300); faithful mode computes them into these."""
+        if self._scratch_grads is None:
+            self._scratch_grads = [torch.empty_like(g) for g in self.d.grad_views]
+        return self._scratch_grads
+
+    # ---- hipGraph choreography both trainers use ---------------------------------------------------------------------
+    @staticmethod
+    def _warm_up(iteration, dev):
+        """Two eager iterations on a side stream before a capture (lazy buffers, workspaces and kernel modules exist
+        afterwards); the device is idle when this returns."""
+        warm = torch.cuda.Stream(dev)
+        warm.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(warm):
+            for _ in range(2):
+                iteration()
+        torch.cuda.current_stream().wait_stream(warm)
+        torch.cuda.synchronize()
+
+    def _capture(self, launches, pool=None, namespace_of=None):
+        """Record ``launches()`` into a new hipGraph.  Graphs of one trainer may replay concurrently, so each is captured
+        under a scratch-buffer namespace of its own (ops.workspace_namespace) -- or, ``namespace_of`` = an earlier
+        graph, under that graph's: two graphs that only ever replay one after the other on one stream share scratch
+        buffers like eager launches do."""
+        counted = self.d.step_count, self.iterations
+        graph = torch.cuda.CUDAGraph()
+        ns = namespace_of if namespace_of is not None else graph
+        with ops.workspace_namespace(("graph", id(ns))), torch.cuda.graph(graph, pool=pool):
+            launches()
+        # the captured calls did not execute: the device-side step counter did not move
+        self.d.step_count, self.iterations = counted
+        return graph
+
+    def _replay_beside(self, main, *graphs, stream=None):
+        """Replay ``graphs`` on a stream of the trainer's own (default: the generator stream): behind everything the
+        caller has enqueued so far on its stream ``main`` (its refills of the static inputs, the previous iteration)
+        and beside whatever it enqueues next.  Returns the event recorded behind each graph; which of them the caller's
+        stream has to wait for, and when, is the schedule's decision."""
+        sg = stream if stream is not None else self._gen_replay_stream
+        sg.wait_stream(main)
+        events = []
+        with torch.cuda.stream(sg):
+            for graph in graphs:
+                graph.replay()
+                events.append(sg.record_event())
+        return events
+
+    def _join_generators(self):
+        """The current stream waits for the last replay of the generator graph (which runs on the trainer's stream)."""
+        if self._gen_event is not None and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream().wait_event(self._gen_event)
 
     def _reduce_big_async(self):
         """Start the SUM all-reduce of the largest gradient (call on the stream that produced it); no-op on 1 rank."""
@@ -157,7 +225,7 @@ class _TrainerBase:
     def _reduce(self):
         """The data-parallel exchange of everything that is not yet in flight: SUM over ranks (1/world is folded into
         Adam and into the loss read-out).  No-op on one rank."""
-        pending = getattr(self, "_pending", None)
+        pending = self._pending
         if pending is None:
             red = self.d.bucket_reduced()
             dp.allreduce_bucket_(red, red.numel(), self.pg)                         # everything in one collective
@@ -206,21 +274,23 @@ class _TrainerBase:
     # every eager ``step`` counts the non-finite elements of its inputs, losses and discriminator parameters on the
     # device and raises ops.NonFiniteError before returning; (b) ``check_finite(*tensors)`` does the same on request
     # (graph replays, anomaly mode off).
+    def _count_nonfinite(self, tensors):
+        if self._nf is None:
+            self._nf = torch.zeros(1, dtype=torch.int32, device=self.d.flat.device)
+        ops.nonfinite_count(tensors, self._nf)
+        return self._nf
+
     def _watch(self, *tensors):
         if torch.is_anomaly_enabled():
-            if getattr(self, "_nf", None) is None:
-                self._nf = torch.zeros(1, dtype=torch.int32, device=self.d.flat.device)
-            ops.nonfinite_count([t for t in tensors if isinstance(t, torch.Tensor)], self._nf)
+            self._count_nonfinite([t for t in tensors if isinstance(t, torch.Tensor)])
 
     def check_finite(self, *tensors):
         """Raise ops.NonFiniteError if the last losses, the discriminator's parameters / Adam moments, anything watched
         since the last check (anomaly mode) or any of ``tensors`` (e.g. the batch just used) holds a NaN or Inf.
         Synchronises."""
-        if getattr(self, "_nf", None) is None:
-            self._nf = torch.zeros(1, dtype=torch.int32, device=self.d.flat.device)
-        ops.nonfinite_count([self.loss_g, self.loss_d, self.d.flat, self.d.exp_avg, self.d.exp_avg_sq, *tensors], self._nf)
-        n = int(self._nf.item())
-        self._nf.zero_()
+        nf = self._count_nonfinite([self.loss_g, self.loss_d, self.d.flat, self.d.exp_avg, self.d.exp_avg_sq, *tensors])
+        n = int(nf.item())
+        nf.zero_()
         if n:
             raise ops.NonFiniteError(f"{type(self).__name__}: {n} non-finite value(s) in inputs, losses, discriminator "
                                      f"parameters or optimizer state after iteration {self.iterations}")
@@ -270,23 +340,20 @@ class SimnnTrainer(_TrainerBase):
                            disc.fc1.bias, disc.fc2.weight, disc.fc2.bias], lr, betas, eps, compute_dtype,
                           elide_dead_backward, process_group)
         self._last_generated = None
-        self._graph_gen = None     # pipelined capture: the generator forward as a graph of its own (see capture)
-        self._gen_event = None     # recorded behind the last replay of that graph
         self._prepared = None      # (packed conv2 images, permuted fc1 weight) for the current weights
         self.overlap = overlap
         self._tm_cache = {}        # tap-major copies of the generator's ConvTranspose2d weights (per weight version)
         self._side = None
-        self._graph = None
-        self._scratch_grads = None
         self._pending_fake = None  # step_pipelined: fake batch whose generator half has not run yet (= _fake_buf)
         self._fake_buf = None      # trainer-owned copy of that batch
+        self._pieces = None        # world > 1 / pieces=True: (the five graphs, the tensors that cross their boundaries)
+        self._piece_streams = None
 
     @property
     def last_generated(self):
         """The generator's output of the last iteration; after a pipelined ``replay`` it is produced on a stream of the
         trainer's own, and reading it makes the current stream wait for that stream's last replay."""
-        if self._gen_event is not None and not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream().wait_event(self._gen_event)
+        self._join_generators()
         return self._last_generated
 
     def invalidate_weights(self):
@@ -296,6 +363,13 @@ class SimnnTrainer(_TrainerBase):
     def _refresh_operands(self):
         if self._prepared is not None:
             Fn.simnn_disc_prepare(self.d.views[2], self.d.views[4], self.dt, out=self._prepared)
+
+    def _operands(self):
+        """(packed conv2 images, permuted fc1 weight) of the current weights: built on first use, from then on
+        refreshed in place by ``_adam`` (cross-iteration state: the storage must be stable under graph replay)."""
+        if self._prepared is None:
+            self._prepared = Fn.simnn_disc_prepare(self.d.views[2], self.d.views[4], self.dt)
+        return self._prepared
 
     def _adam(self):
         """Adam, with fc1.weight's two layout changes folded in: its gradient slot holds the channels-last (128, P, 32)
@@ -310,19 +384,15 @@ class SimnnTrainer(_TrainerBase):
             ops.simnn_conv2_pack(d.views[2], self.dt, out=self._prepared[0])
             return
         # one launch: adam_prep + Adam(small) + Adam(fc1.weight) + conv2 re-pack (gdm_simnn_adam_step)
-        if getattr(self, "_adam_done", None) is None:
+        if self._adam_done is None:
             # completion counters + cached bias-correction terms; sync_hyper zeroes it when it rewrites the record
             self._adam_done = d.derived_record = torch.zeros(ops.SIMNN_ADAM_RECORD_INTS, dtype=torch.int32,
                                                              device=d.flat.device)
-        want = d.sync_hyper(self.lr, self.betas, self.eps, 1.0 / self.world)
-        if d._hyper is None:
-            d._hyper = ops.adam_hyper(d.flat.device, *want, step=d.step_count)
-            d._hyper_host = want
-        d.step_count += 1
+        hyper = d.hyper_record(self.lr, self.betas, self.eps, 1.0 / self.world)
         ns = d.n_small
         ops.simnn_adam_step(d.flat[ns:], d.grad[ns:], d.exp_avg[ns:], d.exp_avg_sq[ns:], n, 32, k // 32, self._prepared[1],
                             d.flat[:ns], d.grad[:ns], d.exp_avg[:ns], d.exp_avg_sq[:ns], d.views[2], self._prepared[0],
-                            d._hyper, self._adam_done)
+                            hyper, self._adam_done)
 
     def _gen_state(self):
         g = self.gen
@@ -331,43 +401,110 @@ class SimnnTrainer(_TrainerBase):
                for bn in (g.batch_norm1, g.batch_norm2, g.batch_norm3)]
         return ws, bns
 
-    def _streams(self, dev):
+    def _streams(self, dev, fork=True):
+        """The side streams of the eager schedules -- side[0] generator forward, side[1] fc1's weight gradient, side[2]
+        the previous iteration's generator half -- or None: every branch on the current stream."""
+        if not (self.overlap and fork):
+            return None
         if self._side is None:
             self._side = [torch.cuda.Stream(dev) for _ in range(3)]
         return self._side
 
-    def _d_backward(self, saved, dh, pack, wf1p, outs, x_pair, keep, fork=True):
-        """Discriminator backward below the head: fc1's weight gradient runs beside the data-gradient chain
-        (fork=False: everything on the current stream -- a branch of a captured graph must not fork again: a
-        second-level fork crashed hipStreamEndCapture)."""
-        dt = self.dt
-        x, p1, code1, flat, code2 = saved[:5]
-        b = p1.shape[0]
-        n, k = wf1p.shape
-        main = torch.cuda.current_stream()
-        side = self._streams(p1.device) if (self.overlap and fork) else None
-        # branch A: fc1 weight gradient
-        if side:
-            side[1].wait_stream(main)
-        with torch.cuda.stream(side[1] if side else main):
-            # (128, P*32): the channels-last layout of the feature map, kept as it is -- Adam transposes on the fly
-            ops.gemm(dh.t(), flat, compute=dt, out=outs[4].view(n, k))
-            if self.world > 1 and outs is self.d.grad_views:
-                # 99.9 % of the exchange (fc1.weight's gradient) starts now and overlaps the convolution backward
-                self._reduce_big_async()
-        # main: fc1 data gradient = pooled gradient of the conv trunk
-        dflat = ops.gemm(dh, wf1p, compute=dt, out_dtype=dt)
-        h1s, w1s = p1.shape[1], p1.shape[2]
-        dp2 = dflat.view(b, h1s // 2, w1s // 2, 32)
+    # ---- stages: each enqueues a fixed run of launches on the current stream -----------------------------------------
+    def _gen_forward(self, noise, keep):
+        """SIMNN.py:293-296; the output only feeds the (external) bridge."""
+        ws, bns = self._gen_state()
+        self._last_generated, gsaved = Fn.simnn_gen_forward(noise, ws, bns, self.gen.training, self.dt,
+                                                            cache=self._tm_cache, need_backward=False)
+        keep.append(gsaved)
+        return self._last_generated
+
+    def _conv1_pair(self, real, fake):
+        """conv1 of the 2B batch [real ; fake] (SIMNN.py:282-316 run D(real) and D(fake) as one batch) -> (p1, code1)."""
+        w1, b1 = self.d.views[:2]
+        b, h, w = real.shape
+        h1, w1s = (h + 1) // 2, (w + 1) // 2
+        p1 = torch.empty((2 * b, h1, w1s, 16), dtype=ops.torch_dtype(self.dt), device=real.device)
+        code1 = torch.empty((2 * b, h1, ops.simnn_code1_width(w1s)), dtype=torch.int64, device=real.device)
+        # two B launches, not one 2B launch (``x1=fake`` of ops.simnn_conv1_fwd): inside the iteration the 2B launch takes
+        # 64-66 us against 2 x 30 (same-box A/B of the step: 0.612-0.614 vs 0.608-0.610 ms)
+        ops.simnn_conv1_fwd(real, w1, b1, self.dt, out=(p1[:b], code1[:b]))
+        ops.simnn_conv1_fwd(fake, w1, b1, self.dt, out=(p1[b:], code1[b:]))
+        return p1, code1
+
+    def _features_head(self, x, trunk, n0, y0, y1, loss_out, grad_out=None, want_grad=True):
+        """conv2 + fc1 on ``trunk`` = (p1, code1) filled by ``_conv1_pair`` (or, trunk None, conv1 + conv2 + fc1 on the
+        batch ``x``), then fc2 + sigmoid + BCE with label y0 on the first n0 rows and y1 on the rest + the head's
+        backward: one launch pair.  Returns (saved, dh, what else has to stay alive)."""
+        w1, b1, _w2, b2, _wf1, bf1, wf2, bf2 = self.d.views
+        pack, wf1p = self._operands()
+        hid, saved = Fn.simnn_disc_features(x, w1, b1, pack, b2, wf1p, bf1, self.dt, trunk_out=trunk)
+        prob, dh, _ = ops.simnn_head(hid, wf2, bf2, n0, y0, y1, loss_out=loss_out, want_grad=want_grad,
+                                     grad_out=grad_out, dh_dtype=self.dt)
+        return saved, dh, (hid, prob)
+
+    def _disc_features_head(self, trunk):
+        """The discriminator step's forward above conv1 and its loss (labels 0.9 / 0.1, SIMNN.py:284-311)."""
+        gv = self.d.grad_views
+        return self._features_head(None, trunk, trunk[0].shape[0] // 2, 0.9, 0.1, self.loss_d,
+                                   grad_out=(gv[6], gv[7], gv[5]))
+
+    def _fc1_dw(self, saved, dh, outs):
+        """fc1's weight gradient into outs[4]."""
+        n, k = self._prepared[1].shape
+        # (128, P*32): the channels-last layout of the feature map, kept as it is -- Adam transposes on the fly
+        ops.gemm(dh.t(), saved[3], compute=self.dt, out=outs[4].view(n, k))
+
+    def _backward_rest(self, saved, dh, outs, x_pair, keep):
+        """The backward below fc1: its data gradient, conv2's weight gradient, conv2's data gradient with conv1's
+        weight gradient fused in.  x_pair = (x0, x1 or None): the input tensor(s) the batch was made of."""
+        _x, p1, code1, _flat, code2 = saved[:5]
+        pack, wf1p = self._prepared
+        # fc1 data gradient = pooled gradient of the conv trunk
+        dflat = ops.gemm(dh, wf1p, compute=self.dt, out_dtype=self.dt)
+        dp2 = dflat.view(p1.shape[0], p1.shape[1] // 2, p1.shape[2] // 2, 32)
         keep.append(dflat)
         # conv2 weight gradient, then conv2 data gradient with conv1's weight gradient fused in: both on the main
         # stream -- they are issue-bound persistent kernels that fill the chip, side by side they only take turns
         # (tools/overlap_probe.py), and one after the other each runs at its own speed
         ops.simnn_conv2_bwd_weight(dp2, code2, p1, out=(outs[2], outs[3]))
-        x0, x1 = x_pair if x_pair is not None else (x, None)
-        ops.simnn_conv2_bwd_fused(dp2, code2, pack, code1, x0, x1, out=(outs[0], outs[1]))
+        ops.simnn_conv2_bwd_fused(dp2, code2, pack, code1, x_pair[0], x_pair[1], out=(outs[0], outs[1]))
+
+    def _d_backward(self, saved, dh, outs, x_pair, keep, fork=True):
+        """Discriminator backward below the head: fc1's weight gradient runs beside the data-gradient chain
+        (fork=False: everything on the current stream -- a branch of a captured graph must not fork again: a
+        second-level fork crashed hipStreamEndCapture)."""
+        main = torch.cuda.current_stream()
+        side = self._streams(saved[1].device, fork)
+        if side:
+            side[1].wait_stream(main)
+        with torch.cuda.stream(side[1] if side else main):
+            self._fc1_dw(saved, dh, outs)
+            if self.world > 1 and outs is self.d.grad_views:
+                # 99.9 % of the exchange (fc1.weight's gradient) starts now and overlaps the convolution backward
+                self._reduce_big_async()
+        self._backward_rest(saved, dh, outs, x_pair, keep)
         if side:
             main.wait_stream(side[1])
+
+    def _generator_half(self, fake, keep, fork=False):
+        """SIMNN.py:322-331 on the current stream: D forward on fake with the current (updated) weights, label 1.0, and
+        (faithful mode) the dead backward: gen_loss.backward() only fills D's .grad, which the next zero_grad() wipes
+        (SIMNN.py:330, 282), so it goes into a scratch set of gradient buffers.  ``fork`` as in ``_d_backward``."""
+        saved, dh, head = self._features_head(fake, None, fake.shape[0], 1.0, 1.0, self.loss_g,
+                                              want_grad=not self.elide)
+        if not self.elide:
+            self._d_backward(saved, dh, self._scratch(), (fake, None), keep, fork=fork)
+        keep.append((saved, dh, head))
+
+    # ---- schedules: where the stages run -------------------------------------------------------------------------------
+    def _gen_forward_beside(self, noise, keep, side):
+        """The generator forward on its side stream, forked from the current one (side None: on the current one)."""
+        main = torch.cuda.current_stream()
+        if side:
+            side[0].wait_stream(main)
+        with torch.cuda.stream(side[0] if side else main):
+            return self._gen_forward(noise, keep)
 
     @torch.no_grad()
     def step(self, real, noise, fake):
@@ -378,99 +515,43 @@ class SimnnTrainer(_TrainerBase):
         all-reduce; ``disc_loss_value()`` divides by world)."""
         if self._pending_fake is not None:
             self.flush()
-        dt = self.dt
-        w1, b1, w2, b2, wf1, bf1, wf2, bf2 = self.d.views
-        gv = self.d.grad_views
         real = Fn._f32c(real)
         self._watch(real, noise, fake)
-        b, h, w = real.shape
         main = torch.cuda.current_stream()
-        side = self._streams(real.device) if self.overlap else None
+        side = self._streams(real.device)
         keep = []
-        ws, bns = self._gen_state()
-
-        def generator_forward():
-            # SIMNN.py:293-296; the output only feeds the (external) bridge -> own stream
-            if side:
-                side[0].wait_stream(main)
-            with torch.cuda.stream(side[0] if side else main):
-                generated, gsaved = Fn.simnn_gen_forward(noise, ws, bns, self.gen.training, dt, cache=self._tm_cache,
-                                                           need_backward=False)
-                keep.append(gsaved)
-            self._last_generated = generated
-            return generated
-
         bridge = callable(fake)
         if bridge:
-            generated = generator_forward()
+            generated = self._gen_forward_beside(noise, keep, side)
             if side:
                 main.wait_stream(side[0])
             fake = fake(generated)
         fake = Fn._f32c(fake.to(real.device))
         assert fake.shape == real.shape, (fake.shape, real.shape)
         # --- discriminator step on the 2B batch [real ; fake] (SIMNN.py:282-316)
-        if self._prepared is None:
-            self._prepared = Fn.simnn_disc_prepare(w2, wf1, dt)
-        pack, wf1p = self._prepared
-        h1, w1s = (h + 1) // 2, (w + 1) // 2
-        adt = ops.torch_dtype(dt)
-        p1 = torch.empty((2 * b, h1, w1s, 16), dtype=adt, device=real.device)
-        code1 = torch.empty((2 * b, h1, ops.simnn_code1_width(w1s)), dtype=torch.int64, device=real.device)
-        # two B launches, not one 2B launch (ops.simnn_conv1_fwd(..., x1=fake)): inside the iteration the 2B launch takes
-        # 64-66 us against 2 x 30 (same-box A/B of the step: 0.612-0.614 vs 0.608-0.610 ms)
-        ops.simnn_conv1_fwd(real, w1, b1, dt, out=(p1[:b], code1[:b]))
-        ops.simnn_conv1_fwd(fake, w1, b1, dt, out=(p1[b:], code1[b:]))
+        self._operands()
+        trunk = self._conv1_pair(real, fake)
         if not bridge:
             # tensor stand-in for the bridge: the generator is independent of the discriminator step and runs beside
             # it.  Forked after the first main-stream launch: a branch that forks at the very root of a captured graph
             # was observed to run BEFORE the main branch instead of beside it.
-            generator_forward()
-        hid, saved = Fn.simnn_disc_features(None, w1, b1, pack, b2, wf1p, bf1, dt, trunk_out=(p1, code1))
-        # fc2 + sigmoid + both BCE terms (labels 0.9 / 0.1, SIMNN.py:284-311) + head backward: one launch pair
-        _prob, dh, _ = ops.simnn_head(hid, wf2, bf2, b, 0.9, 0.1, loss_out=self.loss_d, grad_out=(gv[6], gv[7], gv[5]),
-                                      dh_dtype=dt)
-        self._d_backward(saved, dh, pack, wf1p, gv, (real, fake), keep)
+            self._gen_forward_beside(noise, keep, side)
+        saved, dh, head = self._disc_features_head(trunk)
+        self._d_backward(saved, dh, self.d.grad_views, (real, fake), keep)
         # Adam also rewrites the weight-derived operands in place (fc1's operand copy inside the kernel, conv2's packed
         # images right after): they are cross-iteration state, so their storage must be stable under graph replay
         self._reduce_and_step()
-        # --- "generator" step (SIMNN.py:322-331): D forward on fake with the updated weights, label 1.0
-        p1g = torch.empty((b, h1, w1s, 16), dtype=adt, device=real.device)
-        code1g = torch.empty((b, h1, ops.simnn_code1_width(w1s)), dtype=torch.int64, device=real.device)
-        ops.simnn_conv1_fwd(fake, w1, b1, dt, out=(p1g, code1g))
-        hid_g, saved_g = Fn.simnn_disc_features(None, w1, b1, pack, b2, wf1p, bf1, dt, trunk_out=(p1g, code1g))
-        _prob, dh_g, _ = ops.simnn_head(hid_g, wf2, bf2, b, 1.0, 1.0, loss_out=self.loss_g, want_grad=not self.elide,
-                                        dh_dtype=dt)
-        if not self.elide:
-            # dead values: gen_loss.backward() only fills D's .grad, which the next zero_grad() wipes (SIMNN.py:330,
-            # 282); they are computed (faithful mode) into a scratch set of gradient buffers
-            if self._scratch_grads is None:
-                self._scratch_grads = [torch.empty_like(g) for g in gv]
-            self._d_backward(saved_g, dh_g, pack, wf1p, self._scratch_grads, (fake, None), keep)
+        # --- "generator" step (SIMNN.py:322-331)
+        self._generator_half(fake, keep, fork=True)
         if side:
             main.wait_stream(side[0])
         # gen_opt.step(): every generator .grad is None -> no-op
         self.iterations += 1
-        del keep
+        del keep, saved, dh, head
         self._anomaly_check()
         return self.loss_d, self.loss_g
 
     # ---- the same iteration, generator half of iteration i beside the discriminator step of iteration i+1 ----------
-    def _generator_half(self, fake, keep):
-        """SIMNN.py:322-331 on the current stream: D forward on fake with the current weights, label 1.0, and (faithful
-        mode) the dead backward into scratch gradient buffers.  Needs fresh ``self._prepared``."""
-        dt = self.dt
-        w1, b1, w2, b2, wf1, bf1, wf2, bf2 = self.d.views
-        pack, wf1p = self._prepared
-        b = fake.shape[0]
-        hid_g, saved_g = Fn.simnn_disc_features(fake, w1, b1, pack, b2, wf1p, bf1, dt)
-        _prob, dh_g, _ = ops.simnn_head(hid_g, wf2, bf2, b, 1.0, 1.0, loss_out=self.loss_g, want_grad=not self.elide,
-                                        dh_dtype=dt)
-        if not self.elide:
-            if self._scratch_grads is None:
-                self._scratch_grads = [torch.empty_like(g) for g in self.d.grad_views]
-            self._d_backward(saved_g, dh_g, pack, wf1p, self._scratch_grads, (fake, None), keep, fork=False)
-        keep.append((hid_g, saved_g, dh_g))
-
     @torch.no_grad()
     def step_pipelined(self, real, noise, fake, with_generator=True):
         """Like ``step`` for tensor inputs, but the generator half of THIS iteration is left pending and the pending
@@ -478,40 +559,19 @@ class SimnnTrainer(_TrainerBase):
         iteration, gen_loss of the previous one) as device tensors; call ``flush`` after the last iteration."""
         if callable(fake):
             raise ops.GdmError("step_pipelined needs a tensor for the fake batch (the bridge is host code)")
-        dt = self.dt
-        w1, b1, w2, b2, wf1, bf1, wf2, bf2 = self.d.views
-        gv = self.d.grad_views
         real = Fn._f32c(real)
         fake = Fn._f32c(fake.to(real.device))
         assert fake.shape == real.shape, (fake.shape, real.shape)
-        b, h, w = real.shape
         main = torch.cuda.current_stream()
-        side = self._streams(real.device) if self.overlap else None
+        side = self._streams(real.device)
         keep = []
-        ws, bns = self._gen_state()
         pending = self._pending_fake
-        if self._prepared is None:
-            self._prepared = Fn.simnn_disc_prepare(w2, wf1, dt)
-        pack, wf1p = self._prepared
-        if self._scratch_grads is None:
-            self._scratch_grads = [torch.empty_like(g) for g in gv]
-        h1, w1s = (h + 1) // 2, (w + 1) // 2
-        adt = ops.torch_dtype(dt)
-        p1 = torch.empty((2 * b, h1, w1s, 16), dtype=adt, device=real.device)
-        code1 = torch.empty((2 * b, h1, ops.simnn_code1_width(w1s)), dtype=torch.int64, device=real.device)
-        # two B launches, not one 2B launch (ops.simnn_conv1_fwd(..., x1=fake)): inside the iteration the 2B launch takes
-        # 64-66 us against 2 x 30 (same-box A/B of the step: 0.612-0.614 vs 0.608-0.610 ms)
-        ops.simnn_conv1_fwd(real, w1, b1, dt, out=(p1[:b], code1[:b]))
-        ops.simnn_conv1_fwd(fake, w1, b1, dt, out=(p1[b:], code1[b:]))
+        self._operands()           # both made here, on the caller's stream (the half that uses the scratch
+        self._scratch()            # gradients runs on a side stream)
+        trunk = self._conv1_pair(real, fake)
         # branches fork after the first main-stream launch (see step)
         if with_generator:
-            if side:
-                side[0].wait_stream(main)
-            with torch.cuda.stream(side[0] if side else main):
-                generated, gsaved = Fn.simnn_gen_forward(noise, ws, bns, self.gen.training, dt, cache=self._tm_cache,
-                                                               need_backward=False)
-                keep.append(gsaved)
-            self._last_generated = generated
+            self._gen_forward_beside(noise, keep, side)
         # generator half of the previous iteration: reads the weights / prepared operands that stay untouched until
         # this call's Adam, writes only gen_loss and scratch buffers.  Then, on the same stream (so after the half's last
         # read of it), the trainer's own copy of the fake batch is refreshed with THIS iteration's: the caller may
@@ -526,10 +586,8 @@ class SimnnTrainer(_TrainerBase):
                     raise ops.GdmError("step_pipelined saw a new batch geometry inside a graph capture")
                 self._fake_buf = torch.empty_like(fake)
             self._fake_buf.copy_(fake)
-        hid, saved = Fn.simnn_disc_features(None, w1, b1, pack, b2, wf1p, bf1, dt, trunk_out=(p1, code1))
-        _prob, dh, _ = ops.simnn_head(hid, wf2, bf2, b, 0.9, 0.1, loss_out=self.loss_d, grad_out=(gv[6], gv[7], gv[5]),
-                                      dh_dtype=dt)
-        self._d_backward(saved, dh, pack, wf1p, gv, (real, fake), keep)
+        saved, dh, head = self._disc_features_head(trunk)
+        self._d_backward(saved, dh, self.d.grad_views, (real, fake), keep)
         if side:
             main.wait_stream(side[2])
         self._reduce_and_step()         # (Adam refreshes the weight-derived operands in place)
@@ -537,7 +595,7 @@ class SimnnTrainer(_TrainerBase):
             main.wait_stream(side[0])
         self._pending_fake = self._fake_buf
         self.iterations += 1
-        del keep
+        del keep, saved, dh, head
         return self.loss_d, self.loss_g
 
     @torch.no_grad()
@@ -571,29 +629,16 @@ class SimnnTrainer(_TrainerBase):
         self._pieces = None
         self._static = (Fn._f32c(real), noise, Fn._f32c(fake))
         fn = self.step_pipelined if pipelined else self.step
-        warm = torch.cuda.Stream(real.device)
-        warm.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(warm):
-            for _ in range(2):
-                fn(*self._static)
-        torch.cuda.current_stream().wait_stream(warm)
-        torch.cuda.synchronize()
+        self._warm_up(lambda: fn(*self._static), real.device)
         self._graph_gen = None
-        self._graph = torch.cuda.CUDAGraph()
         if pipelined and generator_graph:
-            ws, bns = self._gen_state()
-            self._graph_gen = torch.cuda.CUDAGraph()
-            with ops.workspace_namespace(("graph", id(self._graph_gen))), torch.cuda.graph(self._graph_gen):
-                self._last_generated, _gs = Fn.simnn_gen_forward(self._static[1], ws, bns, self.gen.training, self.dt,
-                                                                 cache=self._tm_cache, need_backward=False)
+            keep = []
+            self._graph_gen = self._capture(lambda: self._gen_forward(noise, keep))
             self._gen_replay_stream = torch.cuda.Stream(real.device)
-            with ops.workspace_namespace(("graph", id(self._graph))), torch.cuda.graph(self._graph):
-                self.step_pipelined(*self._static, with_generator=False)   # finds a pending half and leaves one
+            # (finds a pending half and leaves one)
+            self._graph = self._capture(lambda: self.step_pipelined(*self._static, with_generator=False))
         else:
-            with ops.workspace_namespace(("graph", id(self._graph))), torch.cuda.graph(self._graph):
-                fn(*self._static)
-        self.d.step_count -= 1     # the captured call did not execute: the device-side step counter did not move
-        self.iterations -= 1
+            self._graph = self._capture(lambda: fn(*self._static))
         return self._graph
 
     # ---- the pipelined iteration as graphs around the data-parallel exchange (world > 1) ------------------------------
@@ -611,63 +656,30 @@ class SimnnTrainer(_TrainerBase):
         ``self._pieces`` so their storage is never handed out again.  Bit-identical to eager ``step_pipelined`` calls."""
         real, fake = Fn._f32c(real), Fn._f32c(fake)
         self._static = (real, noise, fake)
-        dev = real.device
-        warm = torch.cuda.Stream(dev)
-        warm.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(warm):
-            for _ in range(2):
-                self.step_pipelined(*self._static)
-        torch.cuda.current_stream().wait_stream(warm)
-        torch.cuda.synchronize()
-        dt = self.dt
-        w1, b1, w2, b2, wf1, bf1, wf2, bf2 = self.d.views
+        self._warm_up(lambda: self.step_pipelined(*self._static), real.device)
         gv = self.d.grad_views
-        pack, wf1p = self._prepared
-        b, h, w = real.shape
-        h1, w1s = (h + 1) // 2, (w + 1) // 2
-        adt = ops.torch_dtype(dt)
-        g = {k: torch.cuda.CUDAGraph() for k in ("gen", "half", "a", "b", "c")}
-        ctx = {}
+        keep, ctx = [], {}
 
-        def cap(name):
-            return ops.workspace_namespace(("graph", id(g[name])))
-
-        with cap("gen"), torch.cuda.graph(g["gen"]):
-            ws, bns = self._gen_state()
-            self._last_generated, _gs = Fn.simnn_gen_forward(noise, ws, bns, self.gen.training, dt, cache=self._tm_cache,
-                                                             need_backward=False)
-        with cap("half"), torch.cuda.graph(g["half"]):
-            keep = []
+        def half():
             self._generator_half(self._pending_fake, keep)
             self._fake_buf.copy_(fake)
-            ctx["half_keep"] = keep
-        with cap("a"), torch.cuda.graph(g["a"]):
-            p1 = torch.empty((2 * b, h1, w1s, 16), dtype=adt, device=dev)
-            code1 = torch.empty((2 * b, h1, ops.simnn_code1_width(w1s)), dtype=torch.int64, device=dev)
-            ops.simnn_conv1_fwd(real, w1, b1, dt, out=(p1[:b], code1[:b]))
-            ops.simnn_conv1_fwd(fake, w1, b1, dt, out=(p1[b:], code1[b:]))
-            hid, saved = Fn.simnn_disc_features(None, w1, b1, pack, b2, wf1p, bf1, dt, trunk_out=(p1, code1))
-            _prob, dh, _ = ops.simnn_head(hid, wf2, bf2, b, 0.9, 0.1, loss_out=self.loss_d, grad_out=(gv[6], gv[7], gv[5]),
-                                          dh_dtype=dt)
-            ctx.update(saved=saved, dh=dh, hid=hid, prob=_prob)
-            _x, p1, code1, flat, code2 = saved[:5]
-            n, k = wf1p.shape
+
+        def a():
+            ctx["saved"], ctx["dh"], ctx["head"] = self._disc_features_head(self._conv1_pair(real, fake))
             # fc1's weight gradient closes this graph: its all-reduce (99.9 % of the exchange) then runs beside graph B.
             # (As a graph of its own on a third stream -- the eager schedule's branch -- every iteration paid two more
             # cross-queue dependencies: 0.785 ms against 0.666 eager on one rank.)
-            ops.gemm(dh.t(), flat, compute=dt, out=gv[4].view(n, k))
-        with cap("b"), torch.cuda.graph(g["b"]):
-            dflat = ops.gemm(ctx["dh"], wf1p, compute=dt, out_dtype=dt)
-            dp2 = dflat.view(2 * b, h1 // 2, w1s // 2, 32)
-            ops.simnn_conv2_bwd_weight(dp2, code2, p1, out=(gv[2], gv[3]))
-            ops.simnn_conv2_bwd_fused(dp2, code2, pack, code1, real, fake, out=(gv[0], gv[1]))
-            ctx["dflat"] = dflat
-        with cap("c"), torch.cuda.graph(g["c"]):
-            self._adam()
-        self.d.step_count -= 1     # the captured Adam did not execute
+            self._fc1_dw(ctx["saved"], ctx["dh"], gv)
+
+        g = {"gen": self._capture(lambda: self._gen_forward(noise, keep)),
+             "half": self._capture(half),
+             "a": self._capture(a),
+             "b": self._capture(lambda: self._backward_rest(ctx["saved"], ctx["dh"], gv, (real, fake), keep)),
+             "c": self._capture(self._adam)}
+        ctx["keep"] = keep
         self._pieces = (g, ctx)
         self._graph, self._graph_gen = g["a"], None
-        self._piece_streams = tuple(torch.cuda.Stream(dev) for _ in range(3))      # sg, sh, s1
+        self._piece_streams = tuple(torch.cuda.Stream(real.device) for _ in range(3))      # sg, sh, s1
         return g
 
     def _replay_pieces(self):
@@ -675,14 +687,8 @@ class SimnnTrainer(_TrainerBase):
         sg, sh, s1 = self._piece_streams
         main = torch.cuda.current_stream()
         # G and H start behind everything the caller has enqueued (refills of the static inputs, the previous Adam)
-        sg.wait_stream(main)
-        with torch.cuda.stream(sg):
-            g["gen"].replay()
-            self._gen_event = sg.record_event()
-        sh.wait_stream(main)
-        with torch.cuda.stream(sh):
-            g["half"].replay()
-            half_ev = sh.record_event()
+        self._gen_event, = self._replay_beside(main, g["gen"], stream=sg)
+        half_ev, = self._replay_beside(main, g["half"], stream=sh)
         g["a"].replay()
         if self.world > 1:
             s1.wait_stream(main)
@@ -699,17 +705,13 @@ class SimnnTrainer(_TrainerBase):
 
     def replay(self):
         self._sync_hyper()         # lr schedule etc.: the captured Adam reads the device record
-        if getattr(self, "_pieces", None) is not None:
+        if self._pieces is not None:
             return self._replay_pieces()
         main = torch.cuda.current_stream()
         if self._graph_gen is not None:
             # behind everything the caller has enqueued so far (its refill of ``noise``, the previous iteration) and
             # beside this iteration's main graph
-            sg = self._gen_replay_stream
-            sg.wait_stream(main)
-            with torch.cuda.stream(sg):
-                self._graph_gen.replay()
-                self._gen_event = sg.record_event()
+            self._gen_event, = self._replay_beside(main, self._graph_gen)
         self._graph.replay()
         if self._graph_gen is not None:
             # whatever the caller enqueues next (a refill of the static inputs, the next replay) comes after the
@@ -744,20 +746,17 @@ class MmganTrainer(_TrainerBase):
         self._init_common([d.conv1.weight, d.conv1.bias, d.conv2.weight, d.conv2.bias, d.fc.weight, d.fc.bias], lr,
                           betas, eps, compute_dtype, elide_dead_backward, process_group)
         self._last_g1 = self._last_g2 = None
+        self._gen_b = None         # the generators' second forward of the iteration: what the G step's bridge consumes
         self._pack = None          # packed weight images of the fused discriminator kernel (persistent buffer)
-        self._graph = None
-        self._graph_gen = None     # one rank: the generators' launches as graphs of their own (see capture)
-        self._graph_gen_in = None
-        self._gen_event = None     # recorded behind the last replay of that graph
-        self._gen_stream = None
-        self._gen_replay_stream = None
+        self._pack_t = None        # the roll length they were packed for
+        self._graph_gen_in = None  # one rank: the staging launch of the generators' graph, a graph of its own (capture)
+        self._gen_stream = None    # the two side streams of the eager generator chains
+        self._gen_join_pending = False     # they were forked late and have not been joined yet
+        self._adam_in_kernel = False       # the D step's kernel applies Adam itself
+        self._adam_views = None
 
     # The generators' outputs of the last iteration.  After ``replay`` on one rank they are produced on a stream of the
     # trainer's own: reading them here makes the CURRENT stream wait for that stream's last replay.
-    def _join_generators(self):
-        if self._gen_event is not None and not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream().wait_event(self._gen_event)
-
     @property
     def last_g1(self):
         self._join_generators()
@@ -780,12 +779,18 @@ class MmganTrainer(_TrainerBase):
         return [(blk[0].weight.detach(), blk[0].bias.detach(), blk[1].weight.detach(), blk[1].bias.detach(),
                  blk[1].running_mean, blk[1].running_var, blk[1].num_batches_tracked) for blk in gen.gen]
 
+    def _g1_input(self, given, noise1):
+        """Generator 1's conditioning input: the caller's, or (network_tests.py:83-84) drawn on the CPU generator -- one
+        draw per forward, in call order -- and then moved to the device."""
+        if given is not None:
+            return given
+        return torch.randn(len(noise1), self.mm.generator1.input_tensor_dim).to(noise1.device)
+
     def _generators_forward(self, noise1, noise2, beats, g1_input, streams=None):
         """Both generators (network_tests.py:186-187).  They are independent chains of four latency-bound
         Linear+BN+Sigmoid launches: with ``streams`` = (s1, s2) each chain runs on its own stream."""
         mm, dt = self.mm, self.dt
-        if g1_input is None:   # network_tests.py:83-84: drawn on the CPU generator, then moved
-            g1_input = torch.randn(len(noise1), mm.generator1.input_tensor_dim).to(noise1.device)
+        g1_input = self._g1_input(g1_input, noise1)
         s1, s2 = streams if streams is not None else (None, None)
         with torch.cuda.stream(s1 if s1 is not None else torch.cuda.current_stream()):
             x1 = torch.cat((noise1, g1_input), dim=1)
@@ -815,18 +820,14 @@ class MmganTrainer(_TrainerBase):
         if not self._adam_in_kernel:
             return None
         d = self.d
-        want = d.sync_hyper(self.lr, self.betas, self.eps, 1.0)
-        if d._hyper is None:
-            d._hyper = ops.adam_hyper(d.flat.device, *want, step=d.step_count)
-            d._hyper_host = want
-        if getattr(self, "_adam_views", None) is None:
+        hyper = d.hyper_record(self.lr, self.betas, self.eps, 1.0)
+        if self._adam_views is None:
             offs = [((v.data_ptr() - d.flat.data_ptr()) // 4, v.numel()) for v in d.views]
             self._adam_views = ([d.flat[o:o + n] for o, n in offs], [d.exp_avg[o:o + n] for o, n in offs],
                                 [d.exp_avg_sq[o:o + n] for o, n in offs])
             self._adam_done = torch.zeros(1, dtype=torch.int32, device=d.flat.device)
-        d.step_count += 1
         p, m, v = self._adam_views
-        return dict(params=p, exp_avg=m, exp_avg_sq=v, hyper=d._hyper, done=self._adam_done)
+        return dict(params=p, exp_avg=m, exp_avg_sq=v, hyper=hyper, done=self._adam_done)
 
     def _gen_fused_ok(self, b):
         """Whether an iteration's generator work takes the fused chain (staged inputs + one launch per block depth)."""
@@ -854,11 +855,14 @@ class MmganTrainer(_TrainerBase):
         Returns (g1_a, g2_a, g1_b, g2_b); falls back to two sequential forwards where the fused block does not apply."""
         mm, dt = self.mm, self.dt
         b = len(noise1)
-        if self.exact_bn and self.world > 1 and mm.generator1.training and mm.generator2.training:
-            if g1_in_a is None:
-                g1_in_a = torch.randn(b, mm.generator1.input_tensor_dim).to(noise1.device)
-            if g1_in_b is None:
-                g1_in_b = torch.randn(b, mm.generator1.input_tensor_dim).to(noise1.device)
+        exact = self.exact_bn and self.world > 1 and mm.generator1.training and mm.generator2.training
+        if not exact and not self._gen_fused_ok(b):
+            g1a, g2a = self._generators_forward(noise1, noise2, beats, g1_in_a, streams)
+            g1b, g2b = self._generators_forward(noise1, noise2, beats, g1_in_b, streams)
+            return g1a, g2a, g1b, g2b
+        g1_in_a = self._g1_input(g1_in_a, noise1)      # call by call
+        g1_in_b = self._g1_input(g1_in_b, noise1)
+        if exact:
             a = mm.generator1.adj_size
             outs = []
             for g1_in in (g1_in_a, g1_in_b):     # the reference's call order: G1, G2 (294), then G1, G2 again (312)
@@ -866,15 +870,6 @@ class MmganTrainer(_TrainerBase):
                 o2 = Fn.mlp_bn_sigmoid_forward_global(torch.cat((noise2, beats), dim=1), self._layers(mm.generator2), self.pg)
                 outs += [o1.view(b, -1, a[0], a[1]), o2]
             return tuple(outs)
-        fused = self._gen_fused_ok(b)
-        if not fused:
-            g1a, g2a = self._generators_forward(noise1, noise2, beats, g1_in_a, streams)
-            g1b, g2b = self._generators_forward(noise1, noise2, beats, g1_in_b, streams)
-            return g1a, g2a, g1b, g2b
-        if g1_in_a is None:    # network_tests.py:83-84: drawn on the CPU generator, call by call
-            g1_in_a = torch.randn(b, mm.generator1.input_tensor_dim).to(noise1.device)
-        if g1_in_b is None:
-            g1_in_b = torch.randn(b, mm.generator1.input_tensor_dim).to(noise1.device)
         s1 = streams[0] if streams is not None else None
         l1, l2 = self._layers(mm.generator1), self._layers(mm.generator2)
         with torch.cuda.stream(s1 if s1 is not None else torch.cuda.current_stream()):
@@ -917,6 +912,13 @@ class MmganTrainer(_TrainerBase):
             self._gen_stream = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
         return self._gen_stream
 
+    def _join_sides(self):
+        """The current stream waits for both generator chains."""
+        main = torch.cuda.current_stream()
+        for sd in self._gen_stream:
+            main.wait_stream(sd)
+        self._gen_join_pending = False
+
     def _part_a(self, piano_roll, durations, beats, noise1, noise2, fake_a, g1_in_a, g1_in_b, with_generators=True):
         """D step up to the gradient (network_tests.py:293-307): the generators (both forwards of the iteration, see
         _generators_forward_both) on side streams beside the discriminator's forward + loss + backward; every branch
@@ -931,7 +933,6 @@ class MmganTrainer(_TrainerBase):
         fused = self._fused_ok(t)
         # the generators only feed the (external) bridge: each runs on a side stream of its own beside the
         # discriminator kernels (a generator's second forward follows its first one: BN running statistics)
-        main = torch.cuda.current_stream()
         sides = self._sides(dev)
 
         def generators():
@@ -954,8 +955,7 @@ class MmganTrainer(_TrainerBase):
             # branch: fork after a first small launch on the main stream)
             self.d.extra[1:4].zero_()
             g1, g2 = generators()
-            for sd in sides:
-                main.wait_stream(sd)
+            self._join_sides()
             fake_a = fake_a(g1, g2)
         if fused:
             if self._pack is None:
@@ -989,51 +989,37 @@ class MmganTrainer(_TrainerBase):
         # piece is a graph of its own and has to join its branches itself
         self._gen_join_pending = gen_late and self.world == 1
         if with_generators and not self._gen_join_pending:
-            for sd in sides:
-                main.wait_stream(sd)
+            self._join_sides()
 
     def _part_b(self, piano_roll, beats, noise1, noise2, fake_b, g1_in_b):
         """Adam (308), then the "G" step (311-315): D forward on the bridge's output for the generators' second forward
         (which ran at the start of the iteration: _generators_forward_both) + the dead backward in faithful mode."""
         dt = self.dt
         w1, b1, w2, b2, wf, bf = self.d.views
-        gv = self.d.grad_views
         t = piano_roll.shape[2]
         fused = self._fused_ok(t)
-        if not (fused and getattr(self, "_adam_in_kernel", False)):      # (else: already applied by _part_a's kernel)
+        if not (fused and self._adam_in_kernel):      # (else: already applied by _part_a's kernel)
             self._adam()
             if fused:
                 ops.dcnn_pack(w1, b1, w2, b2, wf, bf, t, out=self._pack)     # weights changed: refresh in place
         if callable(fake_b):
-            if getattr(self, "_gen_join_pending", False):
+            if self._gen_join_pending:
                 # mixed bridge (tensor fake_a, callable fake_b): the generator chains were forked late and are still
                 # running on their side streams -- the bridge reads their outputs on this stream
-                main = torch.cuda.current_stream()
-                for sd in self._sides(piano_roll.device):
-                    main.wait_stream(sd)
-                self._gen_join_pending = False
+                self._join_sides()
             fake_b = fake_b(*self._gen_b)      # the generators' second forward ran at the start of the iteration
+        # the loss, and unless elided the dead values (only D's .grad in the reference, wiped by the next zero_grad)
         if fused:
-            if self.elide:
-                ops.dcnn_fused(Fn._f32c(fake_b), None, t, 1.0, 1.0, self._pack, loss_out=self.loss_g, want_grad=False,
-                               criterion=self.criterion)
-            else:   # dead values (only D's .grad in the reference, wiped by the next zero_grad): scratch buffers
-                if getattr(self, "_scratch_grads", None) is None:
-                    self._scratch_grads = [torch.empty_like(g) for g in gv]
-                ops.dcnn_fused(Fn._f32c(fake_b), None, t, 1.0, 1.0, self._pack, loss_out=self.loss_g,
-                               grad_out=self._scratch_grads, criterion=self.criterion)
+            ops.dcnn_fused(Fn._f32c(fake_b), None, t, 1.0, 1.0, self._pack, loss_out=self.loss_g,
+                           want_grad=not self.elide, grad_out=None if self.elide else self._scratch(),
+                           criterion=self.criterion)
         else:
             logits_g, saved_g = Fn.dcnn_forward(fake_b, w1, b1, w2, b2, wf, bf, dt)
-            if self.elide:
-                self._criterion_loss(logits_g.view(-1), 1.0, loss_out=self.loss_g, want_grad=False)
-            else:
-                _, dlg = self._criterion_loss(logits_g.view(-1), 1.0, loss_out=self.loss_g)
-                Fn.dcnn_backward(saved_g, dlg, w2, wf, dt)     # dead values (only D's .grad in the reference)
-        if getattr(self, "_gen_join_pending", False):
-            main = torch.cuda.current_stream()
-            for sd in self._sides(piano_roll.device):
-                main.wait_stream(sd)
-            self._gen_join_pending = False
+            _, dlg = self._criterion_loss(logits_g.view(-1), 1.0, loss_out=self.loss_g, want_grad=not self.elide)
+            if not self.elide:
+                Fn.dcnn_backward(saved_g, dlg, w2, wf, dt)
+        if self._gen_join_pending:
+            self._join_sides()
 
     # ---- hipGraph capture for fixed input buffers --------------------------------------------------------------------
     def capture(self, piano_roll, durations, beats, noise1, noise2, fake_a, fake_b, g1_in_a, g1_in_b):
@@ -1049,13 +1035,14 @@ class MmganTrainer(_TrainerBase):
         if any(callable(a) for a in args) or any(a is None for a in args):
             raise ops.GdmError("graph capture needs tensor inputs (incl. g1_in_a/g1_in_b)")
         self._static = args
-        warm = torch.cuda.Stream(piano_roll.device)
-        warm.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(warm):
-            for _ in range(2):
-                self.step(*args[:7], g1_in_a=g1_in_a, g1_in_b=g1_in_b)
-        torch.cuda.current_stream().wait_stream(warm)
-        torch.cuda.synchronize()
+        self._warm_up(lambda: self.step(*args[:7], g1_in_a=g1_in_a, g1_in_b=g1_in_b), piano_roll.device)
+
+        def part_a(**kw):
+            self._part_a(piano_roll, durations, beats, noise1, noise2, fake_a, g1_in_a, g1_in_b, **kw)
+
+        def part_b():
+            self._part_b(piano_roll, beats, noise1, noise2, fake_b, g1_in_b)
+
         if self.world == 1:
             # TWO graphs without a single fork or join: the discriminator chain (zero, kernel, slab sum, Adam, re-pack,
             # kernel, slab sum) and the generators' eight launches.  Inside one multi-branch graph every edge between
@@ -1069,36 +1056,26 @@ class MmganTrainer(_TrainerBase):
             # limit, eval-mode generators) concatenates the caller's tensors itself, inside the block graph -- then
             # there is no staging graph and ``replay`` makes the caller's stream wait for the WHOLE generator graph
             # before a refill of the inputs may follow.
-            self._gen_staged = self._gen_fused_ok(len(noise1))
-            self._graph_gen_in = None
-            self._graph_gen = torch.cuda.CUDAGraph()
-            self._graph = torch.cuda.CUDAGraph()
-            ns_gen, ns_main = ("graph", id(self._graph_gen)), ("graph", id(self._graph))
-            staged, pool = None, None
-            if self._gen_staged:
-                self._graph_gen_in = torch.cuda.CUDAGraph()
-                with ops.workspace_namespace(ns_gen), torch.cuda.graph(self._graph_gen_in):
-                    staged = self._gen_inputs(noise1, noise2, beats, g1_in_a, g1_in_b)
-                pool = self._graph_gen_in.pool()
-            with ops.workspace_namespace(ns_gen), torch.cuda.graph(self._graph_gen, pool=pool):
+            staged = []
+
+            def stage():
+                staged.append(self._gen_inputs(noise1, noise2, beats, g1_in_a, g1_in_b))
+
+            def generators():
                 g1, g2, g1b, g2b = self._generators_forward_both(noise1, noise2, beats, g1_in_a, g1_in_b, None,
-                                                                 staged=staged)
+                                                                 staged=staged[0] if staged else None)
                 self._last_g1, self._last_g2 = g1, g2
                 self._gen_b = (g1b, g2b)
-            with ops.workspace_namespace(ns_main), torch.cuda.graph(self._graph):
-                self._part_a(piano_roll, durations, beats, noise1, noise2, fake_a, g1_in_a, g1_in_b,
-                             with_generators=False)
-                self._part_b(piano_roll, beats, noise1, noise2, fake_b, g1_in_b)
+
+            # (the staging graph and the block graph replay one after the other on one stream: one namespace, one pool)
+            gin = self._graph_gen_in = self._capture(stage) if self._gen_fused_ok(len(noise1)) else None
+            self._graph_gen = self._capture(generators, pool=gin.pool() if gin else None, namespace_of=gin)
+            self._graph = self._capture(lambda: (part_a(with_generators=False), part_b()))
             self._gen_replay_stream = torch.cuda.Stream(piano_roll.device)
         else:
-            ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with ops.workspace_namespace(("graph", id(ga))), torch.cuda.graph(ga):
-                self._part_a(piano_roll, durations, beats, noise1, noise2, fake_a, g1_in_a, g1_in_b)
-            pool = ga.pool()
-            with ops.workspace_namespace(("graph", id(ga))), torch.cuda.graph(gb, pool=pool):   # (sequential: shared)
-                self._part_b(piano_roll, beats, noise1, noise2, fake_b, g1_in_b)
+            ga = self._capture(part_a)
+            gb = self._capture(part_b, pool=ga.pool(), namespace_of=ga)      # (sequential: shared)
             self._graph = (ga, gb)
-        self.d.step_count -= 1     # the captured call did not execute: the device-side step counter did not move
         return self._graph
 
     def replay(self):
@@ -1111,21 +1088,14 @@ class MmganTrainer(_TrainerBase):
             # the generator graph: behind everything the caller has enqueued so far (its refill of the static inputs, the
             # previous iteration), beside this iteration's discriminator graph
             main = torch.cuda.current_stream()
-            sg = self._gen_replay_stream
-            sg.wait_stream(main)
-            with torch.cuda.stream(sg):
-                staged_ev = None
-                if self._graph_gen_in is not None:
-                    self._graph_gen_in.replay()
-                    staged_ev = sg.record_event()
-                self._graph_gen.replay()
-                self._gen_event = sg.record_event()
+            graphs = [g for g in (self._graph_gen_in, self._graph_gen) if g is not None]
+            *staged_ev, self._gen_event = self._replay_beside(main, *graphs)
             self._graph.replay()
             # whatever the caller enqueues next (a refill of the inputs, the next replay) comes after the generators'
             # READS of the caller's tensors: the one staging launch at the head of their stream.  (Waiting for their whole
             # graph cost 4 % at B = 256 and 17 % at B = 16, where the generators' chain is the longer one.)  Without a
             # staging graph (fallback generator chain) the block graph itself reads them: wait for all of it.
-            main.wait_event(staged_ev if staged_ev is not None else self._gen_event)
+            main.wait_event(staged_ev[0] if staged_ev else self._gen_event)
         self.d.step_count += 1
         self.iterations += 1
         return self.loss_d, self.loss_g

@@ -239,13 +239,13 @@ def test_fc1_gemms_at_their_real_shapes(comp, m, k):
     h1 = ops.gemm(fd, wd.t(), bias_n=bd, act=ops.ACT_RELU, compute=comp)
     _gemm_check(f"forward {tag}", h1.cpu(), rb(flat.float()), rb(wf1p).t(), bias=bf1, relu=True,
                 n_chain=pf["per_tiles"] * pf["kt"] + pf["split"] + 2, out_dt=torch.float32)
-    # dW = dh^T (128, M) @ flat (functional.py:97, train.py:352)
+    # dW = dh^T (128, M) @ flat (functional.py:97, train.py:456)
     pw = gemm_path(n, k, m, comp)
     _mirror_is_the_library(pw, ops.gemm_plan(dhd.t(), fd, compute=comp), f"dW {tag}")
     dw = ops.gemm(dhd.t(), fd, compute=comp)
     _gemm_check(f"dW {tag}", dw.cpu(), rb(dh).t(), rb(flat.float()), n_chain=pw["per_tiles"] * pw["kt"] + pw["split"] + 2,
                 out_dt=torch.float32)
-    # dX = dh @ wf1p, stored in the compute dtype (functional.py:99, train.py:357)
+    # dX = dh @ wf1p, stored in the compute dtype (functional.py:99, train.py:464)
     px = gemm_path(m, k, n, comp)
     _mirror_is_the_library(px, ops.gemm_plan(dhd, wd, compute=comp, out_dtype=comp), f"dX {tag}")
     dxf = ops.gemm(dhd, wd, compute=comp, out_dtype=comp)
