@@ -200,19 +200,46 @@ def sample_matrices(gen, n_samples=None, *, noise=None, compute_dtype="bf16", de
     return out.contiguous()
 
 
+def _song_batches(spec, batch_size, shuffle):
+    """One epoch over the (N, H, W) windows of a song as ``DataLoader(batch_size, shuffle)`` deals them: the last,
+    partial batch is kept."""
+    n = len(spec)
+    if not shuffle:
+        return (spec[a:a + batch_size] for a in range(0, n, batch_size))
+    order = torch.randperm(n).to(spec.device)
+    return (spec[order[a:a + batch_size]] for a in range(0, n, batch_size))
+
+
 def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5, 0.999), display_step=5, save_step=5,
-          z_dim=100, model_path="models/", input_hw=(128, 216), fake_provider=None, device=None, seed=None,
-          compute_dtype=None, elide_dead_backward=False, max_steps=None, save=True, log=print):
+          z_dim=100, model_path="models/", input_hw=None, fake_provider=None, device=None, seed=None,
+          compute_dtype=None, elide_dead_backward=False, max_steps=None, save=True, log=print, audio_file=None,
+          window_size=5, hop_length_audio=5, shuffle=True):
     """The reference's ``__main__`` training loop (SIMNN.py:234-348) on the fused MI355X step.
 
     dataloader: iterable of real batches (B,H,W) fp32 (the reference's MaestroDataset/DataLoader); if None, seeded
         synthetic spectrogram windows are used (``max_steps`` batches, default 10).
+    audio_file: a WAV file to train on instead (``datasets.InputSong(audio_file, window_size, hop_length_audio)``, the
+        reference's single-song configuration): every epoch deals the song's windows in batches of ``batch_size``,
+        shuffled unless ``shuffle=False``.  ``input_hw`` then defaults to the (128, frames) of the song's windows
+        (otherwise to the reference's (128, 216)).
     fake_provider(generated_numpy (B,20,20)) -> (B,H,W) tensor: stands in for the DES/FluidSynth bridge
         ``matrix_to_wav`` (SIMNN.py:301); if None, seeded synthetic windows are used.
     Returns (gen, disc, gen_losses, disc_losses).
     """
     from .train import SimnnTrainer
     device = torch.device(device if device is not None else "cuda")
+    song = None
+    if audio_file is not None:
+        if dataloader is not None:
+            raise ValueError("train() takes audio_file or dataloader, not both")
+        from .datasets import InputSong
+        song = InputSong(audio_file, window_size, hop_length_audio, device=device).spectrograms()
+        song_hw = tuple(song.shape[1:])
+        if input_hw is not None and tuple(input_hw) != song_hw:
+            raise ValueError(f"input_hw = {tuple(input_hw)} but the windows of {audio_file} are {song_hw}")
+        input_hw = song_hw
+    elif input_hw is None:
+        input_hw = (128, 216)
     if seed is not None:
         torch.manual_seed(seed)
     gen = Generator().to(device)
@@ -224,7 +251,9 @@ def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5,
     gen_losses, disc_losses = [], []
     cur_step = 0
     for epoch in range(n_epochs):
-        if dataloader is None:
+        if song is not None:
+            batches = _song_batches(song, batch_size, shuffle)
+        elif dataloader is None:
             n = max_steps if max_steps is not None else 10
             batches = (synthetic.spectrogram_batch(batch_size, input_hw, seed=1234 + i) for i in range(n))
         else:
@@ -254,4 +283,13 @@ def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5,
 
 
 if __name__ == "__main__":
-    train()
+    import argparse
+    ap = argparse.ArgumentParser(description="Train model 1 (the reference's SIMNN.py __main__ loop).")
+    ap.add_argument("--audio-file", default=None, help="WAV file to train on (default: seeded synthetic windows)")
+    ap.add_argument("--epochs", type=int, default=1)
+    ap.add_argument("--batch-size", type=int, default=30)
+    ap.add_argument("--max-steps", type=int, default=None)
+    ap.add_argument("--no-save", action="store_true", help="write no generator checkpoints")
+    a = ap.parse_args()
+    train(audio_file=a.audio_file, n_epochs=a.epochs, batch_size=a.batch_size, max_steps=a.max_steps,
+          save=not a.no_save)

@@ -13,6 +13,9 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
 # model 2's criterion names -> GDM_CRIT_* (include/gdm.h; network_tests.py:248-250 of the reference)
 CRITERIA = {"bce": 0, "mse": 1, "l1": 2}
+# GDM_PCM_* sample formats (include/gdm.h) and their bytes per sample
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32 = range(5)
+PCM_BYTES = (1, 2, 3, 4, 4)
 
 _c = ctypes
 _P, _I, _L, _F, _Z = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_size_t
@@ -50,6 +53,8 @@ SIGNATURES = {
     "gdm_stft_frames": (_I, [_P, _I, _L, _L, _I, _I, _I, _P, _P]),
     "gdm_power_spectrum": (_I, [_P, _L, _I, _I, _P, _P]),
     "gdm_power_to_db": (_I, [_P, _I, _I, _I, _F, _F, _P, _P]),
+    "gdm_pcm_to_float": (_I, [_P, _I, _I, _I, _L, _L, _L, _P, _P]),
+    "gdm_pcm_stft_frames": (_I, [_P, _I, _I, _I, _L, _L, _L, _I, _L, _L, _I, _I, _I, _P, _P]),
     "gdm_bn_workspace_bytes": (_Z, [_I, _I]),
     "gdm_bn_act_fwd": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _F, _F, _I, _P, _I, _P, _P, _I, _P, _Z, _P]),
     "gdm_bn_act_bwd": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),

@@ -74,6 +74,87 @@ __global__ __launch_bounds__(1024) void power_to_db_kernel(const float* __restri
   }
 }
 
+// ---- PCM front end (GAN_DES/datasets.py:26-43, util.py:89-119: torchaudio.load(normalize=True) + the window loops) ----
+// The file's interleaved little-endian sample bytes are decoded where they are read.  One fp32 per stored sample first,
+// then the mono rule: channel c, or channels added left to right in fp32 and divided once (waveform.mean(dim=0)).
+template <int FMT>
+__device__ __forceinline__ float pcm_decode(const uint8_t* __restrict__ p, int64_t e) {
+#pragma clang fp contract(off)
+  if constexpr (FMT == GDM_PCM_U8) {
+    return (float)((int)p[e] - 128) * 0x1p-7f;
+  } else if constexpr (FMT == GDM_PCM_S16) {
+    return (float)((const int16_t*)p)[e] * 0x1p-15f;
+  } else if constexpr (FMT == GDM_PCM_S24) {
+    const uint8_t* q = p + 3 * e;                              // no alignment to rely on: three byte loads
+    const int32_t v = (int32_t)((uint32_t)q[0] << 8 | (uint32_t)q[1] << 16 | (uint32_t)q[2] << 24) >> 8;
+    return (float)v * 0x1p-23f;
+  } else if constexpr (FMT == GDM_PCM_S32) {
+    return (float)((const int32_t*)p)[e] * 0x1p-31f;           // int -> float rounds to nearest even; the scale is exact
+  } else {
+    return ((const float*)p)[e];
+  }
+}
+
+// MEAN: waveform.mean(dim=0); otherwise channel `mix` (InputSong's channel = 0)
+template <int FMT, bool MEAN>
+__device__ __forceinline__ float pcm_mono(const uint8_t* __restrict__ p, int channels, int mix, int64_t s) {
+#pragma clang fp contract(off)
+  const int64_t e = s * channels;
+  if constexpr (!MEAN) {
+    return pcm_decode<FMT>(p, e + mix);
+  } else {
+    float acc = pcm_decode<FMT>(p, e);
+    for (int c = 1; c < channels; ++c) acc = acc + pcm_decode<FMT>(p, e + c);
+    return acc / (float)channels;
+  }
+}
+
+// out[t] = mono(first + t); four consecutive t per lane, one 16-byte store where all four exist and out allows it
+template <int FMT, bool MEAN>
+__global__ __launch_bounds__(256) void pcm_to_float_kernel(const uint8_t* __restrict__ pcm, int channels, int mix,
+                                                           int64_t first, int64_t count, float* __restrict__ out) {
+  const int64_t total4 = (count + 3) / 4;
+  const bool wide = ((uintptr_t)out & 15) == 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+    const int64_t t = i * 4;
+    if (wide && t + 4 <= count) {
+      f32x4 v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = pcm_mono<FMT, MEAN>(pcm, channels, mix, first + t + e);
+      *(f32x4*)(out + t) = v;
+    } else {
+      for (int64_t u = t; u < count && u < t + 4; ++u) out[u] = pcm_mono<FMT, MEAN>(pcm, channels, mix, first + u);
+    }
+  }
+}
+
+// stft_frames_kernel reading the song itself: window w starts at start0 + w * stride (w < n_regular) or at tail_start,
+// and the reflection stays inside the window's win_len samples.
+template <int FMT, bool MEAN>
+__global__ __launch_bounds__(256) void pcm_stft_frames_kernel(const uint8_t* __restrict__ pcm, int channels, int mix,
+                                                              int64_t start0, int64_t stride, int n_regular,
+                                                              int64_t tail_start, int64_t L, int hop, int n_fft,
+                                                              int frames, int64_t total4, float* __restrict__ out) {
+  const int per_row = n_fft / 4;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+    const int n = (int)(i % per_row) * 4;
+    const int64_t row = i / per_row;
+    const int f = (int)(row % frames);
+    const int64_t w = row / frames;
+    const int64_t start = w < n_regular ? start0 + w * stride : tail_start;
+    const int64_t s0 = (int64_t)f * hop + n - n_fft / 2;
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      int64_t s = s0 + e;
+      s = s < 0 ? -s : s;
+      s = s >= L ? 2 * (L - 1) - s : s;
+      v[e] = pcm_mono<FMT, MEAN>(pcm, channels, mix, start + s);
+    }
+    *(f32x4*)(out + row * n_fft + n) = v;
+  }
+}
+
 inline unsigned blocks_for(int64_t total) {
   int64_t b = (total + 255) / 256;
   return (unsigned)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
@@ -114,5 +195,87 @@ extern "C" int gdm_power_to_db(const float* mel, int B, int frames, int n_mels, 
   hipLaunchKernelGGL(power_to_db_kernel, dim3(B), dim3(1024), sm, (hipStream_t)stream, mel, frames, n_mels, top_db, amin,
                      out);
   GDM_LAUNCH_OK("gdm_power_to_db");
+  return GDM_OK;
+}
+
+// format x mono rule -> kernel instance; LAUNCH(kernel template) expands to the 10-way switch once per entry point
+#define GDM_PCM_DISPATCH(LAUNCH)                                                      \
+  switch (fmt * 2 + (mix < 0)) {                                                      \
+    case GDM_PCM_U8 * 2: LAUNCH(GDM_PCM_U8, false); break;                            \
+    case GDM_PCM_U8 * 2 + 1: LAUNCH(GDM_PCM_U8, true); break;                         \
+    case GDM_PCM_S16 * 2: LAUNCH(GDM_PCM_S16, false); break;                          \
+    case GDM_PCM_S16 * 2 + 1: LAUNCH(GDM_PCM_S16, true); break;                       \
+    case GDM_PCM_S24 * 2: LAUNCH(GDM_PCM_S24, false); break;                          \
+    case GDM_PCM_S24 * 2 + 1: LAUNCH(GDM_PCM_S24, true); break;                       \
+    case GDM_PCM_S32 * 2: LAUNCH(GDM_PCM_S32, false); break;                          \
+    case GDM_PCM_S32 * 2 + 1: LAUNCH(GDM_PCM_S32, true); break;                       \
+    case GDM_PCM_F32 * 2: LAUNCH(GDM_PCM_F32, false); break;                          \
+    default: LAUNCH(GDM_PCM_F32, true); break;                                        \
+  }
+
+// what both PCM entry points ask of the buffer description (n_samples is bounded so that no byte index overflows)
+static int pcm_check(const char* who, const void* pcm, int fmt, int channels, int mix, int64_t n_samples) {
+  GDM_REQUIRE(pcm, "%s: null pointer", who);
+  GDM_REQUIRE(fmt >= GDM_PCM_U8 && fmt <= GDM_PCM_F32, "%s: unknown sample format %d", who, fmt);
+  GDM_REQUIRE(channels >= 1 && channels <= 8, "%s: %d channels (1 to 8 are supported)", who, channels);
+  GDM_REQUIRE(mix >= -1 && mix < channels, "%s: mix = %d is neither -1 (mean) nor one of %d channels", who, mix, channels);
+  GDM_REQUIRE(n_samples > 0 && n_samples <= ((int64_t)1 << 40), "%s: bad sample count %lld", who, (long long)n_samples);
+  const int align = fmt == GDM_PCM_S16 ? 2 : (fmt == GDM_PCM_S32 || fmt == GDM_PCM_F32) ? 4 : 1;
+  GDM_REQUIRE(((uintptr_t)pcm & (align - 1)) == 0, "%s: the sample buffer must be aligned to its %d-byte elements", who, align);
+  return GDM_OK;
+}
+
+extern "C" int gdm_pcm_to_float(const void* pcm, int fmt, int channels, int mix, int64_t n_samples, int64_t first,
+                                int64_t count, float* out, void* stream) {
+  if (int rc = pcm_check("gdm_pcm_to_float", pcm, fmt, channels, mix, n_samples)) return rc;
+  GDM_REQUIRE(out, "gdm_pcm_to_float: null pointer");
+  GDM_REQUIRE(first >= 0 && count > 0 && first <= n_samples && count <= n_samples - first,
+              "gdm_pcm_to_float: samples %lld .. +%lld are not within the %lld of the buffer", (long long)first,
+              (long long)count, (long long)n_samples);
+  const uint8_t* p = (const uint8_t*)pcm;
+#define GDM_PCM_LAUNCH(F, M)                                                                                          \
+  hipLaunchKernelGGL((pcm_to_float_kernel<F, M>), dim3(blocks_for((count + 3) / 4)), dim3(256), 0, (hipStream_t)stream, \
+                     p, channels, mix, first, count, out)
+  GDM_PCM_DISPATCH(GDM_PCM_LAUNCH)
+#undef GDM_PCM_LAUNCH
+  GDM_LAUNCH_OK("gdm_pcm_to_float");
+  return GDM_OK;
+}
+
+extern "C" int gdm_pcm_stft_frames(const void* pcm, int fmt, int channels, int mix, int64_t n_samples, int64_t start0,
+                                   int64_t stride, int n_regular, int64_t tail_start, int64_t win_len, int hop, int n_fft,
+                                   int frames, float* out, void* stream) {
+  if (int rc = pcm_check("gdm_pcm_stft_frames", pcm, fmt, channels, mix, n_samples)) return rc;
+  GDM_REQUIRE(out, "gdm_pcm_stft_frames: null pointer");
+  GDM_REQUIRE(hop > 0 && n_fft >= 4 && n_fft % 4 == 0 && frames > 0, "gdm_pcm_stft_frames: bad arguments");
+  GDM_REQUIRE(win_len > n_fft / 2, "gdm_pcm_stft_frames: reflect padding needs more than n_fft/2 = %d samples, got %lld",
+              n_fft / 2, (long long)win_len);
+  GDM_REQUIRE((int64_t)(frames - 1) * hop <= win_len, "gdm_pcm_stft_frames: %d frames of hop %d exceed %lld samples",
+              frames, hop, (long long)win_len);
+  GDM_REQUIRE(win_len <= n_samples, "gdm_pcm_stft_frames: a window of %lld samples in a song of %lld", (long long)win_len,
+              (long long)n_samples);
+  const int64_t last_ok = n_samples - win_len;                  // the largest start a window may have
+  const bool tail = tail_start >= 0;
+  GDM_REQUIRE(n_regular >= 0 && (n_regular > 0 || tail), "gdm_pcm_stft_frames: no window");
+  if (n_regular > 0) {
+    GDM_REQUIRE(start0 >= 0 && start0 <= last_ok, "gdm_pcm_stft_frames: window 0 starts at %lld, outside 0 .. %lld",
+                (long long)start0, (long long)last_ok);
+    // |stride| <= n_samples <= 2^40 and n_regular < 2^31: the product below cannot overflow
+    GDM_REQUIRE(stride >= -n_samples && stride <= n_samples, "gdm_pcm_stft_frames: stride %lld", (long long)stride);
+    const int64_t end = start0 + (int64_t)(n_regular - 1) * stride;          // starts are linear in w: two ends suffice
+    GDM_REQUIRE(end >= 0 && end <= last_ok, "gdm_pcm_stft_frames: window %d starts at %lld, outside 0 .. %lld",
+                n_regular - 1, (long long)end, (long long)last_ok);
+  }
+  GDM_REQUIRE(!tail || tail_start <= last_ok, "gdm_pcm_stft_frames: the tail window starts at %lld, outside 0 .. %lld",
+              (long long)tail_start, (long long)last_ok);
+  GDM_REQUIRE(((uintptr_t)out & 15) == 0, "gdm_pcm_stft_frames: output must be 16-byte aligned");
+  const int64_t total4 = ((int64_t)n_regular + (tail ? 1 : 0)) * frames * (n_fft / 4);
+  const uint8_t* p = (const uint8_t*)pcm;
+#define GDM_PCM_LAUNCH(F, M)                                                                                         \
+  hipLaunchKernelGGL((pcm_stft_frames_kernel<F, M>), dim3(blocks_for(total4)), dim3(256), 0, (hipStream_t)stream, p, \
+                     channels, mix, start0, stride, n_regular, tail_start, win_len, hop, n_fft, frames, total4, out)
+  GDM_PCM_DISPATCH(GDM_PCM_LAUNCH)
+#undef GDM_PCM_LAUNCH
+  GDM_LAUNCH_OK("gdm_pcm_stft_frames");
   return GDM_OK;
 }

@@ -1,5 +1,8 @@
-"""Drop-in surface of the piano-roll data path (MMGAN_MIDI_DES/datasets.py) on MI355X.
+"""Drop-in surface of the two data paths on MI355X: model 2's piano rolls (MMGAN_MIDI_DES/datasets.py, SURVEY.md
+section 8f row 3) and model 1's single-song dataset (GAN_DES/datasets.py:17-52, "the single-song dataset of BASELINE
+config 1").
 
+    InputSong(audio_file, window_size=5, hop_length_audio=5, device='cuda')                     GAN_DES/datasets.py:17-52
     generate_piano_roll(midi_input, sequence_length=100, beats_length=50, start=0, end=50)      datasets.py:13-70
     MaestroDatasetMidi(root_dir, sequence_length=100, beats_length=50, device='cpu')            datasets.py:103-123
 
@@ -18,6 +21,10 @@ of what is and is not pinned: PARITY UNPINNED).  The reference's control flow is
 index is absolute although the planes are only ``end - start`` wide (a note_on beyond the width ends the event loop:
 IndexError inside the reference's bare ``try``), messages at ``sequence_length`` seconds or later end it as well, and
 the final slice is ``[:, start:end]`` of the already ``end - start`` wide planes (empty for start >= end - start).
+
+``InputSong`` reads a WAV file (``util.load_wav``, host), uploads its sample bytes once and computes the mel-dB windows
+of the whole song on the device straight from them (``util.melspectrogram_db_from_pcm``): the decoded, overlapping
+float windows the reference keeps in ``self.audio_files`` are never built.  MaestroDataset (FluidSynth) stays outside.
 """
 import glob
 import os
@@ -26,7 +33,7 @@ import struct
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, util
 
 DEFAULT_TEMPO = 500000
 _K_OTHER, _K_ON, _K_OFF, _K_TEMPO, _K_TSIG, _K_EOT = 0, 1, 2, 3, 4, 5
@@ -301,3 +308,59 @@ class MaestroDatasetMidi(torch.utils.data.Dataset):
         roll, dur, beats = generate_piano_rolls([self.file_list[idx]], self.sequence_length, self.beats_length,
                                                 device=self.device)
         return roll[0], dur[0], beats[0]
+
+
+class InputSong(torch.utils.data.Dataset):
+    """One song cut into excerpts (GAN_DES/datasets.py:17-52): item i = the (128, frames) mel-dB tensor of window i, on
+    ``device``.  As upstream, windows are ``hop_length_audio`` seconds long and apart (``window_size`` is stored and
+    otherwise unused), the last one is taken from the end of the song, channel 0 is used and the file's sample rate
+    goes to the filter bank (``util.song_windows`` lists the consequences).
+
+    All windows are computed on first use, ``windows_per_chunk`` at a time so that the frame matrix of a long song stays
+    bounded (64 windows of 216 frames x 2048 samples are 113 MB), and kept; items are views of that tensor."""
+
+    def __init__(self, audio_file, window_size=5, hop_length_audio=5, *, device="cuda", windows_per_chunk=64):
+        self._wav = util.load_wav(audio_file)
+        self.sample_rate = self._wav.sample_rate
+        self.audio_file_length = self._wav.n_frames / self.sample_rate
+        self.window_size = window_size
+        self.hop_length_audio = hop_length_audio
+        self.device = torch.device(device)
+        self.windows_per_chunk = max(1, int(windows_per_chunk))
+        self.windows = util.song_windows(self._wav.n_frames, self.sample_rate, hop_length_audio, window_size,
+                                         mode="input_song")
+        self._pcm = util.upload_pcm(self._wav, self.device)
+        self._spec = self._orig = None
+
+    @property
+    def orig_waveform(self):
+        """(channels, n) fp32 on the device, what torchaudio.load(normalize=True) returns; decoded on first use."""
+        if self._orig is None:
+            w = self._wav
+            self._orig = torch.empty((w.channels, w.n_frames), dtype=torch.float32, device=self.device)
+            for c in range(w.channels):
+                ops.pcm_to_float(self._pcm, w.fmt, w.channels, c, w.n_frames, out=self._orig[c])
+        return self._orig
+
+    def spectrograms(self):
+        """(len(self), 128, frames) fp32 on the device: every window's mel-dB tensor (computed once)."""
+        if self._spec is None:
+            length = self.windows[0][1]                                # one length for all windows of a song
+            hop, win_len = util.mel_geometry(length)
+            starts = [s for s, _ in self.windows]
+            k = self.windows_per_chunk
+            parts = [util.melspectrogram_db_from_pcm(self._pcm, self._wav, 0, starts[a:a + k], win_len,
+                                                     sr=self.sample_rate, hop=hop)
+                     for a in range(0, len(starts), k)]
+            self._spec = parts[0] if len(parts) == 1 else torch.cat(parts)
+        return self._spec
+
+    def __len__(self):
+        return len(self.windows)
+
+    def __getitem__(self, item):
+        n = len(self.windows)
+        i = int(item)
+        if not -n <= i < n:
+            raise IndexError(f"window {item} of a song with {n}")
+        return self.spectrograms()[i]

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, BF16, CRITERIA, F32, GdmError, check  # noqa: F401
+from ._lib import PCM_BYTES, PCM_F32, PCM_S16, PCM_S24, PCM_S32, PCM_U8  # noqa: F401
 
 _TORCH_DT = {F32: torch.float32, BF16: torch.bfloat16}
 
@@ -1025,3 +1026,52 @@ def power_to_db(mel, b, frames, top_db=80.0, amin=1e-10):
     _call("gdm_power_to_db", _p(mel), int(b), int(frames), int(n_mels), float(-1.0 if top_db is None else top_db),
           float(amin), _p(out), _stream())
     return out
+
+
+# ---- PCM front end (GAN_DES/datasets.py:26-43, util.py:89-119) --------------------------------------------------------
+def _pcm_args(pcm, fmt, channels, n_samples, what):
+    """The sample buffer is a flat uint8 device tensor; its size is what the C entry cannot check."""
+    _need_gpu(pcm)
+    if pcm.dtype != torch.uint8 or pcm.dim() != 1 or not pcm.is_contiguous():
+        raise GdmError(f"{what}: pcm must be a contiguous 1-D uint8 tensor (the WAV data chunk)")
+    fmt, channels, n_samples = int(fmt), int(channels), int(n_samples)
+    if 0 <= fmt < len(PCM_BYTES) and channels > 0 and n_samples * channels * PCM_BYTES[fmt] > pcm.numel():
+        raise GdmError(f"{what}: {n_samples} frames of {channels} x {PCM_BYTES[fmt]} bytes exceed the buffer's "
+                       f"{pcm.numel()} bytes")
+    return fmt, channels, n_samples
+
+
+def pcm_to_float(pcm, fmt, channels, mix, n_samples, first=0, count=None, out=None):
+    """pcm (bytes of n_samples interleaved frames) -> (count,) fp32: channel ``mix``, or the channel mean for mix = -1,
+    of samples first .. first + count (default: to the end).  ``out``: a contiguous (count,) fp32 tensor to fill."""
+    fmt, channels, n_samples = _pcm_args(pcm, fmt, channels, n_samples, "pcm_to_float")
+    first = int(first)
+    count = n_samples - first if count is None else int(count)
+    if out is None:
+        out = torch.empty(max(count, 0), dtype=torch.float32, device=pcm.device)
+    else:
+        _need_gpu(out)
+        assert out.dtype == torch.float32 and out.shape == (count,) and out.is_contiguous()
+    _call("gdm_pcm_to_float", _p(pcm), fmt, channels, int(mix), n_samples, first, count, _p(out), _stream())
+    return out
+
+
+def pcm_stft_frames(pcm, fmt, channels, mix, n_samples, start0, stride, n_regular, tail_start, win_len, hop, n_fft,
+                    out=None):
+    """stft_frames over windows of the song in ``pcm`` without materialising them: n_regular windows at
+    start0 + w * stride, one more at tail_start if that is >= 0, each win_len samples long ->
+    ((windows * frames, n_fft) frames, frames) with frames = 1 + win_len // hop."""
+    fmt, channels, n_samples = _pcm_args(pcm, fmt, channels, n_samples, "pcm_stft_frames")
+    n_regular, tail_start, win_len, hop, n_fft = int(n_regular), int(tail_start), int(win_len), int(hop), int(n_fft)
+    if hop <= 0 or n_fft <= 0 or n_regular < 0:
+        raise GdmError("pcm_stft_frames: hop and n_fft must be positive, n_regular not negative")
+    frames = 1 + max(win_len, 0) // hop
+    rows = (n_regular + (tail_start >= 0)) * frames
+    if out is None:
+        out = torch.empty((rows, n_fft), dtype=torch.float32, device=pcm.device)
+    else:
+        _need_gpu(out)
+        assert out.dtype == torch.float32 and out.shape == (rows, n_fft) and out.is_contiguous()
+    _call("gdm_pcm_stft_frames", _p(pcm), fmt, channels, int(mix), n_samples, int(start0), int(stride), n_regular,
+          tail_start, win_len, hop, n_fft, frames, _p(out), _stream())
+    return out, frames

@@ -477,6 +477,39 @@ int gdm_stft_frames(const float* x, int B, int64_t L, int64_t x_stride, int hop,
 int gdm_power_spectrum(const float* c, int64_t rows, int nfreq, int ldp, float* p, void* stream);
 int gdm_power_to_db(const float* mel, int B, int frames, int n_mels, float top_db, float amin, float* out, void* stream);
 
+/* ---- PCM front end of the featuriser (GAN_DES/datasets.py:26-43, GAN_DES/util.py:89-119) ---------------------------
+ * What torchaudio.load(normalize=True), the channel rule and the window loops of InputSong / split_audio_data /
+ * get_melspectrogram_db_tensor_from_file produce, read straight from a WAV file's sample bytes on the device: `pcm` is
+ * the data chunk (little-endian, interleaved, n_samples sample frames of `channels` = 1..8 samples, aligned to the
+ * element size: 1 byte for U8 and S24, 2 for S16, 4 for S32 and F32).  Each stored sample becomes one fp32 first:
+ *   U8  (v - 128) * 2^-7        S16  v * 2^-15        S24 (3 bytes)  v * 2^-23
+ *   S32 (float)v, rounded to nearest even, then * 2^-31              F32  the float as stored
+ * These are the values torchaudio documents for normalize=True.  PINNED: S16 only (every step is exact in fp32, and the
+ * three 16-bit files the reference ships are fixtures); the other formats follow the formula above and nothing else,
+ * because torchaudio is not available to compare with.
+ * mix = c >= 0: channel c (InputSong's `channel = 0`).  mix = -1: waveform.mean(dim=0) = the decoded channels added left
+ * to right in fp32, then one correctly rounded division by `channels` (S32 therefore rounds per sample and per sum;
+ * S16 and S24 means are exact).  No multiply-add is contracted.
+ * gdm_pcm_to_float: out[t] = mono(first + t), t < count; requires 0 <= first, count > 0, first + count <= n_samples.
+ * gdm_pcm_stft_frames: gdm_stft_frames over windows of the song that are never materialised.  Window w < n_regular
+ *   starts at start0 + w * stride; if tail_start >= 0 one more window starts there (InputSong's last window, taken from
+ *   the end).  All windows are win_len samples long.
+ *   out[((w * frames + f) * n_fft) + j] = mono(start_w + reflect(f * hop + j - n_fft / 2, win_len)), the reflection
+ *   (s < 0 -> -s, s >= win_len -> 2 (win_len - 1) - s) staying inside the window: no neighbour's sample is read.
+ *   Checked before the launch: every start >= 0 and start + win_len <= n_samples, win_len > n_fft / 2,
+ *   (frames - 1) * hop <= win_len, n_fft % 4 == 0, out 16-byte aligned.  A bad table is GDM_EINVAL, never a read
+ *   outside the buffer (whose size, n_samples * channels * bytes per sample, is the caller's statement).            */
+#define GDM_PCM_U8 0
+#define GDM_PCM_S16 1
+#define GDM_PCM_S24 2
+#define GDM_PCM_S32 3
+#define GDM_PCM_F32 4
+int gdm_pcm_to_float(const void* pcm, int fmt, int channels, int mix, int64_t n_samples, int64_t first, int64_t count,
+                     float* out, void* stream);
+int gdm_pcm_stft_frames(const void* pcm, int fmt, int channels, int mix, int64_t n_samples, int64_t start0,
+                        int64_t stride, int n_regular, int64_t tail_start, int64_t win_len, int hop, int n_fft,
+                        int frames, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
