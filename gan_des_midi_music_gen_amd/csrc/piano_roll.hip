@@ -10,6 +10,7 @@
 // (CSR over file * 128 + note).  One workgroup per file clears the file's two (128, W) planes with coalesced stores,
 // then thread `note` replays its row.  Integer work on a few KB per file: bound by launch latency and the planes' bytes.
 #include "gdm_common.h"
+#include "buffer_ops.h"
 
 namespace {
 
@@ -38,7 +39,73 @@ __global__ __launch_bounds__(128) void piano_roll_kernel(const int32_t* __restri
   }
 }
 
+// The windowed form (data_viewing_and_processing.ipynb cell 11 cuts cell 10's (128, sample_size) planes into windows of
+// L steps): one workgroup per OUTPUT window.  Both planes of the window are built in LDS -- cleared, then thread `note`
+// replays its row from the start of the file and keeps only what falls into columns [s0, s0 + L): note_on_time
+// carries over from earlier windows and a duration keeps its full-length value in every window it crosses -- and
+// leave with 16-byte stores, lane after lane (the per-file kernel above writes L floats apart between lanes).  Every
+// output plane is written by exactly one workgroup: no atomics and no memset launch.
+constexpr int kWinThreads = 256;
+constexpr int kWinMaxL = 160 * 1024 / (2 * 128 * 4);           // both planes of a window in one workgroup's LDS
+
+__global__ __launch_bounds__(kWinThreads) void piano_roll_windows_kernel(
+    const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ ev_step, const int32_t* __restrict__ ev_vel,
+    const int32_t* __restrict__ win_file, const int32_t* __restrict__ win_s0, int L, float* __restrict__ roll,
+    float* __restrict__ dur) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
+  float* r_s = (float*)dyn_smem;                              // [128][L]
+  float* d_s = r_s + 128 * L;                                 // [128][L]; 512 L bytes on: 16-byte aligned
+  const int n = blockIdx.x, f = win_file[n], s0 = win_s0[n], s1 = s0 + L;
+  const int n4 = 2 * 128 * L / 4;                             // float4s of both planes
+  f32x4* lds4 = (f32x4*)dyn_smem;
+  for (int i = threadIdx.x; i < n4; i += kWinThreads) lds4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    const int note = threadIdx.x;
+    float* r = r_s + note * L;                                // column = step - s0, inside [0, L) only
+    float* d = d_s + note * L;
+    int on_time = 0;                                          // note_on_time = np.zeros(128)
+    const int e0 = row_ptr[f * 128 + note], e1 = row_ptr[f * 128 + note + 1];
+    for (int e = e0; e < e1; ++e) {
+      const int step = ev_step[e], vel = ev_vel[e];
+      if (vel >= 0) {
+        if (step >= s0 && step < s1) r[step - s0] = (float)vel;
+        on_time = step;
+      } else {
+        const float len = (float)(step - on_time);
+        const int a = on_time > s0 ? on_time : s0, b = step < s1 ? step : s1;
+        for (int s = a; s < b; ++s) d[s - s0] = len;
+      }
+    }
+  }
+  __syncthreads();
+  f32x4* ro = (f32x4*)(roll + (int64_t)n * 128 * L);
+  f32x4* dn = (f32x4*)(dur + (int64_t)n * 128 * L);
+  const int h4 = n4 / 2;
+  for (int i = threadIdx.x; i < h4; i += kWinThreads) {
+    ro[i] = lds4[i];
+    dn[i] = lds4[h4 + i];
+  }
+}
+
 }  // namespace
+
+extern "C" int gdm_piano_roll_windows(const int32_t* row_ptr, const int32_t* ev_step, const int32_t* ev_vel,
+                                      const int32_t* win_file, const int32_t* win_s0, int n_windows, int L, float* roll,
+                                      float* dur, void* stream) {
+  GDM_REQUIRE(row_ptr && win_file && win_s0 && roll && dur && n_windows > 0 && L > 0,
+              "gdm_piano_roll_windows: bad arguments");
+  const size_t lds = (size_t)2 * 128 * 4 * L;
+  GDM_REQUIRE(L <= kWinMaxL, "gdm_piano_roll_windows: L = %d needs %zu bytes of LDS, a workgroup has %d (L <= %d)", L,
+              lds, 160 * 1024, kWinMaxL);
+  GDM_REQUIRE(((uintptr_t)roll | (uintptr_t)dur) % 16 == 0,
+              "gdm_piano_roll_windows: roll and dur must be 16-byte aligned");
+  allow_lds(piano_roll_windows_kernel, 160 * 1024);
+  hipLaunchKernelGGL(piano_roll_windows_kernel, dim3(n_windows), dim3(kWinThreads), lds, (hipStream_t)stream, row_ptr,
+                     ev_step, ev_vel, win_file, win_s0, L, roll, dur);
+  GDM_LAUNCH_OK("gdm_piano_roll_windows");
+  return GDM_OK;
+}
 
 extern "C" int gdm_piano_roll_raster(const int32_t* row_ptr, const int32_t* ev_step, const int32_t* ev_vel, int n_files,
                                      int W, float* roll, float* dur, void* stream) {

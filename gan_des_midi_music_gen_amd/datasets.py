@@ -5,6 +5,9 @@ config 1").
     InputSong(audio_file, window_size=5, hop_length_audio=5, device='cuda')                     GAN_DES/datasets.py:17-52
     generate_piano_roll(midi_input, sequence_length=100, beats_length=50, start=0, end=50)      datasets.py:13-70
     MaestroDatasetMidi(root_dir, sequence_length=100, beats_length=50, device='cpu')            datasets.py:103-123
+    MaestroDatasetPickle(pickle_file_name, sequence_length=100, beats_length=50, device='cpu')  datasets.py:73-87
+    MaestroDatasetTorch(root_dir, sequence_length=100, beats_length=50, device='cpu')           datasets.py:90-100
+    MaestroWindows.from_midi(root_dir_or_list, sample_size=300, sequence_length=50, ...)        notebook cells 10-11
 
 ``generate_piano_roll`` keeps the reference's signature and return value (numpy ``piano_roll (128, W)``, ``durations
 (128, W)``, ``beats (beats_length,)``); ``generate_piano_rolls`` is the batched form the training data path wants: a list
@@ -22,12 +25,21 @@ index is absolute although the planes are only ``end - start`` wide (a note_on b
 IndexError inside the reference's bare ``try``), messages at ``sequence_length`` seconds or later end it as well, and
 the final slice is ``[:, start:end]`` of the already ``end - start`` wide planes (empty for start >= end - start).
 
+``MaestroWindows`` is the dataset model 2 trains on, built the way data_viewing_and_processing.ipynb cell 11 builds
+``preprocessed_data_50.pkl``: every file's (128, sample_size) planes of cell 10 cut into windows of ``sequence_length``
+steps, window 0 dropped.  The host plans (``window_plan``: which windows a file yields, from the rounded running time
+of the last message cell 10's loop looks at), the device rasterises all windows of all files in one launch
+(``ops.piano_roll_windows``) and the result stays there; ``batches`` hands out views of it.  ``to_pickle`` writes the
+reference's file, ``MaestroDatasetPickle`` reads one, ``MaestroDatasetTorch`` / ``write_torch_files`` are the per-file
+``.pt`` route of notebook cell 9.
+
 ``InputSong`` reads a WAV file (``util.load_wav``, host), uploads its sample bytes once and computes the mel-dB windows
 of the whole song on the device straight from them (``util.melspectrogram_db_from_pcm``): the decoded, overlapping
 float windows the reference keeps in ``self.audio_files`` are never built.  MaestroDataset (FluidSynth) stays outside.
 """
 import glob
 import os
+import pickle
 import struct
 
 import numpy as np
@@ -164,7 +176,11 @@ def message_seconds(md):
 
 def _row_events(md, sequence_length, width):
     """Note messages the reference's loop processes, grouped by note: (row_ptr (129,), step, vel) as int32 arrays."""
-    secs, kind, a, b = message_seconds(md)
+    return _rows_of(message_seconds(md), sequence_length, width)
+
+
+def _rows_of(stream, sequence_length, width):
+    secs, kind, a, b = stream
     step = np.rint(np.cumsum(secs)).astype(np.int64)           # my_time += msg.time; int(round(my_time)) (half to even)
     stop = len(step)
     late = np.flatnonzero(step >= sequence_length)
@@ -181,6 +197,44 @@ def _row_events(md, sequence_length, width):
     np.cumsum(np.bincount(notes, minlength=128)[:128], out=row_ptr[1:])
     vel = np.where(kind[sel] == _K_ON, b[sel], -1).astype(np.int32)
     return row_ptr, step[sel].astype(np.int32), vel
+
+
+def total_time_step(md, sample_size, stream=None):
+    """``total_time`` of notebook cell 10's generate_piano_roll(midi, sample_size, ...): the rounded running time of the
+    last message its loop looks at -- the one that triggers ``break`` included, so the value can reach or exceed
+    ``sample_size`` -- over the stream mido yields, whose last message is ONE end_of_track carrying the deltas of all
+    removed end_of_track messages behind the last kept message (``message_seconds`` drops it; its time is added here to
+    the same float64 running sum, converted with the tempo then in force).  ``stream``: ``message_seconds(md)`` if the
+    caller has it already."""
+    secs, kind, a, _b = message_seconds(md) if stream is None else stream
+    carry, tempo = 0, DEFAULT_TEMPO
+    if len(md.tick):
+        kept = md.tick[md.kind != _K_EOT]
+        carry = int(md.tick.max()) - (int(kept.max()) if len(kept) else 0)
+    is_t = np.flatnonzero(kind == _K_TEMPO)
+    if len(is_t):
+        tempo = int(a[is_t[-1]])
+    last = carry * (tempo * 1e-6 / md.ticks_per_beat) if carry > 0 else 0.0     # mido.tick2second's association
+    step = np.rint(np.cumsum(np.append(secs, last))).astype(np.int64)           # int(round(my_time)): half to even
+    late = np.flatnonzero(step >= sample_size)
+    return int(step[late[0]] if len(late) else step[-1])
+
+
+def window_plan(midi_input, sample_size=300, sequence_length=50):
+    """What notebook cell 11 keeps of one file: (total_time, kept window indices (int64 array), row events).
+
+    ``nw = total_time // sequence_length`` windows are looked at; window i is kept iff ``1 <= i < nw`` (upstream's
+    ``i != 0``) and ``(i + 1) * sequence_length <= sample_size`` (upstream's shape check on a slice of the
+    ``sample_size`` wide plane): ``max(0, min(nw, sample_size // sequence_length) - 1)`` windows, contiguous from 1.
+    The row events are ``_row_events(md, sample_size, sample_size)``, the CSR the raster kernels take."""
+    if sequence_length <= 0 or sample_size <= 0:
+        raise ValueError(f"sample_size={sample_size} and sequence_length={sequence_length} must be positive")
+    md = midi_input if isinstance(midi_input, MidiData) else read_midi(midi_input)
+    stream = message_seconds(md)
+    total_time = total_time_step(md, sample_size, stream)
+    nw = total_time // sequence_length
+    kept = np.arange(1, max(1, min(nw, sample_size // sequence_length)), dtype=np.int64)
+    return total_time, kept, _rows_of(stream, sample_size, sample_size)
 
 
 def _qpm_to_bpm(qpm, num, den):
@@ -308,6 +362,188 @@ class MaestroDatasetMidi(torch.utils.data.Dataset):
         roll, dur, beats = generate_piano_rolls([self.file_list[idx]], self.sequence_length, self.beats_length,
                                                 device=self.device)
         return roll[0], dur[0], beats[0]
+
+
+class _Batches:
+    """One epoch per ``iter()``: (piano_roll, durations, beats) batches of a resident dataset."""
+
+    def __init__(self, tensors, batch_size, drop_last, shuffle, generator):
+        if batch_size <= 0:
+            raise ValueError(f"batch_size={batch_size} must be positive")
+        self.tensors, self.batch_size, self.drop_last = tensors, int(batch_size), drop_last
+        self.shuffle, self.generator = shuffle, generator
+
+    def __len__(self):
+        n = len(self.tensors[0])
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def __iter__(self):
+        b = self.batch_size
+        if not self.shuffle:
+            for k in range(len(self)):                              # slices of the resident tensors: views, no copy
+                yield tuple(t[k * b:(k + 1) * b] for t in self.tensors)
+            return
+        perm = torch.randperm(len(self.tensors[0]), generator=self.generator)      # host, as DataLoader's sampler
+        perm = perm.to(self.tensors[0].device)
+        for k in range(len(self)):
+            idx = perm[k * b:(k + 1) * b]
+            yield tuple(t.index_select(0, idx) for t in self.tensors)
+
+
+class _ResidentWindows(torch.utils.data.Dataset):
+    """piano_roll, durations (N,128,L) and beats (N,beats_length) fp32 stacked on one device; items are views."""
+
+    piano_roll = durations = beats = None
+
+    def __len__(self):
+        return self.piano_roll.shape[0]
+
+    def __getitem__(self, idx):
+        n = len(self)
+        i = int(idx)
+        if not -n <= i < n:
+            raise IndexError(f"item {idx} of a dataset with {n}")
+        return self.piano_roll[i], self.durations[i], self.beats[i]
+
+    def batches(self, batch_size, drop_last=True, shuffle=False, generator=None):
+        """Re-iterable over (piano_roll, durations, beats) batches, one epoch per ``iter()``.  Unshuffled, the batches
+        are contiguous slices of the resident tensors (views, nothing copied) and equal what the reference's
+        ``DataLoader(dataset, batch_size, drop_last=True)`` collates; shuffled, each epoch draws a permutation from
+        ``generator`` and gathers with one ``index_select`` per tensor."""
+        return _Batches((self.piano_roll, self.durations, self.beats), batch_size, drop_last, shuffle, generator)
+
+
+class MaestroWindows(_ResidentWindows):
+    """The training set of model 2 as data_viewing_and_processing.ipynb cell 11 builds it, resident on the device:
+    ``piano_roll``, ``durations`` (N,128,L) and ``beats`` (N,beats_length) fp32; the host arrays ``file_index`` and
+    ``window_index`` (int64) say which input file and which window of it item n is (window i = steps i*L .. (i+1)*L).
+    ``beats`` holds the file's first ``beats_length`` beat times, zero-padded, the same row for all windows of a file.
+
+    Memory: two (128, L) fp32 planes and a beats row per window -- 51 KB at L = 50, about 280 MB for MAESTRO's
+    ~5.4 k windows (1 276 files, sample_size 300)."""
+
+    def __init__(self, piano_roll, durations, beats, file_index, window_index, sample_size, files=None):
+        self.piano_roll, self.durations, self.beats = piano_roll, durations, beats
+        self.file_index = np.asarray(file_index, dtype=np.int64)
+        self.window_index = np.asarray(window_index, dtype=np.int64)
+        self.sample_size, self.sequence_length, self.beats_length = int(sample_size), piano_roll.shape[2], beats.shape[1]
+        self.files = files
+        self.device = piano_roll.device
+
+    @classmethod
+    def from_midi(cls, root_dir_or_list, sample_size=300, sequence_length=50, beats_length=50, device="cuda",
+                  pattern="**/*.mid*"):
+        """Parse the files (a directory searched with ``pattern``, or a list of paths / bytes / MidiData), upload the
+        concatenated row events once and rasterise every kept window in one launch.  Files that yield no window
+        contribute nothing; if none does, ValueError."""
+        if sequence_length <= 0 or sample_size <= 0:
+            raise ValueError(f"sample_size={sample_size} and sequence_length={sequence_length} must be positive")
+        if isinstance(root_dir_or_list, (str, os.PathLike)):
+            files = sorted(glob.glob(os.path.join(root_dir_or_list, pattern), recursive=True))
+        else:
+            files = list(root_dir_or_list)
+        ptrs, steps, vels, beats = [np.zeros(1, dtype=np.int32)], [], [], []
+        win_file, file_index, window_index = [], [], []
+        total = 0
+        for idx, item in enumerate(files):
+            md = item if isinstance(item, MidiData) else read_midi(item)
+            _total_time, kept, (rp, st, ve) = window_plan(md, sample_size, sequence_length)
+            if not len(kept):
+                continue
+            win_file.append(np.full(len(kept), len(beats), dtype=np.int32))      # index among the uploaded files
+            file_index.append(np.full(len(kept), idx, dtype=np.int64))
+            window_index.append(kept)
+            ptrs.append(rp[1:] + total)
+            total += int(rp[-1])
+            steps.append(st)
+            vels.append(ve)
+            beats.append(_fit_beats(get_beats(md), beats_length))
+        if not beats:
+            raise ValueError(f"none of the {len(files)} files read yields a window: a file needs "
+                             f"2 * sequence_length = {2 * sequence_length} seconds (window 0 is dropped) within "
+                             f"sample_size = {sample_size}")
+        dev = torch.device(device)
+        win_file, window_index = np.concatenate(win_file), np.concatenate(window_index)
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+        roll, dur = ops.piano_roll_windows(up(np.concatenate(ptrs)), up(np.concatenate(steps)), up(np.concatenate(vels)),
+                                           up(win_file), up((window_index * sequence_length).astype(np.int32)),
+                                           sequence_length)
+        rows = up(np.stack(beats).astype(np.float32))
+        return cls(roll, dur, rows.index_select(0, up(win_file.astype(np.int64))), np.concatenate(file_index),
+                   window_index, sample_size, files=[f for f in files if isinstance(f, (str, os.PathLike))] or None)
+
+    def save(self, path):
+        """Plain tensors (torch.save); ``load`` reads them back with ``weights_only=True``."""
+        torch.save({"piano_roll": self.piano_roll.cpu(), "durations": self.durations.cpu(), "beats": self.beats.cpu(),
+                    "file_index": torch.from_numpy(self.file_index), "window_index": torch.from_numpy(self.window_index),
+                    "sample_size": torch.tensor(self.sample_size)}, path)
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        dev = torch.device(device)
+        return cls(d["piano_roll"].to(dev), d["durations"].to(dev), d["beats"].to(dev), d["file_index"].numpy(),
+                   d["window_index"].numpy(), int(d["sample_size"]))
+
+    def to_pickle(self, path):
+        """The reference's ``preprocessed_data_{L}.pkl`` (notebook cell 11): a pickled list of (piano_roll, durations,
+        beats) CPU float32 tensors, readable by the reference's own MaestroDatasetPickle."""
+        roll, dur, beats = self.piano_roll.cpu(), self.durations.cpu(), self.beats.cpu()
+        data = [(roll[i].clone(), dur[i].clone(), beats[i].clone()) for i in range(len(self))]
+        with open(path, "wb") as f:
+            pickle.dump(data, f)
+
+
+class MaestroDatasetPickle(_ResidentWindows):
+    """The reference's pickle dataset (datasets.py:73-87): ``data_dir/pickle_file_name`` holds the list of (piano_roll,
+    durations, beats) tensors notebook cell 11 (or ``MaestroWindows.to_pickle``) writes; ``data_dir`` replaces the
+    hard-wired ``'data\\'``.  The list is stacked once onto ``device`` and items are views of it; ``sequence_length``
+    and ``beats_length`` are stored and otherwise unused, as upstream.  Works on the CPU and launches nothing.
+
+    The file is read with ``pickle.load``, as upstream reads it: unpickling runs code the file names, so open only files
+    you trust (``MaestroWindows.save`` / ``load`` is the format without that property)."""
+
+    def __init__(self, pickle_file_name, sequence_length=100, beats_length=50, device="cpu", *, data_dir="data"):
+        self.sequence_length, self.beats_length, self.device = sequence_length, beats_length, torch.device(device)
+        with open(os.path.join(data_dir, pickle_file_name), "rb") as f:
+            data = pickle.load(f)
+        if not data:
+            raise ValueError(f"{pickle_file_name} holds no item")
+        self.piano_roll, self.durations, self.beats = (
+            torch.stack([torch.as_tensor(item[k]) for item in data]).float().to(self.device) for k in range(3))
+
+
+class MaestroDatasetTorch(torch.utils.data.Dataset):
+    """The reference's per-file tensor dataset (datasets.py:90-100): item = ``torch.load`` of the (piano_roll,
+    durations, beats) tuple notebook cell 9 (or ``write_torch_files``) saved for one MIDI file, moved to ``device``;
+    ``pattern`` under ``root_dir`` replaces the hard-wired ``'data\\tensors\\*.pt'``."""
+
+    def __init__(self, root_dir, sequence_length=100, beats_length=50, device="cpu", *, pattern="*.pt"):
+        self.data_dir, self.sequence_length, self.beats_length, self.device = root_dir, sequence_length, beats_length, device
+        self.file_list = sorted(glob.glob(os.path.join(root_dir, pattern)))
+
+    def __len__(self):
+        return len(self.file_list)
+
+    def __getitem__(self, idx):
+        return tuple(t.to(self.device) for t in torch.load(self.file_list[idx], map_location="cpu", weights_only=True))
+
+
+def write_torch_files(midi_inputs, out_dir, sequence_length=100, beats_length=50, start=0, end=50, device="cuda"):
+    """Notebook cell 9: one ``data_{idx}.pt`` per MIDI file holding its (piano_roll, durations, beats) CPU float32
+    tuple, all files rasterised by one ``generate_piano_rolls`` launch.  Returns the paths written."""
+    midi_inputs = list(midi_inputs)
+    roll, dur, beats = (t.cpu() for t in generate_piano_rolls(midi_inputs, sequence_length, beats_length, start, end,
+                                                              device))
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for idx in range(len(midi_inputs)):
+        paths.append(os.path.join(out_dir, f"data_{idx}.pt"))
+        torch.save((roll[idx].clone(), dur[idx].clone(), beats[idx].clone()), paths[-1])
+    return paths
 
 
 class InputSong(torch.utils.data.Dataset):

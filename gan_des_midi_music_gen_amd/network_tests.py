@@ -9,6 +9,7 @@
     MultiModalGAN(z_dim=100, hidden_dim=64, adj_size=(28, 28), roll_size=(2,128,50), input_dim=50, output_dim=16,
                   instrument=None, start=30, end=80, device='cpu')                             :163-206
     TestMultiModalGAN.test_training_loop(batch_size=16) / training_loop(...)                   :208-350
+    training_loop(..., midi_dir=DIR | pickle_file=FILE) / python -m ... --midi-dir DIR         :229-230 on real data
 
 Module trees and state_dict keys equal the reference's (``gen.{i}.0`` = Linear, ``gen.{i}.1`` = BatchNorm1d,
 ``conv1/conv2/fc``), so the committed ``mmgan_64_64_epoch_*.pth`` files load with ``strict=True``.  The nn children
@@ -224,11 +225,16 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
                   device=None, noise_dim=50, gen2_output_dim=20, max_beat_length=50, adj_size=(64, 64),
                   sequence_length=50, lr=0.01, model_path=None, save_dir=None, compute_dtype=None,
                   elide_dead_backward=False, print_interval=10, seed=None, epoch_sleep=0.0, log=print,
-                  criterion="bce"):
+                  criterion="bce", midi_dir=None, pickle_file=None, sample_size=300):
     """The body of ``TestMultiModalGAN.test_training_loop`` (network_tests.py:209-350) on the fused MI355X step.
 
     train_loader: iterable of (piano_roll, durations, beats) batches (the reference's MaestroDatasetPickle loader,
         batch_size, drop_last); None -> seeded MAESTRO-shaped synthetic batches (``steps_per_epoch``, default 8).
+    midi_dir: a directory (or list) of MIDI files -> ``datasets.MaestroWindows.from_midi(midi_dir, sample_size,
+        sequence_length, max_beat_length)``, the dataset notebook cell 11 pickles, built once on the device;
+        pickle_file: path of such a pickle (``preprocessed_data_{sequence_length}.pkl``) -> ``MaestroDatasetPickle``.
+        Either feeds every epoch with ``batches(batch_size)``: unshuffled, drop_last, as the reference's DataLoader
+        (network_tests.py:229-230).  At most one of train_loader / midi_dir / pickle_file.
     fake_provider(g1_out, g2_out, count) -> ((B,2,128,T) tensor, failed): the DES bridge; "des" -> the built-in one
         (DES core + batched log -> MIDI -> piano-roll kernel); None -> synthetic rolls.
     save_dir: if given, per-epoch ``losses/*.pkl`` and ``models/mmgan_{a}_{b}_epoch_{e}.pth`` are written there with
@@ -237,8 +243,22 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
         nn.BCEWithLogitsLoss(), nn.MSELoss(), nn.L1Loss()).
     Returns (disc_losses, gen_losses) of the last epoch, like the reference.
     """
+    if sum(src is not None for src in (train_loader, midi_dir, pickle_file)) > 1:
+        raise ValueError("give at most one of train_loader, midi_dir and pickle_file")
     from .train import MmganTrainer, StepLR
     device = torch.device(device if device is not None else "cuda")
+    if midi_dir is not None or pickle_file is not None:
+        from . import datasets
+        if midi_dir is not None:
+            dataset = datasets.MaestroWindows.from_midi(midi_dir, sample_size, sequence_length, max_beat_length, device)
+        else:
+            dataset = datasets.MaestroDatasetPickle(pickle_file, sequence_length, max_beat_length, device, data_dir="")
+        if tuple(dataset.piano_roll.shape[1:]) != (128, sequence_length):
+            raise ValueError(f"the dataset's rolls are {tuple(dataset.piano_roll.shape[1:])}, the model takes "
+                             f"(128, {sequence_length})")
+        if len(dataset) < batch_size:
+            raise ValueError(f"the dataset holds {len(dataset)} windows, fewer than one batch of {batch_size}")
+        train_loader = dataset.batches(batch_size)
     if seed is not None:
         torch.manual_seed(seed)
     roll_size = (2, 128, sequence_length)
@@ -317,8 +337,8 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
 
 class TestMultiModalGAN(unittest.TestCase):
     def test_training_loop(self, batch_size=16):
-        """Same entry point as the reference's unittest; runs a short synthetic-data schedule when the MAESTRO pickle
-        and the DES bridge are absent (they are not part of this build)."""
+        """Same entry point as the reference's unittest; runs a short synthetic-data schedule (no MAESTRO file ships
+        with this build: ``training_loop(midi_dir=...)`` / ``pickle_file=...`` is the real-data route)."""
         if not torch.cuda.is_available():
             self.skipTest("needs a HIP device")
         # network_tests.py:211: the reference's loop runs under anomaly detection; here that makes every iteration check
@@ -332,5 +352,37 @@ class TestMultiModalGAN(unittest.TestCase):
             torch.autograd.set_detect_anomaly(was)
 
 
+_CLI_OPTIONS = ("--midi-dir", "--pickle", "--epochs", "--batch-size", "--sequence-length", "--sample-size",
+                "--fake-provider", "--save-dir", "--max-steps")
+
+
+def main(argv=None):
+    """``python -m gan_des_midi_music_gen_amd.network_tests``: with --midi-dir or --pickle, ``training_loop`` on that
+    data; without any of the options below, the reference's ``unittest.main()``."""
+    import argparse
+    import sys
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if not any(a.split("=")[0] in _CLI_OPTIONS for a in argv):
+        return unittest.main(argv=[sys.argv[0]] + argv)
+    ap = argparse.ArgumentParser(prog="gan_des_midi_music_gen_amd.network_tests", description=main.__doc__)
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--midi-dir", help="directory of MIDI files (MaestroWindows.from_midi)")
+    src.add_argument("--pickle", help="preprocessed_data_{L}.pkl of notebook cell 11 (MaestroDatasetPickle)")
+    ap.add_argument("--epochs", type=int, default=100)
+    ap.add_argument("--batch-size", type=int, default=16)
+    ap.add_argument("--sequence-length", type=int, default=50)
+    ap.add_argument("--sample-size", type=int, default=300)
+    ap.add_argument("--fake-provider", choices=("des",), default=None,
+                    help="des: the built-in DES bridge; default: synthetic fake rolls")
+    ap.add_argument("--save-dir", default=None)
+    ap.add_argument("--max-steps", type=int, default=None, help="steps per epoch at most")
+    a = ap.parse_args(argv)
+    training_loop(a.batch_size, num_epochs=a.epochs, midi_dir=a.midi_dir, pickle_file=a.pickle,
+                  sample_size=a.sample_size, sequence_length=a.sequence_length, fake_provider=a.fake_provider,
+                  save_dir=a.save_dir, steps_per_epoch=a.max_steps)
+    return 0
+
+
 if __name__ == "__main__":
-    unittest.main()
+    import sys
+    sys.exit(main())

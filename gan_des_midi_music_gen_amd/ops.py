@@ -942,6 +942,53 @@ def piano_roll_raster(row_ptr, ev_step, ev_vel, n_files, width):
     return roll, dur
 
 
+PIANO_ROLL_WINDOW_MAX = 160     # both (128, L) fp32 planes of a window in one workgroup's 160 KB of LDS
+
+
+def piano_roll_windows(row_ptr, ev_step, ev_vel, win_file, win_s0, length, *, roll=None, dur=None):
+    """CSR note messages of F files (piano_roll_raster's arrays) and N windows (file index, first step; int32 device
+    tensors) -> (roll, dur) (N, 128, length) fp32: columns [s0, s0 + length) of each window's file, one launch
+    (gdm_piano_roll_windows, include/gdm.h).  ``roll`` / ``dur``: contiguous (N, 128, length) fp32 tensors to fill.
+
+    Everything the kernel indexes with is checked here first (small reductions and one sync, not arithmetic of the
+    path): the arrays come from the host, where a wrong one would otherwise become a read outside a buffer."""
+    _need_gpu(row_ptr, ev_step, ev_vel, win_file, win_s0, roll, dur)
+    length = int(length)
+    for t in (row_ptr, ev_step, ev_vel, win_file, win_s0):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise GdmError("piano_roll_windows: row_ptr, ev_step, ev_vel, win_file, win_s0 must be contiguous 1-D int32")
+    n_files, rest = divmod(row_ptr.numel() - 1, 128)
+    if n_files < 1 or rest:
+        raise GdmError("piano_roll_windows: row_ptr must hold 128 * files + 1 offsets")
+    if ev_step.numel() != ev_vel.numel():
+        raise GdmError("piano_roll_windows: ev_step and ev_vel must have one length")
+    n = win_file.numel()
+    if n < 1 or win_s0.numel() != n:
+        raise GdmError("piano_roll_windows: win_file and win_s0 must hold N > 0 windows each")
+    if not 0 < length <= PIANO_ROLL_WINDOW_MAX:
+        raise GdmError(f"piano_roll_windows: length = {length} is outside 1..{PIANO_ROLL_WINDOW_MAX} (both planes of a "
+                       "window are built in one workgroup's LDS)")
+    n_ev = ev_step.numel()
+    bad = ((row_ptr[1:] < row_ptr[:-1]).any() | (row_ptr[0] != 0) | (row_ptr[-1] != n_ev) |
+           (win_file < 0).any() | (win_file >= n_files).any() | (win_s0 < 0).any() |
+           (win_s0 > 2 ** 31 - 1 - length).any())
+    if bool(bad.item()):
+        raise GdmError(f"piano_roll_windows: row_ptr must ascend from 0 to {n_ev} (the number of messages), file indices "
+                       f"lie in [0, {n_files}) and first steps in [0, {2 ** 31 - 1 - length}]")
+    dev = row_ptr.device
+    shape = (n, 128, length)
+    if roll is None:
+        roll = torch.empty(shape, dtype=torch.float32, device=dev)
+    if dur is None:
+        dur = torch.empty(shape, dtype=torch.float32, device=dev)
+    for t in (roll, dur):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise GdmError(f"piano_roll_windows: roll / dur must be contiguous {shape} fp32 tensors on {dev}")
+    _call("gdm_piano_roll_windows", _p(row_ptr), _p(ev_step), _p(ev_vel), _p(win_file), _p(win_s0), n, length, _p(roll),
+          _p(dur), _stream())
+    return roll, dur
+
+
 DES_MIDI_TRACK_CAP = 512        # GDM_DES_MIDI_TRACK_CAP
 DES_MIDI_ERRORS = {1: "MIDI parameters (gen2 tail) not finite or out of range", 2: "arrival at a node without "
                    "instrument / note level", 3: "program or note outside 0..127", 4: "base + var == 0 (modulo by zero)"}

@@ -431,6 +431,21 @@ int gdm_des_routing(const float* g, int64_t sample_stride, int B, int S, int dim
 int gdm_piano_roll_raster(const int32_t* row_ptr, const int32_t* ev_step, const int32_t* ev_vel, int n_files, int W,
                           float* roll, float* dur, void* stream);
 
+/* ---- windowed piano-roll rasteriser: the planes of generate_piano_roll(midi, sample_size, beats_length) of
+ * data_viewing_and_processing.ipynb cell 10 (the event loop of MMGAN_MIDI_DES/datasets.py:29-45 on (128, sample_size)
+ * planes) cut into windows of L steps as cell 11 cuts them, without building the full-width planes.
+ * row_ptr / ev_step / ev_vel are gdm_piano_roll_raster's CSR arrays.  Window n < n_windows is (win_file[n], win_s0[n]):
+ * roll, dur (n_windows,128,L) fp32 receive columns [s0, s0 + L) of that file's planes -- a duration written by a
+ * note_off keeps its full-length value off - on in every window it crosses, note_on_time carries over from earlier
+ * windows, later messages overwrite earlier ones, and what no message writes is zero.  Any window list is allowed (any
+ * first step, overlaps, window 0); which windows a dataset keeps is the caller's policy.  One launch, one workgroup per
+ * window, both planes built in LDS and stored with 16-byte stores: L <= 160 (2 * 128 * L floats <= 160 KB), roll and
+ * dur 16-byte aligned, win_s0[n] >= 0 and win_s0[n] + L <= INT32_MAX, win_file[n] a file of row_ptr (the caller's
+ * statement about device arrays: the Python wrapper checks it).                                                     */
+int gdm_piano_roll_windows(const int32_t* row_ptr, const int32_t* ev_step, const int32_t* ev_vel,
+                           const int32_t* win_file, const int32_t* win_s0, int n_windows, int L, float* roll,
+                           float* dur, void* stream);
+
 /* ---- DES log -> MIDI track -> piano-roll planes, batched over samples (process_adjsim_log / MidiGenerator,
  * MMGAN_MIDI_DES/sim_log_to_midi.py:14-277, then generate_piano_roll on the file it builds, datasets.py:13-54).
  * One launch, one workgroup per sample.  Records of sample s are value/event_id/node/kind[rec_ptr[s] .. rec_ptr[s+1])
