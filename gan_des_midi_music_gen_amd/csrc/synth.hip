@@ -1,0 +1,205 @@
+// The integer synth of model 1's DES bridge: note lists -> the mel featuriser's STFT frame matrix (gdm_synth_frames) or
+// 16-bit PCM (gdm_synth_pcm).  It stands where the reference renders its MIDI file through FluidSynth and loads the WAV
+// again (GAN_DES/matrix_sim_process.py:114-129); FluidSynth's sound font is not imitated -- the synth is DEFINED here
+// (include/gdm.h) and is integer only, so that a numpy mirror can demand equal bits.
+//
+// A voice (s_on, s_off, pitch p, velocity v) contributes at sample s in [s_on, s_off + R):
+//   phase = uint32(inc[p] * (s - s_on));  e_att = min(s - s_on + 1, A);  e_rel = s < s_off ? R : R - (s - s_off)
+//   voice = (int64(wave[phase >> 21]) * v * e_att * e_rel) >> SHIFT                     (arithmetic shift)
+// and a sample is the int32 sum of its voices clamped to the 16-bit range.
+//
+// Both kernels work on 2048 output samples per workgroup.  The clips are minutes long and the 216 frames of a clip read
+// about a tenth of it, so whole clips are never rendered: a workgroup first COMPACTS the notes that overlap the sample
+// range it will touch into LDS (all threads scan the clip's list; the integer sum does not depend on the order, so the
+// slots are dealt by an LDS atomic counter), rebased to the range's first sample so that everything after is 32-bit.
+// Then every thread produces 8 samples -- the voices in the outer loop, the 8 running sums in registers -- and stores
+// them with 16-byte stores.  LDS: 16 bytes per voice the list can hold (notes_cap of them, 5000 at most: 80 KB) + the
+// 4 KB wave table.
+#include "gdm_common.h"
+#include "buffer_ops.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kChunk = 2048;                       // samples per workgroup = GDM_SYNTH_NFFT
+constexpr int kPer = kChunk / kThreads;            // 8 per thread
+constexpr int kMaxNotes = GDM_DES_NOTES_MAX;
+constexpr int kA = GDM_SYNTH_ATTACK, kR = GDM_SYNTH_RELEASE, kShift = GDM_SYNTH_SHIFT;
+constexpr int kFrames = GDM_SYNTH_FRAMES;
+static_assert(kChunk == GDM_SYNTH_NFFT && GDM_SYNTH_WAVE == 2048, "phase >> 21 indexes a 2048-entry table");
+
+typedef short short8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ int64_t tick_to_sample(int64_t tick) { return (tick * 735) >> 3; }
+
+// Stage the wave table and the voices that sound anywhere in [lo, hi] (hi - lo < 2^13).  A listed voice is
+//   x = phase at sample lo (mod 2^32),  y = inc[p],  z = s_on - lo clamped to [-A, 2^13],
+//   w = (s_off - lo clamped to [-R, 2^20]) + R  |  v << 24
+// The clamps change nothing inside the range: from A samples after s_on the attack is full, and a note-off beyond the
+// range is simply "not yet".  Returns the number of listed voices (<= n <= kMaxNotes: the list cannot overflow).
+__device__ int stage_voices(const int64_t* __restrict__ notes, int n, int64_t lo, int64_t hi,
+                            const int16_t* __restrict__ wave, const uint32_t* __restrict__ inc, int4* s_voice,
+                            int16_t* s_wave, int* s_count) {
+  const int tid = threadIdx.x;
+  if (tid == 0) *s_count = 0;
+  for (int i = tid; i < GDM_SYNTH_WAVE; i += kThreads) s_wave[i] = wave[i];
+  __syncthreads();
+  for (int k = tid; k < n; k += kThreads) {
+    const int64_t s_on = tick_to_sample(notes[4 * (int64_t)k + 0]);
+    const int64_t s_off = tick_to_sample(notes[4 * (int64_t)k + 1]);
+    if (s_on > hi || s_off + kR <= lo) continue;
+    const uint32_t step = inc[notes[4 * (int64_t)k + 2] & 127];
+    const uint32_t vel = (uint32_t)(notes[4 * (int64_t)k + 3] & 127);
+    const int64_t on_rel = min(max(s_on - lo, (int64_t)-kA), (int64_t)1 << 13);
+    const int64_t off_rel = min(max(s_off - lo, (int64_t)-kR), (int64_t)1 << 20);
+    int4 e;
+    e.x = (int)(step * (uint32_t)(uint64_t)(lo - s_on));
+    e.y = (int)step;
+    e.z = (int)on_rel;
+    e.w = (int)((uint32_t)(off_rel + kR) | (vel << 24));
+    s_voice[atomicAdd(s_count, 1)] = e;
+  }
+  __syncthreads();
+  return *s_count;
+}
+
+// THE per-sample function of both kernels: acc[e] += the listed voices at t[e] = sample - lo, e < 8.
+__device__ __forceinline__ void add_voices(const int4* s_voice, int n, const int16_t* s_wave, const int (&t)[kPer],
+                                           int (&acc)[kPer]) {
+  for (int k = 0; k < n; ++k) {
+    const int4 v = s_voice[k];
+    const int off = (int)((uint32_t)v.w & 0xFFFFFFu) - kR, vel = (int)((uint32_t)v.w >> 24);
+#pragma unroll
+    for (int e = 0; e < kPer; ++e) {
+      const int d = t[e] - v.z, past = t[e] - off;                  // samples since note-on / since note-off
+      if (d >= 0 && past < kR) {
+        const uint32_t phase = (uint32_t)v.x + (uint32_t)v.y * (uint32_t)t[e];
+        const int e_att = min(d + 1, kA);
+        const int e_rel = past < 0 ? kR : kR - past;
+        const int64_t p = (int64_t)((int)s_wave[phase >> 21] * vel * e_att) * e_rel;      // the int part is < 2^30
+        acc[e] += (int)(p >> kShift);
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ int clamp16(int v) { return min(32767, max(-32768, v)); }
+
+// One workgroup per (frame, sample): element n of frame f is the synth at f * hop + n - 1024, reflected inside the clip
+// by the rule of pcm_stft_frames_kernel (s < 0 -> -s, then s >= L -> 2 (L - 1) - s), times 2^-15 (PCM_S16's decode).
+__global__ __launch_bounds__(kThreads) void synth_frames_kernel(const int64_t* __restrict__ notes, int notes_cap,
+                                                                const int32_t* __restrict__ n_notes,
+                                                                const int64_t* __restrict__ clip_len,
+                                                                const int16_t* __restrict__ wave,
+                                                                const uint32_t* __restrict__ inc,
+                                                                float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  int4* s_voice = reinterpret_cast<int4*>(s_raw);
+  __shared__ int16_t s_wave[GDM_SYNTH_WAVE];
+  __shared__ int s_count;
+  const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int n = min(max(n_notes[b], 0), min(notes_cap, kMaxNotes));
+  const int64_t L = clip_len[b];
+  f32x4* o = reinterpret_cast<f32x4*>(out + ((int64_t)b * kFrames + f) * kChunk + tid * kPer);
+  if (n == 0 || L <= kChunk / 2) {                     // a blank clip: zero frames (uniform over the workgroup)
+    o[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    o[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    return;
+  }
+  const int64_t hop = L / (kFrames - 1);
+  const int64_t a = (int64_t)f * hop - kChunk / 2, z = a + kChunk - 1;                  // the unreflected range
+  const int64_t lo = max((int64_t)0, min(a, 2 * (L - 1) - z)), hi = min(L - 1, max(z, -a));
+  const int nv = stage_voices(notes + (int64_t)b * notes_cap * 4, n, lo, hi, wave, inc, s_voice, s_wave, &s_count);
+  int t[kPer], acc[kPer];
+#pragma unroll
+  for (int e = 0; e < kPer; ++e) {
+    int64_t s = a + tid * kPer + e;
+    s = s < 0 ? -s : s;
+    s = s >= L ? 2 * (L - 1) - s : s;
+    t[e] = (int)min(max(s - lo, (int64_t)0), hi - lo);   // inside by construction; the clamp bounds it for any input
+    acc[e] = 0;
+  }
+  add_voices(s_voice, nv, s_wave, t, acc);
+  f32x4 v0, v1;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v0[e] = (float)clamp16(acc[e]) * 0x1p-15f;
+    v1[e] = (float)clamp16(acc[4 + e]) * 0x1p-15f;
+  }
+  o[0] = v0;
+  o[1] = v1;
+}
+
+// One workgroup per 2048 samples of [first, first + count) of ONE clip, as 16-bit PCM.
+__global__ __launch_bounds__(kThreads) void synth_pcm_kernel(const int64_t* __restrict__ notes, int notes_cap,
+                                                             const int32_t* __restrict__ n_notes,
+                                                             const int16_t* __restrict__ wave,
+                                                             const uint32_t* __restrict__ inc, int64_t first,
+                                                             int64_t count, int16_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  int4* s_voice = reinterpret_cast<int4*>(s_raw);
+  __shared__ int16_t s_wave[GDM_SYNTH_WAVE];
+  __shared__ int s_count;
+  const int tid = threadIdx.x;
+  const int n = min(max(n_notes[0], 0), min(notes_cap, kMaxNotes));
+  const int64_t c0 = (int64_t)blockIdx.x * kChunk;                   // first output sample of this workgroup
+  const int64_t lo = first + c0;
+  const int nv = stage_voices(notes, n, lo, lo + kChunk - 1, wave, inc, s_voice, s_wave, &s_count);
+  int t[kPer], acc[kPer];
+#pragma unroll
+  for (int e = 0; e < kPer; ++e) {
+    t[e] = tid * kPer + e;
+    acc[e] = 0;
+  }
+  add_voices(s_voice, nv, s_wave, t, acc);
+  const int64_t i0 = c0 + tid * kPer;
+  if (i0 + kPer <= count) {
+    short8 v;
+#pragma unroll
+    for (int e = 0; e < kPer; ++e) v[e] = (short)clamp16(acc[e]);
+    *reinterpret_cast<short8*>(out + i0) = v;
+  } else {
+#pragma unroll
+    for (int e = 0; e < kPer; ++e)
+      if (i0 + e < count) out[i0 + e] = (int16_t)clamp16(acc[e]);
+  }
+}
+
+int tables_ok(const char* who, const void* notes, int notes_cap, const void* n_notes, const void* wave, const void* inc) {
+  GDM_REQUIRE(notes && n_notes && wave && inc, "%s: null pointer", who);
+  GDM_REQUIRE(notes_cap > 0 && notes_cap <= GDM_DES_NOTES_MAX, "%s: %d notes per clip (1 .. %d fit the voice list)", who,
+              notes_cap, GDM_DES_NOTES_MAX);
+  GDM_REQUIRE(((uintptr_t)notes & 7) == 0 && ((uintptr_t)wave & 1) == 0 && ((uintptr_t)inc & 3) == 0,
+              "%s: notes / wave / inc must be aligned to their elements", who);
+  return GDM_OK;
+}
+
+}  // namespace
+
+extern "C" int gdm_synth_frames(const int64_t* notes, int notes_cap, const int32_t* n_notes, const int64_t* clip_len,
+                                int B, const int16_t* wave, const uint32_t* inc, float* frames, void* stream) {
+  if (int rc = tables_ok("gdm_synth_frames", notes, notes_cap, n_notes, wave, inc)) return rc;
+  GDM_REQUIRE(clip_len && frames, "gdm_synth_frames: null pointer");
+  GDM_REQUIRE(B > 0 && B <= 65535, "gdm_synth_frames: B = %d (1 .. 65535)", B);
+  GDM_REQUIRE(((uintptr_t)frames & 15) == 0, "gdm_synth_frames: frames must be 16-byte aligned (16-byte stores)");
+  allow_lds(synth_frames_kernel, kMaxNotes * sizeof(int4));
+  hipLaunchKernelGGL(synth_frames_kernel, dim3(kFrames, B), dim3(kThreads), notes_cap * sizeof(int4), (hipStream_t)stream, notes,
+                     notes_cap, n_notes, clip_len, wave, inc, frames);
+  GDM_LAUNCH_OK("gdm_synth_frames");
+  return GDM_OK;
+}
+
+extern "C" int gdm_synth_pcm(const int64_t* notes, int notes_cap, const int32_t* n_notes, const int16_t* wave,
+                             const uint32_t* inc, int64_t first, int64_t count, int16_t* out, void* stream) {
+  if (int rc = tables_ok("gdm_synth_pcm", notes, notes_cap, n_notes, wave, inc)) return rc;
+  GDM_REQUIRE(out && ((uintptr_t)out & 15) == 0, "gdm_synth_pcm: out must be a 16-byte aligned buffer (16-byte stores)");
+  GDM_REQUIRE(first >= 0 && first <= ((int64_t)1 << 40) && count > 0 && count <= ((int64_t)1 << 30),
+              "gdm_synth_pcm: samples %lld .. +%lld (first within 0 .. 2^40, 1 .. 2^30 samples per call)",
+              (long long)first, (long long)count);
+  allow_lds(synth_pcm_kernel, kMaxNotes * sizeof(int4));
+  hipLaunchKernelGGL(synth_pcm_kernel, dim3((unsigned)((count + kChunk - 1) / kChunk)), dim3(kThreads),
+                     notes_cap * sizeof(int4),
+                     (hipStream_t)stream, notes, notes_cap, n_notes, wave, inc, first, count, out);
+  GDM_LAUNCH_OK("gdm_synth_pcm");
+  return GDM_OK;
+}

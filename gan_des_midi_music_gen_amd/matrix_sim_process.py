@@ -7,10 +7,13 @@
 
 Both reference functions do, per generated sample, (1) a block of numpy arithmetic that turns the generator's matrix
 into the constructor arguments of the discrete-event simulator and (2) the simulation / MIDI / audio rendering.  Part
-(2) is INJECTED here as ``simulate``, exactly where the reference constructs ``Sim``: a callable, or -- for
-matrix_to_midi -- the string "des" for the built-in back end (simulation_v3's deterministic DES core on the host, then
-one batched log -> MIDI -> piano-roll launch, sim_log_to_midi.py / csrc/des_midi.hip).  FluidSynth rendering
-(matrix_to_wav) stays outside.  Part (1) runs batched on the device (``ops.des_scan`` / ``ops.des_routing``, csrc/des_prologue.hip): the
+(2) is INJECTED here as ``simulate``, exactly where the reference constructs ``Sim``: a callable, or the string "des" for
+the built-in back end -- simulation_v3's deterministic DES core on the host, then batched device stages over all B
+event logs: for matrix_to_midi one log -> MIDI -> piano-roll launch (sim_log_to_midi.py / csrc/des_midi.hip); for
+matrix_to_wav log -> notes (sim_log_process_music.py / csrc/des_notes.hip), the integer synth evaluated straight into
+the STFT frame matrix (csrc/synth.hip) and the mel chain (util._db_from_frames).  The synth stands where the reference
+calls FluidSynth: its sound font is not reproducible and is not imitated.  Part (1) runs batched
+on the device (``ops.des_scan`` / ``ops.des_routing``, csrc/des_prologue.hip): the
 generator output never leaves HBM as a whole; what crosses to the host is the per-row masks the RNG bookkeeping needs
 and the final float64 routing matrices the simulator consumes.
 
@@ -281,13 +284,44 @@ def wav_prologue(matrices, size=20, use_same_instrument=None):
     return _batched_specs(h, _wav_draws, lambda h_, i, r, src, sd: _wav_spec(h_, i, r, src, sd, use_same_instrument))
 
 
-def matrix_to_wav(matrices, size=20, use_same_instrument=None, start=0, end=174, device="cpu", simulate=None):
-    """Reference signature + ``simulate(spec, index=...)`` standing in for Sim + log->MIDI + FluidSynth + mel
-    featuriser: it returns the (128, T) dB spectrogram tensor of one sample.  Returns the stacked (B,128,end-start)
-    tensor on ``device``."""
+def matrix_to_wav(matrices, size=20, use_same_instrument=None, start=0, end=174, device="cpu", simulate=None, *,
+                  max_events=200000):
+    """Reference signature + ``simulate``.  Returns the stacked (B,128,end-start) dB tensor on ``device``.
+
+    simulate=callable: ``simulate(spec, index=...)`` stands in for Sim + log->MIDI + FluidSynth + mel featuriser and
+    returns the (128, T) dB spectrogram tensor of one sample.
+    simulate="des": the built-in back end.  Per sample, in the reference's order: draws, routing, ``run_spec`` (the
+    deterministic DES core; it consumes numpy's global stream like upstream's Sim); then the B logs are uploaded once and
+    three batched device stages follow without a host round trip between them: log -> notes, notes -> the (B*216, 2048)
+    STFT frame matrix of the integer synth, frames -> mel dB.  A clip without notes is the reference's "blank wav":
+    -100 dB everywhere.  Exceptions of the prologue and of ``run_spec`` propagate (the reference has no ``try``
+    either).  The reference's 0.5 s wall-clock cap has no counterpart: the core stops after ``max_events`` events."""
     if simulate is None:
-        raise ops.GdmError("matrix_to_wav: the DES / FluidSynth back end is outside this package; pass simulate=callable")
+        raise ops.GdmError("matrix_to_wav: pass simulate=\"des\" for the built-in DES / synth back end or "
+                           "simulate=callable (it receives the DesSpec the reference would construct Sim from)")
     h = _wav_scan(matrices, size)
     specs = _interleaved_specs(h, _wav_draws, lambda h_, i, r, src, sd: _wav_spec(h_, i, r, src, sd, use_same_instrument))
+    if isinstance(simulate, str):
+        if simulate != "des":
+            raise ops.GdmError(f"matrix_to_wav: unknown back end {simulate!r} (the built-in one is \"des\")")
+        mel, _notes = _specs_to_mel(specs, h["g1"].device, max_events)
+        return mel[:, :, start:end].to(device)
     spectrograms = [torch.as_tensor(simulate(spec, index=i)) for i, spec in enumerate(specs)]
     return torch.stack([s[:, start:end] for s in spectrograms]).to(device)
+
+
+def _specs_to_mel(specs, dev, max_events):
+    """The built-in back end behind matrix_to_wav: DesSpecs (consumed one by one, so that each simulation runs before
+    the next sample's draws) -> ((B, 128, 216) dB device tensor, (notes, n_notes, clip_len) device tensors)."""
+    from . import sim_log_process_music, simulation_v3, util
+    logs, insts, notes = [], [], []
+    for spec in specs:
+        log, _reason = simulation_v3.run_spec(spec, max_events=max_events)
+        logs.append(log)
+        insts.append(spec.instruments)
+        notes.append(spec.note_levels)
+    *staged, status = sim_log_process_music.stage_notes(logs, insts, notes, device=dev)
+    frames = ops.synth_frames(*staged)
+    mel = util._db_from_frames(frames, len(logs), ops.SYNTH_FRAMES, ops.SYNTH_RATE, ops.SYNTH_NFFT, 128, 20, 8300, 80)
+    sim_log_process_music.raise_for_status(status)           # read back once, after all three stages are enqueued
+    return mel, tuple(staged)

@@ -1042,6 +1042,109 @@ def des_log_to_roll(value, event_id, node, kind, rec_ptr, tails, instruments, no
     return planes, track, track_len, status
 
 
+# ---- model 1's DES bridge: log -> notes -> integer synth (GAN_DES/sim_log_process_music.py:65-133,159-185;
+# GAN_DES/matrix_sim_process.py:112-129) ------------------------------------------------------------------------------
+DES_NOTES_MAX = 5000            # GDM_DES_NOTES_MAX
+DES_NOTES_ERRORS = {1: "a note for a node without note level", 2: "note outside 0..127"}       # the reference raises
+DES_NOTES_ELONG = 3             # the clip would pass 2^40 samples: left blank, nothing is raised
+SYNTH_ATTACK, SYNTH_RELEASE, SYNTH_SHIFT, SYNTH_WAVE, SYNTH_FRAMES, SYNTH_NFFT = 256, 8192, 30, 2048, 216, 2048
+SYNTH_RATE = 44100
+_synth_tables = {}
+
+
+def synth_tables(device):
+    """(wave int16[2048], inc int32[128] holding the uint32 bit patterns): built once in float64, cached per device."""
+    key = str(device)
+    if key not in _synth_tables:
+        i = torch.arange(SYNTH_WAVE, dtype=torch.float64)
+        wave = torch.round(32767.0 * torch.sin(2.0 * torch.pi * i / SYNTH_WAVE)).to(torch.int16)
+        p = torch.arange(128, dtype=torch.float64)
+        inc = torch.round(2.0 ** 32 * 440.0 * 2.0 ** ((p - 69.0) / 12.0) / SYNTH_RATE).to(torch.int64)
+        inc = torch.where(inc >= 2 ** 31, inc - 2 ** 32, inc).to(torch.int32)
+        _synth_tables[key] = (wave.to(device), inc.to(device))
+    return _synth_tables[key]
+
+
+def des_log_to_notes(value, event_id, node, kind, rec_ptr, note_levels):
+    """Event records of B samples (CSR: rec_ptr (B+1) i64) -> (notes (B,5000,4) i64 of (on_tick, off_tick, pitch,
+    velocity), n_notes (B) i32, clip_len (B) i64, status (B) i32), all device tensors; one launch
+    (gdm_des_log_to_notes, include/gdm.h)."""
+    _need_gpu(value, event_id, node, kind, rec_ptr, note_levels)
+    n = value.numel()
+    b = rec_ptr.numel() - 1
+    for t, dt in ((value, torch.float64), (event_id, torch.int64), (node, torch.int32), (kind, torch.int32)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise GdmError("des_log_to_notes: records must be contiguous f64 / i64 / i32 / i32 arrays of one length")
+    if rec_ptr.dtype != torch.int64 or b < 1 or not rec_ptr.is_contiguous():
+        raise GdmError("des_log_to_notes: rec_ptr must be a contiguous int64 tensor of B + 1 offsets")
+    if note_levels.dtype != torch.int32 or note_levels.dim() != 2 or note_levels.shape[0] != b or \
+            not note_levels.is_contiguous():
+        raise GdmError("des_log_to_notes: note_levels must be contiguous (B, dim) int32")
+    if bool(((rec_ptr[1:] < rec_ptr[:-1]).any() | (rec_ptr[0] < 0) | (rec_ptr[-1] > n)).item()):
+        raise GdmError(f"des_log_to_notes: rec_ptr must ascend within [0, {n}] (the number of records)")
+    dev = value.device
+    notes = torch.zeros((b, DES_NOTES_MAX, 4), dtype=torch.int64, device=dev)
+    n_notes = torch.empty(b, dtype=torch.int32, device=dev)
+    clip_len = torch.empty(b, dtype=torch.int64, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    _call("gdm_des_log_to_notes", _p(value), _p(event_id), _p(node), _p(kind), _p(rec_ptr), n, _p(note_levels),
+          note_levels.shape[1], b, _p(notes), DES_NOTES_MAX, _p(n_notes), _p(clip_len), _p(status), _stream())
+    return notes, n_notes, clip_len, status
+
+
+def _synth_args(notes, n_notes, what, tables):
+    _need_gpu(notes, n_notes)
+    if notes.dtype != torch.int64 or notes.dim() != 3 or notes.shape[2] != 4 or not notes.is_contiguous() or \
+            not 1 <= notes.shape[1] <= DES_NOTES_MAX:
+        raise GdmError(f"{what}: notes must be a contiguous (B, 1..{DES_NOTES_MAX}, 4) int64 tensor")
+    if n_notes.dtype != torch.int32 or n_notes.shape != (notes.shape[0],) or not n_notes.is_contiguous():
+        raise GdmError(f"{what}: n_notes must be a contiguous (B,) int32 tensor")
+    wave, inc = synth_tables(notes.device) if tables is None else tables
+    _need_gpu(wave, inc)
+    if wave.dtype != torch.int16 or wave.shape != (SYNTH_WAVE,) or inc.dtype != torch.int32 or inc.shape != (128,) or \
+            not wave.is_contiguous() or not inc.is_contiguous():
+        raise GdmError(f"{what}: tables must be (wave int16[{SYNTH_WAVE}], inc int32[128] holding uint32 bits)")
+    return wave, inc
+
+
+def synth_frames(notes, n_notes, clip_len, *, tables=None, out=None):
+    """Note lists of B clips -> the (B * 216, 2048) fp32 frame matrix ``util._db_from_frames`` takes (gdm_synth_frames,
+    include/gdm.h).  ``out``: a contiguous tensor of that shape to fill."""
+    wave, inc = _synth_args(notes, n_notes, "synth_frames", tables)
+    b = notes.shape[0]
+    _need_gpu(clip_len)
+    if clip_len.dtype != torch.int64 or clip_len.shape != (b,) or not clip_len.is_contiguous():
+        raise GdmError("synth_frames: clip_len must be a contiguous (B,) int64 tensor")
+    if out is None:
+        out = torch.empty((b * SYNTH_FRAMES, SYNTH_NFFT), dtype=torch.float32, device=notes.device)
+    else:
+        _need_gpu(out)
+        if out.dtype != torch.float32 or out.shape != (b * SYNTH_FRAMES, SYNTH_NFFT) or not out.is_contiguous():
+            raise GdmError(f"synth_frames: out must be a contiguous ({b * SYNTH_FRAMES}, {SYNTH_NFFT}) fp32 tensor")
+    _call("gdm_synth_frames", _p(notes), notes.shape[1], _p(n_notes), _p(clip_len), b, _p(wave), _p(inc), _p(out),
+          _stream())
+    return out
+
+
+def synth_pcm(notes, n_notes, first, count, *, tables=None, out=None):
+    """Samples [first, first + count) of ONE clip (notes (1, cap, 4), n_notes (1,)) as an int16 device tensor
+    (gdm_synth_pcm, include/gdm.h)."""
+    wave, inc = _synth_args(notes, n_notes, "synth_pcm", tables)
+    first, count = int(first), int(count)
+    if notes.shape[0] != 1:
+        raise GdmError("synth_pcm renders one clip: pass notes[b:b + 1], n_notes[b:b + 1]")
+    if first < 0 or count <= 0 or count > 1 << 30:
+        raise GdmError(f"synth_pcm: samples {first} .. +{count} (first >= 0, 1 .. 2^30 samples per call)")
+    if out is None:
+        out = torch.empty(count, dtype=torch.int16, device=notes.device)
+    else:
+        _need_gpu(out)
+        if out.dtype != torch.int16 or out.shape != (count,) or not out.is_contiguous():
+            raise GdmError(f"synth_pcm: out must be a contiguous ({count},) int16 tensor")
+    _call("gdm_synth_pcm", _p(notes), notes.shape[1], _p(n_notes), _p(wave), _p(inc), first, count, _p(out), _stream())
+    return out
+
+
 # ---- mel-spectrogram featuriser kernels (GAN_DES/util.py:37-61) -------------------------------------------------------
 def stft_frames(x, hop, n_fft):
     """x (B, L) fp32 -> (B * frames, n_fft) centred, reflect-padded frames; frames = 1 + L // hop."""

@@ -134,8 +134,35 @@ def write_midi(track, path, ticks_per_beat=480):
 def _int_rows(rows, dim_name):
     out = np.ascontiguousarray([[int(x) for x in np.asarray(r).reshape(-1)] for r in rows], dtype=np.int32)
     if out.ndim != 2 or out.shape[1] == 0:
-        raise ops.GdmError(f"log_to_rolls: {dim_name} must hold one equally long list per sample")
+        raise ops.GdmError(f"{dim_name} must hold one equally long list per sample")
     return out
+
+
+def _upload_logs(logs, device, who):
+    """What both batched consumers do with B event logs (``who`` names the caller in messages): checks, then
+    -> (logs as arrays, device, ``up`` (host array -> device tensor), ``records``).  ``records()`` uploads the CSR form
+    the kernels take -- value, event_id, node, kind of the lines the reader looks at, and rec_ptr (B + 1)."""
+    if len(logs) == 0:
+        raise ops.GdmError(f"{who}: no samples")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ops.GdmError(f"{who} runs on a HIP device; there is no CPU path")
+    logs = [np.asarray(lg) for lg in logs]
+    for lg in logs:
+        if lg.dtype != EVENT_DTYPE or lg.ndim != 1:
+            raise ops.GdmError(f"{who}: every log must be a 1-d simulation_v3.EVENT_DTYPE array")
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    def records():
+        heads = [lg[:MAX_LINES] for lg in logs]              # what the reader looks at; the rest never crosses
+        rec_ptr = np.zeros(len(logs) + 1, dtype=np.int64)
+        np.cumsum([len(h) for h in heads], out=rec_ptr[1:])
+        rec = np.concatenate(heads) if rec_ptr[-1] else np.zeros(0, dtype=EVENT_DTYPE)
+        return up(rec["value"]), up(rec["event_id"]), up(rec["node"]), up(rec["kind"]), up(rec_ptr)
+
+    return logs, dev, up, records
 
 
 def log_to_rolls(logs, gen2_tails, instruments, note_levels, *, start=0, end=30, generate=False, save=None,
@@ -147,16 +174,8 @@ def log_to_rolls(logs, gen2_tails, instruments, note_levels, *, start=0, end=30,
     reference's decision ``generate or line count % 100 == 0``.  tracks[i]: (n, 4) int32 (kind, a, b, time) -- the saved
     track, or the track as process_line left it when sample i is not saved (its planes are zero then).
     A sample the reference would raise for raises ValueError here."""
+    logs, dev, up, records = _upload_logs(logs, device, "log_to_rolls")
     b = len(logs)
-    if b == 0:
-        raise ops.GdmError("log_to_rolls: no samples")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ops.GdmError("log_to_rolls runs on a HIP device; there is no CPU path")
-    logs = [np.asarray(lg) for lg in logs]
-    for lg in logs:
-        if lg.dtype != EVENT_DTYPE or lg.ndim != 1:
-            raise ops.GdmError("log_to_rolls: every log must be a 1-d simulation_v3.EVENT_DTYPE array")
     tails = np.ascontiguousarray(gen2_tails.detach().float().cpu().numpy() if torch.is_tensor(gen2_tails)
                                  else np.asarray(gen2_tails, dtype=np.float32))
     if tails.ndim != 2 or tails.shape[0] != b or tails.shape[1] < 6:
@@ -169,14 +188,8 @@ def log_to_rolls(logs, gen2_tails, instruments, note_levels, *, start=0, end=30,
     save = np.ascontiguousarray(save, dtype=np.int32)
     if save.shape != (b,):
         raise ops.GdmError("log_to_rolls: save must hold one flag per sample")
-    heads = [lg[:MAX_LINES] for lg in logs]                  # what the reader looks at; the rest never crosses
-    rec_ptr = np.zeros(b + 1, dtype=np.int64)
-    np.cumsum([len(h) for h in heads], out=rec_ptr[1:])
-    rec = np.concatenate(heads) if rec_ptr[-1] else np.zeros(0, dtype=EVENT_DTYPE)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    planes, track, track_len, status = ops.des_log_to_roll(
-        up(rec["value"]), up(rec["event_id"]), up(rec["node"]), up(rec["kind"]), up(rec_ptr), up(tails), up(inst),
-        up(notes), up(save), start, end, sequence_length)
+    planes, track, track_len, status = ops.des_log_to_roll(*records(), up(tails), up(inst), up(notes), up(save), start,
+                                                           end, sequence_length)
     status, track_len, track = status.cpu().numpy(), track_len.cpu().numpy(), track.cpu().numpy()
     for i in range(b):
         if status[i] >> 8:

@@ -525,6 +525,51 @@ int gdm_pcm_stft_frames(const void* pcm, int fmt, int channels, int mix, int64_t
                         int64_t stride, int n_regular, int64_t tail_start, int64_t win_len, int hop, int n_fft,
                         int frames, float* out, void* stream);
 
+/* ---- model 1's DES bridge: DES log -> notes -> integer synth -> STFT frames / PCM --------------------------------
+ * What the reference does per generated sample between Sim.run and the mel featuriser (GAN_DES/matrix_sim_process.py:
+ * 112-129): process_adjsim_log builds a MIDI file from the log, FluidSynth renders it, the WAV is loaded again.
+ *
+ * gdm_des_log_to_notes (GAN_DES/sim_log_process_music.py:65-133 MidiGenerator.process_line, :159-185 the reader):
+ *   one launch, one workgroup per sample; records in the CSR layout of gdm_des_log_to_roll, only the first 5000 of a
+ *   sample are looked at; note_levels (B, dim) i32.  Outputs: notes (B, notes_cap, 4) i64 = (on_tick, off_tick, pitch,
+ *   velocity) -- the ticks are the cumulative delta times of the strictly sequential note_on / note_off track, as mido
+ *   reads it --, n_notes (B) i32 <= 5000, clip_len (B) i64 = sample(last off_tick) + GDM_SYNTH_RELEASE (0: no notes),
+ *   status (B) i32 = 0 or a GDM_DES_NOTES_E* code; a sample with a code has n_notes = clip_len = 0.
+ *   sample(tick) = (tick * 735) >> 3: 1/480 s per tick (set_tempo 1 000 000, 480 ticks per beat) at 44 100 Hz.
+ *
+ * The synth (defined HERE: FluidSynth's sound font is not imitated).  Integer only.  Tables: wave[2048] i16 (default
+ * round(32767 sin(2 pi i / 2048))), inc[128] u32 = round(2^32 * 440 * 2^((p - 69) / 12) / 44100), both built by the
+ * host in float64.  A voice with s_on = sample(on_tick), s_off = sample(off_tick), pitch p and velocity v (both taken
+ * & 127) contributes at sample s in [s_on, s_off + R):
+ *     phase = (uint32)(inc[p] * (s - s_on))            e_att = min(s - s_on + 1, A)
+ *     e_rel = s < s_off ? R : R - (s - s_off)          voice = ((int64)wave[phase >> 21] * v * e_att * e_rel) >> SHIFT
+ *   (arithmetic shift: -8128 <= voice <= 8127).  A sample is the int32 sum of its voices clamped to [-32768, 32767];
+ *   5000 voices stay below 2^26.
+ * gdm_synth_frames: frames (B * 216, 2048) fp32, the matrix gdm_stft_frames would cut from the rendered clips: with
+ *   hop = clip_len / 215, element (b, f, n) = sample(reflect(f * hop + n - 1024, clip_len)) * 2^-15, reflect as in
+ *   gdm_pcm_stft_frames.  A clip with n_notes = 0 (or clip_len <= 1024) gives zero frames.  One workgroup per (b, f).
+ * gdm_synth_pcm: out[i] = sample(first + i), i < count, of ONE clip (notes, n_notes point at it), as 16-bit PCM.
+ * Checked before the launch: notes_cap <= 5000 (the voice list in LDS), alignment (frames / out: 16 bytes), the sample
+ * range.  n_notes is clamped to [0, notes_cap] on the device; no other device value forms an address.              */
+#define GDM_DES_NOTES_MAX 5000
+#define GDM_DES_NOTES_ENODE 1  /* a note for a node without note level (KeyError upstream) */
+#define GDM_DES_NOTES_EPITCH 2 /* note outside 0..127 (mido refuses the message) */
+#define GDM_DES_NOTES_ELONG 3  /* the clip would pass 2^40 samples: left blank, nothing is raised */
+#define GDM_SYNTH_ATTACK 256
+#define GDM_SYNTH_RELEASE 8192
+#define GDM_SYNTH_SHIFT 30
+#define GDM_SYNTH_WAVE 2048
+#define GDM_SYNTH_FRAMES 216
+#define GDM_SYNTH_NFFT 2048
+int gdm_des_log_to_notes(const double* value, const int64_t* event_id, const int32_t* node, const int32_t* kind,
+                         const int64_t* rec_ptr, int64_t n_records, const int32_t* note_levels, int dim, int B,
+                         int64_t* notes, int notes_cap, int32_t* n_notes, int64_t* clip_len, int32_t* status,
+                         void* stream);
+int gdm_synth_frames(const int64_t* notes, int notes_cap, const int32_t* n_notes, const int64_t* clip_len, int B,
+                     const int16_t* wave, const uint32_t* inc, float* frames, void* stream);
+int gdm_synth_pcm(const int64_t* notes, int notes_cap, const int32_t* n_notes, const int16_t* wave, const uint32_t* inc,
+                  int64_t first, int64_t count, int16_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
