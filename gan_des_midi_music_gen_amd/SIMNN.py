@@ -8,7 +8,7 @@ Same public names, constructor signatures, state_dict keys and training-loop sem
     Discriminator(no_of_channels=1, disc_dim=32)                  SIMNN.py:115-142
     SimNN(n)                                                      SIMNN.py:145-170
     generate_song(model_folder, bridge="des")                     SIMNN.py:201-216
-    des_fake_provider(start=0, end=216)                           (this build: the DES bridge as a fake provider)
+    des_fake_provider(start=0, end=216, batched=False)            (this build: the DES bridge as a fake provider)
     sample_matrices(gen, n_samples)                               (this build: the batched form of generate_song)
     train(...)  /  python -m gan_des_midi_music_gen_amd.SIMNN     SIMNN.py:234-348 (the __main__ loop)
 
@@ -163,7 +163,8 @@ def generate_song(model_folder, device=None, bridge=None, compute_dtype=None, *,
     (matrix_sim_process.matrix_to_wav(simulate="des"): DES core, log -> notes, integer synth, mel) -- the (128, 216) dB
     spectrogram tensor is returned, as upstream; ``midi_path`` / ``wav_path`` also write the clip's MIDI file and its
     audio (mono 16-bit, 44 100 Hz, rendered on the device in bounded chunks; ``max_seconds`` cuts it; a blank clip is
-    the reference's five seconds of silence).  bridge=callable continues from the (20,20) numpy matrix; with no bridge
+    the reference's five seconds of silence).  bridge="des_batch": the same with the simulation on the device
+    (matrix_to_wav(simulate="des_batch"); see matrix_sim_process for what differs).  bridge=callable continues from the (20,20) numpy matrix; with no bridge
     the matrix is returned.
     compute_dtype: None (the process default, exact fp32 unless changed) or "bf16" (the one-launch eval kernel).
     """
@@ -173,9 +174,9 @@ def generate_song(model_folder, device=None, bridge=None, compute_dtype=None, *,
     with torch.no_grad():
         generated = gen(get_noise(1, 100, device=device)).detach()
     if isinstance(bridge, str):
-        if bridge != "des":
-            raise ValueError(f"unknown bridge {bridge!r} (the built-in one is \"des\")")
-        return _des_song(generated.reshape(1, 20, 20), midi_path, wav_path, max_seconds)
+        if bridge not in ("des", "des_batch"):
+            raise ValueError(f"unknown bridge {bridge!r} (the built-in ones are \"des\" and \"des_batch\")")
+        return _des_song(generated.reshape(1, 20, 20), midi_path, wav_path, max_seconds, batched=bridge == "des_batch")
     adj = generated.squeeze().cpu().numpy()
     return bridge(adj) if bridge is not None else adj
 
@@ -183,13 +184,17 @@ def generate_song(model_folder, device=None, bridge=None, compute_dtype=None, *,
 _WAV_CHUNK = 1 << 22          # samples rendered per gdm_synth_pcm launch (8 MB of PCM)
 
 
-def _des_song(matrix, midi_path, wav_path, max_seconds):
-    """matrix_to_wav(simulate="des") for one matrix, keeping the note list for the two files."""
+def _des_song(matrix, midi_path, wav_path, max_seconds, batched=False):
+    """matrix_to_wav(simulate="des" / "des_batch") for one matrix, keeping the note list for the two files."""
     import struct
     from . import matrix_sim_process as msp, ops, sim_log_process_music as slpm, sim_log_to_midi
-    h = msp._wav_scan(matrix, 20)
-    specs = msp._interleaved_specs(h, msp._wav_draws, lambda h_, i, r, src, sd: msp._wav_spec(h_, i, r, src, sd, None))
-    mel, (notes, n_notes, clip_len) = msp._specs_to_mel(specs, matrix.device, 200000)
+    if batched:
+        mel, (notes, n_notes, clip_len) = msp._batch_to_mel(msp.batched_prologue_wav(matrix, 20, None), 200000)
+    else:
+        h = msp._wav_scan(matrix, 20)
+        specs = msp._interleaved_specs(h, msp._wav_draws,
+                                       lambda h_, i, r, src, sd: msp._wav_spec(h_, i, r, src, sd, None))
+        mel, (notes, n_notes, clip_len) = msp._specs_to_mel(specs, matrix.device, 200000)
     if midi_path is not None:
         sim_log_to_midi.write_midi(slpm.notes_to_track(notes[0, :int(n_notes[0])].cpu().numpy()), midi_path)
     if wav_path is not None:
@@ -214,13 +219,15 @@ def _des_song(matrix, midi_path, wav_path, max_seconds):
     return mel[0]
 
 
-def des_fake_provider(start=0, end=216, max_events=200000):
+def des_fake_provider(start=0, end=216, max_events=200000, batched=False):
     """The built-in DES bridge as the ``fake`` callable of ``SimnnTrainer.step`` / ``train(fake_provider=...)``:
-    generated (B,1,20,20) device tensor -> (B,128,end-start) dB tensor on the same device (SIMNN.py:301)."""
+    generated (B,1,20,20) device tensor -> (B,128,end-start) dB tensor on the same device (SIMNN.py:301).
+    batched: simulate on the device (matrix_to_wav(simulate="des_batch"))."""
     from . import matrix_sim_process as msp
+    simulate = "des_batch" if batched else "des"
 
     def provider(generated):
-        return msp.matrix_to_wav(generated, start=start, end=end, device=generated.device, simulate="des",
+        return msp.matrix_to_wav(generated, start=start, end=end, device=generated.device, simulate=simulate,
                                  max_events=max_events)
     return provider
 
@@ -281,7 +288,8 @@ def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5,
     fake_provider(generated (B,1,20,20) device tensor) -> (B,H,W) tensor: stands in for the DES/FluidSynth bridge
         ``matrix_to_wav`` (SIMNN.py:301); "des": the built-in bridge (``des_fake_provider(0, input_hw[1])``; it needs
         ``input_hw[1] <= 216`` frames, the reference's ``start=0, end=216`` by default); if None, seeded synthetic
-        windows are used.
+        windows are used.  "des_batch": the same bridge with the simulation on the device, one launch per batch
+        (``des_fake_provider(0, input_hw[1], batched=True)``; matrix_sim_process lists what differs from "des").
     Returns (gen, disc, gen_losses, disc_losses).
     """
     from .train import SimnnTrainer
@@ -299,11 +307,13 @@ def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5,
     elif input_hw is None:
         input_hw = (128, 216)
     if isinstance(fake_provider, str):
-        if fake_provider != "des":
-            raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in one is \"des\")")
+        if fake_provider not in ("des", "des_batch"):
+            raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in ones are \"des\" and "
+                             "\"des_batch\")")
         if input_hw[0] != 128 or not 0 < input_hw[1] <= 216:
-            raise ValueError(f"fake_provider=\"des\" makes (128, end - start <= 216) windows, input_hw is {tuple(input_hw)}")
-        fake_provider = des_fake_provider(0, input_hw[1])
+            raise ValueError(f"fake_provider=\"{fake_provider}\" makes (128, end - start <= 216) windows, input_hw is "
+                             f"{tuple(input_hw)}")
+        fake_provider = des_fake_provider(0, input_hw[1], batched=fake_provider == "des_batch")
     if seed is not None:
         torch.manual_seed(seed)
     gen = Generator().to(device)
@@ -346,7 +356,8 @@ def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5,
     return gen, disc, gen_losses, disc_losses
 
 
-if __name__ == "__main__":
+def main(argv=None):
+    """``python -m gan_des_midi_music_gen_amd.SIMNN``: the reference's ``__main__`` training loop."""
     import argparse
     ap = argparse.ArgumentParser(description="Train model 1 (the reference's SIMNN.py __main__ loop).")
     ap.add_argument("--audio-file", default=None, help="WAV file to train on (default: seeded synthetic windows)")
@@ -354,8 +365,13 @@ if __name__ == "__main__":
     ap.add_argument("--batch-size", type=int, default=30)
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--no-save", action="store_true", help="write no generator checkpoints")
-    ap.add_argument("--fake-provider", choices=["des"], default=None,
-                    help="des: fakes from the built-in DES bridge (default: seeded synthetic windows)")
-    a = ap.parse_args()
+    ap.add_argument("--fake-provider", choices=["des", "des_batch"], default=None,
+                    help="des: fakes from the built-in DES bridge; des_batch: the same with the simulation batched on "
+                         "the device (default: seeded synthetic windows)")
+    a = ap.parse_args(argv)
     train(audio_file=a.audio_file, n_epochs=a.epochs, batch_size=a.batch_size, max_steps=a.max_steps,
           save=not a.no_save, fake_provider=a.fake_provider)
+
+
+if __name__ == "__main__":
+    main()

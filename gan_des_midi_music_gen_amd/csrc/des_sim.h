@@ -1,0 +1,523 @@
+// The event logic of the queueing-network discrete-event simulator (SIMULATOR/simulation_v3.py: Sim.run 426-516,
+// Initialization 518-534, ProcessArrival 536-588, ScheduleDeparture 591-612, ProcessDeparture 615-677, get_destination
+// 699-743, FlowBranchOperator 25-74), ONE source for the host core (gdm_des_run, des_core.hip), the host batch mirror
+// (gdm_des_run_batch_host) and the device kernel (des_batch.hip).  Compiles as host code, as gfx950 device code and as
+// plain C++ without any HIP include.
+//
+// What is reproduced bit for bit (tests/golden/des_core.npz pins it through gdm_des_run):
+//   * numpy's legacy MT19937 RandomState: per-node generators seeded from RandomState(seed).randint(3, 9999999), and the
+//     GLOBAL np.random stream FlowBranchOperator.randomly_select_child draws from (simulation_v3.py:57,62),
+//   * scipy.stats.norm(loc, scale).rvs(random_state=rng) = rng.standard_normal() * scale + loc (legacy polar gauss),
+//   * Python's heapq order for simultaneous events (Event.__lt__ compares times only).
+//
+// Storage is the caller's, with capacities that follow from the spec (nothing grows):
+//   event list   at most one pending arrival per source and one departure per server: dim entries (+1)
+//   FIFO rings   ring_stride customer ids per server; admission keeps a queue below queue_cap[node], so a stride of
+//                max(queue_cap) is never exceeded (only the id of a queued event is ever read back)
+//   routing      children / cdf per node, dim entries each, computed once with the operations (and their order) of
+//                FlowBranchOperator.__init__ and numpy's legacy choice(p=...)
+//   generators   dim node states + the global one + the seeder, 624 words each
+// Every capacity is checked where it is used and every index that was computed from data is checked before it forms an
+// address; an overrun ends the sample with DES_STOP_ERROR.
+//
+// Every loop is bounded: each 32-bit generator draw counts against `draws_left`.  The batch entries set it to
+// DES_DRAW_FACTOR * (max_events + dim + 1): a healthy event makes at most one service draw, one inter-arrival draw and
+// one routing draw, about 10 words on average (a polar pair costs 4 words per attempt, accepted with p = pi/4), so 64
+// per event is out of reach of a healthy run and stops `while service <= 0` for loc << 0 after a bounded time
+// (DES_STOP_BUDGET).  gdm_des_run passes INT64_MAX: today's behaviour.
+//
+// Math is a policy (template parameter): log / sqrt of the polar method.  DesMathPortable is plain double arithmetic
+// (+ - * / and bit manipulation, contraction off, no FMA) and gives the same bits on the host and on gfx950; the host
+// core of gdm_des_run uses libm's (what numpy calls), which no portable implementation can match bit for bit.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define DES_HD __host__ __device__
+#else
+#define DES_HD
+#endif
+
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+
+#define DES_STOP_EMPTY 0      /* event list empty */
+#define DES_STOP_CUSTOMERS 1  /* number_of_customers reached */
+#define DES_STOP_EVENTS 2     /* max_events processed */
+#define DES_STOP_ERROR 3      /* bad spec, no destination, customer routed to a source, capacity overrun */
+#define DES_STOP_RECORDS 4    /* max_records written */
+#define DES_STOP_BUDGET 5     /* draw budget exhausted */
+#define DES_DRAW_FACTOR 64
+#define DES_MT_N 624
+
+namespace des {
+
+DES_HD inline uint64_t bits_of(double x) {
+  uint64_t u;
+  __builtin_memcpy(&u, &x, 8);
+  return u;
+}
+DES_HD inline double double_of(uint64_t u) {
+  double x;
+  __builtin_memcpy(&x, &u, 8);
+  return x;
+}
+
+// Natural logarithm in the form of fdlibm's e_log.c (argument reduction x = 2^k (1 + f), sqrt(1/2) < 1 + f < sqrt(2);
+// log(1 + f) = 2s + s R(s^2), s = f / (2 + f), R a degree-14 minimax polynomial; below 1 ulp).  Only + - * / on
+// doubles and integer work on the bit pattern: with contraction off every operation is one IEEE operation.
+DES_HD inline double des_log(double x) {
+  const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10, two54 = 1.80143985094819840000e+16,
+               Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
+               Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
+               Lg7 = 1.479819860511658591e-01;
+  uint64_t u = bits_of(x);
+  int32_t hx = (int32_t)(u >> 32);
+  const uint32_t lx = (uint32_t)u;
+  int32_t k = 0;
+  if (hx < 0x00100000) {                                              // x < 2^-1022
+    if (((hx & 0x7fffffff) | lx) == 0) return double_of(0xfff0000000000000ULL);      // log(+-0) = -inf
+    if (hx < 0) return double_of(0x7ff8000000000000ULL);                             // log(-#) = NaN
+    k -= 54;
+    x *= two54;
+    u = bits_of(x);
+    hx = (int32_t)(u >> 32);
+  }
+  if (hx >= 0x7ff00000) return x + x;
+  k += (hx >> 20) - 1023;
+  hx &= 0x000fffff;
+  const int32_t i0 = (hx + 0x95f64) & 0x100000;
+  u = (u & 0xffffffffULL) | ((uint64_t)(uint32_t)(hx | (i0 ^ 0x3ff00000)) << 32);     // normalise x or x / 2
+  x = double_of(u);
+  k += i0 >> 20;
+  const double f = x - 1.0;
+  const double dk = (double)k;
+  if ((0x000fffff & (2 + hx)) < 3) {                                  // |f| < 2^-20
+    if (f == 0.0) return k == 0 ? 0.0 : dk * ln2_hi + dk * ln2_lo;
+    const double R = f * f * (0.5 - 0.33333333333333333 * f);
+    return k == 0 ? f - R : dk * ln2_hi - ((R - dk * ln2_lo) - f);
+  }
+  const double s = f / (2.0 + f);
+  const double z = s * s;
+  int32_t i = hx - 0x6147a;
+  const double w = z * z;
+  const int32_t j = 0x6b851 - hx;
+  const double t1 = w * (Lg2 + w * (Lg4 + w * Lg6));
+  const double t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)));
+  i |= j;
+  const double R = t2 + t1;
+  if (i > 0) {
+    const double hfsq = 0.5 * f * f;
+    return k == 0 ? f - (hfsq - s * (hfsq + R)) : dk * ln2_hi - ((hfsq - (s * (hfsq + R) + dk * ln2_lo)) - f);
+  }
+  return k == 0 ? f - s * (f - R) : dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f);
+}
+
+// The portable policy.  sqrt is the compiler's IEEE square root: one correctly rounded instruction on x86-64 and the
+// correctly rounded expansion of llvm.sqrt.f64 on gfx950 (tests/test_des_batch_gpu.py compares the two bit for bit).
+struct MathPortable {
+  DES_HD static double log(double x) { return des_log(x); }
+  DES_HD static double sqrt(double x) { return __builtin_sqrt(x); }
+};
+
+// ---- routing table of one node (FlowBranchOperator.__init__, simulation_v3.py:25-74, and the cdf numpy's legacy
+// choice(children, p=...) builds on every call: p.cumsum(); cdf /= cdf[-1]) ----------------------------------------------
+#define DES_BRANCH_UNIFORM 1  /* sum(probabilities) != 1 -> np.random.choice(children) without p (56-58) */
+#define DES_BRANCH_SINK 2     /* sum(children) == 0 (73): also true when the only destination is node 0 */
+DES_HD inline void make_branch(const double* row, int dim, int self, int32_t* children, double* cdf, int32_t* n_out,
+                               uint8_t* flags_out) {
+  int n = 0;
+  for (int j = 0; j < dim; ++j) {
+    const double pj = (j == self) ? 0.0 : row[j];
+    if (pj > 0) {                                      // children / probabilities with non-zero probability (38-40)
+      children[n] = j;
+      cdf[n] = pj;
+      ++n;
+    }
+  }
+  double s = 0.0;                                      // Python sum(): left to right, starting from int 0
+  for (int i = 0; i < n; ++i) s += cdf[i];
+  for (int i = 0; i < n; ++i) cdf[i] = cdf[i] / s;     // line 47 (sum() of the un-normalised list every time)
+  double s1 = 0.0;
+  for (int i = 0; i < n; ++i) s1 += cdf[i];
+  long cs = 0;
+  for (int i = 0; i < n; ++i) cs += children[i];
+  double acc = 0.0;                                    // cumsum
+  for (int i = 0; i < n; ++i) {
+    acc += cdf[i];
+    cdf[i] = acc;
+  }
+  if (n > 0) {
+    const double last = cdf[n - 1];
+    for (int i = 0; i < n; ++i) cdf[i] /= last;
+  }
+  *n_out = n;
+  *flags_out = (uint8_t)((s1 != 1.0 ? DES_BRANCH_UNIFORM : 0) | (cs == 0 ? DES_BRANCH_SINK : 0));
+}
+
+// init_genrand of mt19937_seed: the 624 words of RandomState(s); position 624, no cached gauss
+DES_HD inline void seed_key(uint32_t* key, uint32_t s) {
+  for (int i = 0; i < DES_MT_N; ++i) {
+    key[i] = s;
+    s = 1812433253u * (s ^ (s >> 30)) + (uint32_t)(i + 1);
+  }
+}
+
+struct Ev {
+  double time;
+  int64_t id;
+  int32_t type;            // 1 arrival, 2 departure
+  int32_t server;
+  int32_t source;          // -1 = None
+  int32_t pad;
+};
+
+// Record sinks: array of gdm_des_event-shaped structs (gdm_des_run) or the four field arrays of the CSR layout
+struct OutAos {
+  struct Rec {
+    double value;
+    int64_t event_id;
+    int32_t node;
+    int32_t kind;
+  };
+  Rec* out;
+  DES_HD void put(int64_t i, double v, int64_t id, int node, int kind) const { out[i] = Rec{v, id, node, kind}; }
+};
+struct OutSoa {
+  double* value;
+  int64_t* event_id;
+  int32_t* node;
+  int32_t* kind;
+  DES_HD void put(int64_t i, double v, int64_t id, int nd, int kd) const {
+    value[i] = v;
+    event_id[i] = id;
+    node[i] = (int32_t)nd;
+    kind[i] = (int32_t)kd;
+  }
+};
+
+template <class Math, class Out>
+struct Sim {
+  // ---- storage, set by the caller ----
+  int dim;
+  const double* loc;          // (dim)
+  const double* scale;        // (dim)
+  const int32_t* qcap;        // (dim)
+  uint8_t* is_source;         // (dim)
+  int32_t* in_service;        // (dim)
+  int32_t* qhead;             // (dim)
+  int32_t* qlen;              // (dim)
+  int32_t* nchild;            // (dim)
+  uint8_t* bflags;            // (dim)
+  int32_t* children;          // (dim, dim)
+  double* cdf;                // (dim, dim)
+  int64_t* ring;              // (dim, ring_stride)
+  int64_t ring_stride;
+  uint32_t* node_keys;        // (dim, 624)
+  uint32_t* global_key;       // (624)
+  uint32_t* seeder_key;       // (624)
+  int32_t* pos;               // (dim + 2): nodes, global (index dim), seeder (dim + 1)
+  int32_t* has_gauss;         // (dim + 2)
+  double* gauss;              // (dim + 2)
+  Ev* heap;
+  int heap_cap;
+  Out out;
+  int64_t out_cap;
+  int64_t max_records;        // 0 = no cap
+  int64_t draws_left;
+  // ---- run state ----
+  int heap_n;
+  int64_t n_out;
+  double clock;
+  int64_t total_customers;
+  int stop;                   // 0 while running, else a DES_STOP_* code that ends the sample
+  bool overflow;              // records were dropped beyond out_cap (n_out keeps counting)
+
+  DES_HD void reset() {
+    heap_n = 0;
+    n_out = 0;
+    clock = 0.0;
+    total_customers = 0;
+    stop = 0;
+    overflow = false;
+  }
+  DES_HD void fail() {
+    if (!stop) stop = DES_STOP_ERROR;
+  }
+  DES_HD uint32_t* key_of(int g) const {
+    return g < dim ? node_keys + (int64_t)g * DES_MT_N : (g == dim ? global_key : seeder_key);
+  }
+
+  // ---- numpy.random.RandomState (legacy) ----
+  DES_HD static void twist(uint32_t* key) {
+    const uint32_t UPPER = 0x80000000u, LOWER = 0x7fffffffu, MAT = 0x9908b0dfu;
+    int i;
+    uint32_t y;
+    for (i = 0; i < 624 - 397; ++i) {
+      y = (key[i] & UPPER) | (key[i + 1] & LOWER);
+      key[i] = key[i + 397] ^ (y >> 1) ^ (-(int32_t)(y & 1) & MAT);
+    }
+    for (; i < 623; ++i) {
+      y = (key[i] & UPPER) | (key[i + 1] & LOWER);
+      key[i] = key[i + (397 - 624)] ^ (y >> 1) ^ (-(int32_t)(y & 1) & MAT);
+    }
+    y = (key[623] & UPPER) | (key[0] & LOWER);
+    key[623] = key[396] ^ (y >> 1) ^ (-(int32_t)(y & 1) & MAT);
+  }
+  DES_HD uint32_t next32(int g) {
+    if (draws_left <= 0) {
+      if (!stop) stop = DES_STOP_BUDGET;
+      return 0;
+    }
+    --draws_left;
+    uint32_t* key = key_of(g);
+    uint32_t p = (uint32_t)pos[g];
+    if (p >= DES_MT_N) {                              // (an out-of-range position cannot form an address)
+      twist(key);
+      p = 0;
+    }
+    uint32_t y = key[p];
+    pos[g] = (int32_t)(p + 1);
+    y ^= (y >> 11);
+    y ^= (y << 7) & 0x9d2c5680u;
+    y ^= (y << 15) & 0xefc60000u;
+    y ^= (y >> 18);
+    return y;
+  }
+  DES_HD double next_double(int g) {                  // random_sample: 53 bits from two draws
+    const int32_t a = (int32_t)(next32(g) >> 5), b = (int32_t)(next32(g) >> 6);
+    return (a * 67108864.0 + b) / 9007199254740992.0;
+  }
+  // randint(low, high) for a range below 2^32: masked rejection on 32-bit draws (_bounded_integers, use_masked)
+  DES_HD int64_t randint(int g, int64_t low, int64_t high) {
+    const uint64_t rng = (uint64_t)(high - 1 - low);
+    if (rng == 0) return low;
+    uint32_t mask = (uint32_t)rng;
+    mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
+    uint32_t v;
+    do { v = next32(g) & mask; } while (v > (uint32_t)rng && !stop);
+    return low + (int64_t)v;
+  }
+  DES_HD double standard_normal(int g) {              // legacy_gauss: polar Box-Muller with one cached value
+    if (has_gauss[g]) {
+      const double t = gauss[g];
+      has_gauss[g] = 0;
+      gauss[g] = 0.0;
+      return t;
+    }
+    double f, x1, x2, r2;
+    do {
+      x1 = 2.0 * next_double(g) - 1.0;
+      x2 = 2.0 * next_double(g) - 1.0;
+      r2 = x1 * x1 + x2 * x2;
+    } while ((r2 >= 1.0 || r2 == 0.0) && !stop);
+    if (stop) return 0.0;
+    f = Math::sqrt(-2.0 * Math::log(r2) / r2);
+    gauss[g] = f * x1;
+    has_gauss[g] = 1;
+    return f * x2;
+  }
+  // scipy.stats.norm(loc, scale).rvs(random_state=rng): no draw at all when scale == 0
+  DES_HD double norm_rvs(int node) {
+    if (scale[node] == 0.0) return loc[node];
+    const double z = standard_normal(node);
+    return z * scale[node] + loc[node];
+  }
+
+  // ---- setup ----
+  // source flags, routing tables and idle servers for nodes [first, dim) in steps of `step` (one lane per node on the
+  // device); a negative scale (scipy: "Domain error in arguments") ends the sample
+  DES_HD void setup_nodes(const double* adj, int first, int step) {
+    for (int i = first; i < dim; i += step) {
+      is_source[i] = adj[(int64_t)i * dim + i] > 0;    // sources: diagonal > 0; servers: diagonal <= 0 (363, 379)
+      make_branch(adj + (int64_t)i * dim, dim, i, children + (int64_t)i * dim, cdf + (int64_t)i * dim, &nchild[i],
+                  &bflags[i]);
+      in_service[i] = 0;
+      qhead[i] = 0;
+      qlen[i] = 0;
+    }
+  }
+  // what the batch entries require of one sample before anything runs (a refused sample stops with DES_STOP_ERROR and
+  // leaves the generator state as it came): scale >= 0, every queue fits its ring, a 32-bit seed, a valid position
+  DES_HD bool spec_ok(int64_t seed, int32_t global_pos) const {
+    if (seed < 0 || seed > 0xffffffffLL || global_pos < 0 || global_pos > DES_MT_N) return false;
+    for (int i = 0; i < dim; ++i)
+      if (!(scale[i] >= 0) || (int64_t)qcap[i] > ring_stride) return false;
+    return true;
+  }
+  // per-node generator seeds (451-461): servers first, then sources, each in ascending node order
+  DES_HD void draw_node_seeds(uint32_t seed, uint32_t* node_seed) {
+    const int g = dim + 1;
+    seed_key(seeder_key, seed);
+    pos[g] = DES_MT_N;
+    has_gauss[g] = 0;
+    gauss[g] = 0.0;
+    for (int pass = 0; pass < 2; ++pass)
+      for (int i = 0; i < dim; ++i)
+        if ((is_source[i] != 0) == (pass == 1)) node_seed[i] = (uint32_t)randint(g, 3, 9999999);
+  }
+  DES_HD void seed_nodes(const uint32_t* node_seed, int first, int step) {
+    for (int i = first; i < dim; i += step) {
+      seed_key(node_keys + (int64_t)i * DES_MT_N, node_seed[i]);
+      pos[i] = DES_MT_N;
+      has_gauss[i] = 0;
+      gauss[i] = 0.0;
+    }
+  }
+
+  // ---- Python's heapq ----
+  DES_HD void push(const Ev& e) {                      // heappush = append + _siftdown(heap, 0, len - 1)
+    if (heap_n >= heap_cap) { fail(); return; }
+    int p = heap_n++;
+    while (p > 0) {
+      const int parent = (p - 1) >> 1;
+      if (e.time < heap[parent].time) { heap[p] = heap[parent]; p = parent; continue; }
+      break;
+    }
+    heap[p] = e;
+  }
+  DES_HD Ev pop() {                                    // heappop: last element to the root, _siftup, then _siftdown
+    const Ev last = heap[--heap_n];
+    if (heap_n == 0) return last;
+    const Ev ret = heap[0];
+    const int end = heap_n;
+    int p = 0, child = 1;
+    while (child < end) {
+      const int right = child + 1;
+      if (right < end && !(heap[child].time < heap[right].time)) child = right;
+      heap[p] = heap[child];
+      p = child;
+      child = 2 * p + 1;
+    }
+    while (p > 0) {                                    // _siftdown(heap, 0, pos)
+      const int parent = (p - 1) >> 1;
+      if (last.time < heap[parent].time) { heap[p] = heap[parent]; p = parent; continue; }
+      break;
+    }
+    heap[p] = last;
+    return ret;
+  }
+
+  // ---- the simulation ----
+  DES_HD void log(double v, int64_t id, int node, int kind) {
+    if (n_out < out_cap) out.put(n_out, v, id, node, kind);
+    else overflow = true;
+    ++n_out;
+    if (max_records > 0 && n_out >= max_records && !stop) stop = DES_STOP_RECORDS;
+  }
+  // np.random.choice(children[, p]) on the GLOBAL legacy stream; -1 = a sink-like server (get_destination, 699-743)
+  DES_HD int destination(int id) {
+    if (!is_source[id] && (bflags[id] & DES_BRANCH_SINK)) return -1;
+    const int n = nchild[id];
+    if (n <= 0 || n > dim) { fail(); return -1; }      // "No children available" / np.random.choice([]) raises
+    const int32_t* ch = children + (int64_t)id * dim;
+    if (bflags[id] & DES_BRANCH_UNIFORM) {
+      const int64_t k = randint(dim, 0, n);
+      if (stop || k < 0 || k >= n) { fail(); return -1; }
+      return ch[k];
+    }
+    // legacy choice with p: searchsorted(cdf, random_sample(), side='right')
+    const double* c = cdf + (int64_t)id * dim;
+    const double u = next_double(dim);
+    if (stop) return -1;
+    int lo = 0, hi = n;                                // first index with cdf[i] > u
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (c[mid] <= u) lo = mid + 1; else hi = mid;
+    }
+    return ch[lo < n ? lo : n - 1];
+  }
+  DES_HD void schedule_departure(int server_id, int64_t event_id) {     // 591-612
+    in_service[server_id] = 1;
+    double service = 0.0;
+    if (scale[server_id] == 0.0 && loc[server_id] <= 0.0) { fail(); return; }   // upstream: the loop never ends
+    while (service <= 0 && !stop) service = norm_rvs(server_id);
+    if (stop) return;
+    log(service, event_id, server_id, 2);
+    if (stop) return;
+    push(Ev{clock + service, event_id, 2, server_id, -1, 0});
+  }
+  DES_HD void process_arrival(int server_id, int source, int64_t id) {  // 536-588
+    log(clock, id, server_id, 0);
+    if (stop) return;
+    if (server_id < 0 || server_id >= dim || is_source[server_id]) { fail(); return; }    // KeyError upstream
+    if (in_service[server_id] == 0) {
+      schedule_departure(server_id, id);
+      if (stop) return;
+    } else if ((int64_t)qlen[server_id] < (int64_t)qcap[server_id]) {
+      const int64_t n = qlen[server_id];
+      if (n < 0 || n >= ring_stride) { fail(); return; }
+      int64_t slot = (int64_t)qhead[server_id] + n;
+      if (slot >= ring_stride) slot -= ring_stride;
+      if (slot < 0 || slot >= ring_stride) { fail(); return; }
+      ring[(int64_t)server_id * ring_stride + slot] = id;
+      qlen[server_id] = (int32_t)(n + 1);
+    }                                                  // else: the customer reneges
+    if (source >= 0) {
+      const double dt = norm_rvs(source);
+      if (stop) return;
+      push(Ev{clock + dt, total_customers, 1, server_id, source, 0});
+      ++total_customers;
+    }
+  }
+  DES_HD void process_departure(int server_id, int64_t id) {            // 615-677
+    log(clock, id, server_id, 1);
+    if (stop) return;
+    if (server_id < 0 || server_id >= dim) { fail(); return; }
+    int next = destination(server_id);
+    if (stop) return;
+    const bool sink = (bflags[server_id] & DES_BRANCH_SINK) != 0;
+    if (next < 0) {                                    // sink-like node: first idle child that is a server (628-633)
+      const int32_t* ch = children + (int64_t)server_id * dim;
+      const int n = nchild[server_id] < dim ? nchild[server_id] : dim;
+      for (int k = 0; k < n; ++k) {
+        const int c = ch[k];
+        if (c >= 0 && c < dim && !is_source[c] && in_service[c] == 0) { next = c; break; }
+      }
+    }
+    if (next >= 0 || sink) {
+      if (qlen[server_id] > 0) {
+        const int64_t h = qhead[server_id];
+        if (h < 0 || h >= ring_stride) { fail(); return; }
+        const int64_t customer = ring[(int64_t)server_id * ring_stride + h];
+        qhead[server_id] = (int32_t)(h + 1 >= ring_stride ? 0 : h + 1);
+        --qlen[server_id];
+        schedule_departure(server_id, customer);
+        if (stop) return;
+      } else {
+        in_service[server_id] = 0;
+      }
+      if (!sink) process_arrival(next, -1, id);
+    } else {
+      fail();                                          // queue-type nodes (delayed departures): not produced by the bridges
+    }
+  }
+
+  // Initialization (518-534) and the event loop (463-516).  Node tables and generators are set up; returns the stop
+  // reason.  max_events <= 0: no event cap (gdm_des_run only).
+  DES_HD int run(int64_t number_of_customers, int64_t max_events) {
+    for (int i = 0; i < dim && !stop; ++i) {
+      if (!is_source[i]) continue;
+      const double dt = norm_rvs(i);
+      if (stop) break;
+      const int next = destination(i);
+      if (stop) break;
+      push(Ev{clock + dt, total_customers, 1, next, i, 0});
+      ++total_customers;
+    }
+    int reason = DES_STOP_EMPTY;
+    int64_t processed = 0;
+    while (!stop && heap_n > 0) {
+      const Ev evt = pop();
+      if (total_customers > number_of_customers - 1) { reason = DES_STOP_CUSTOMERS; break; }
+      clock = evt.time;
+      if (evt.type == 1) process_arrival(evt.server, evt.source, evt.id);
+      else process_departure(evt.server, evt.id);
+      if (++processed >= max_events && max_events > 0) { reason = DES_STOP_EVENTS; break; }   // (reference: wall clock)
+    }
+    return stop ? stop : reason;
+  }
+};
+
+}  // namespace des

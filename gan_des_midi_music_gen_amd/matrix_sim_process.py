@@ -33,6 +33,23 @@ that leaves numpy's global stream alone.  Reference quirks kept: matrix_to_midi 
 sources (its emptiness test at line 42 is always true); matrix_to_wav raises ValueError for more than one thresholded
 source (line 30) and IndexError for a thresholded column >= dim (line 67); an all-zero row raises ValueError from
 ``np.random.choice([])``.
+
+simulate="des_batch" (opt-in; "des" is unchanged) batches the one stage "des" leaves per sample and on the host: the
+batched prologue (``batched_prologue_midi`` / ``batched_prologue_wav``: one scan launch, ALL host draws in the
+reference's order with a snapshot of ``np.random.get_state()`` after each sample's reseed, one routing launch whose
+output stays on the device), then ``gdm_des_run_batch`` (one wave per sample, csrc/des_batch.hip) simulates every
+sample from ITS snapshot, and the batched consumers read the device log in place.  Below DES_BATCH_DEVICE_MIN_B samples
+the host mirror ``gdm_des_run_batch_host`` simulates instead -- the same source compiled for the host, the same bits --
+because the launch costs 8-10 ms however small the batch is.  Four differences from "des":
+  1. order: all draws come first, then all simulations -- sample i+1's draws no longer continue from where simulation i
+     left numpy's global stream, they continue from sample i's reseed.  Each sample is still simulated exactly as the
+     reference would simulate it from the state it is given;
+  2. last bits: the device has no libm, so ``log`` is the portable one of csrc/des_sim.h -- same events, ids, nodes,
+     kinds and ``floor(value)`` on the golden runs, values within 7.7e-14 relative (DESIGN.md section 7);
+  3. record cap: a simulation stops once 5001 records are written (both consumers look at the first 5000 and count up
+     to 5001 lines), so ``max_events`` is rarely reached;
+  4. final stream position: after the call numpy's global stream is where the batched prologue left it (where
+     ``midi_prologue`` / ``wav_prologue`` leave it), not where the last simulation would have.
 """
 from dataclasses import dataclass, field
 
@@ -137,6 +154,89 @@ def _batched_specs(h, draws, spec_of):
     return [spec_of(h, i, routing[i], src_all[i], seeds[i]) for i in range(b)]
 
 
+# "des_batch" simulates on the device from this batch size on and with the host mirror below it.  The two give the same
+# bits, so the choice is one of speed only: the launch takes 8-10 ms whatever B is (one wave per sample, a latency-bound
+# chain), the sequential host mirror 0.15 ms (15 nodes) to 0.22 ms (61 nodes) per sample plus the transfers of the
+# routing matrices and the logs -- measured crossover B = 45-55.
+DES_BATCH_DEVICE_MIN_B = 48
+
+
+class BatchedPrologue:
+    """What the batched prologue leaves, each product where its consumer needs it: ``routing`` (B,dim,dim) fp64 on the
+    device; ``loc``, ``scale`` (B,dim) f64, ``queue_cap`` (B,dim) i32, ``seed``, ``customers`` (B) i64, ``instruments``,
+    ``note_levels`` (B,dim) i32 on the host (built with the float32 arithmetic of ``_midi_spec`` / ``_wav_spec``);
+    ``states``: the B snapshots of ``np.random.get_state()`` taken right after each sample's reseed; ``h``: the scan."""
+
+    def __init__(self, h, routing, src, seeds, states, spec_of):
+        self.h, self.routing, self.states = h, routing, states
+        self._src, self._seeds, self._spec_of = src, seeds, spec_of
+        heads = [spec_of(h, i, None, src[i], seeds[i]) for i in range(h["b"])]       # the per-node parameters
+        self.loc = np.ascontiguousarray([[float(d[1]) for d in sp.distributions] for sp in heads], dtype=np.float64)
+        self.scale = np.ascontiguousarray([[float(d[2]) for d in sp.distributions] for sp in heads], dtype=np.float64)
+        self.queue_cap = np.ascontiguousarray([sp.queue_list for sp in heads], dtype=np.int32)
+        self.seed = np.ascontiguousarray([int(np.asarray(sp.seeds).reshape(-1)[0]) for sp in heads], dtype=np.int64)
+        self.customers = np.ascontiguousarray([sp.num_customers for sp in heads], dtype=np.int64)
+        self.instruments = np.ascontiguousarray([[int(x) for x in sp.instruments] for sp in heads], dtype=np.int32)
+        self.note_levels = np.ascontiguousarray([[int(x) for x in sp.note_levels] for sp in heads], dtype=np.int32)
+
+    def specs(self):
+        """The DesSpecs ``midi_prologue`` / ``wav_prologue`` return (downloads the routing matrices)."""
+        routing = self.routing.cpu().numpy()
+        return [self._spec_of(self.h, i, routing[i], self._src[i], self._seeds[i]) for i in range(self.h["b"])]
+
+    def simulate(self, device, max_events=200000, max_records=5001):
+        """``gdm_des_run_batch`` (device: a HIP device) or the host mirror with portable math (device=None), every
+        sample from its snapshot -> simulation_v3.BatchLog."""
+        from . import simulation_v3
+        if device is None:
+            return simulation_v3.run_batch_host(self.routing.cpu().numpy(), self.loc, self.scale, self.queue_cap,
+                                                self.seed, self.customers, self.states, math=1, max_events=max_events,
+                                                max_records=max_records)
+        return simulation_v3.run_batch_device(self.routing, self.loc, self.scale, self.queue_cap, self.seed,
+                                              self.customers, self.states, device=device, max_events=max_events,
+                                              max_records=max_records, max_queue_cap=max(1, int(self.queue_cap.max())))
+
+
+    def simulate_on(self, device, max_events=200000, max_records=5001):
+        """``simulate`` for the bridges: a BatchLog of tensors on ``device`` either way -- from the kernel when the batch
+        holds at least DES_BATCH_DEVICE_MIN_B samples, else from the host mirror (same bits), uploaded once."""
+        from . import simulation_v3
+        if self.h["b"] >= DES_BATCH_DEVICE_MIN_B:
+            return self.simulate(device, max_events=max_events, max_records=max_records)
+        host = self.simulate(None, max_events=max_events, max_records=max_records)
+        dev = torch.device(device)
+        fields = [torch.from_numpy(np.ascontiguousarray(a.view(np.int32) if a.dtype == np.uint32 else a)).to(dev)
+                  for a in host]
+        return simulation_v3.BatchLog(*fields)
+
+
+def _batched_prologue(h, draws, spec_of):
+    b, dim = h["b"], h["dim"]
+    src_all = np.zeros((b, dim), dtype=bool)
+    cols_all = np.empty((b, dim), dtype=np.int32)
+    seeds, states = [], []
+    for i in range(b):                                                   # global-RNG order of the reference, per sample
+        src_all[i], cols_all[i], sd = draws(h, i)
+        seeds.append(sd)
+        states.append(np.random.get_state())                             # where simulation i starts
+    dev = h["g1"].device
+    routing = ops.des_routing(h["g1"], h["size"], dim, torch.from_numpy(src_all.astype(np.uint8)).to(dev),
+                              torch.from_numpy(cols_all).to(dev))
+    return BatchedPrologue(h, routing, src_all, seeds, states, spec_of)
+
+
+def batched_prologue_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None):
+    """``midi_prologue`` with its products left where "des_batch" needs them -> BatchedPrologue."""
+    h = _midi_scan(gen1_output, gen2_output, adj_size)
+    return _batched_prologue(h, _midi_draws, lambda h_, i, r, src, sd: _midi_spec(h_, i, r, src, sd, instrument))
+
+
+def batched_prologue_wav(matrices, size=20, use_same_instrument=None):
+    """``wav_prologue`` with its products left where "des_batch" needs them -> BatchedPrologue."""
+    h = _wav_scan(matrices, size)
+    return _batched_prologue(h, _wav_draws, lambda h_, i, r, src, sd: _wav_spec(h_, i, r, src, sd, use_same_instrument))
+
+
 def _interleaved_specs(h, draws, spec_of):
     """The reference's order: a sample's spec is complete (and handed to the caller, who simulates) before the next
     sample draws anything."""
@@ -168,6 +268,12 @@ def matrix_to_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None,
     the file upstream overwrites per sample).  The reference's 2.5 s wall-clock timeout has no counterpart: the core
     stops after ``max_events`` events instead.
 
+    simulate="des_batch": batched prologue, ONE device simulator launch for all B samples (each from its own snapshot
+    of numpy's stream, 5001-record cap), then the same ``des_log_to_roll`` launch fed from the device log; the save
+    flags come from the device counts, and the one read-back at the end brings the stop reasons with the tracks.  A
+    sample whose simulation errors (or exhausts its draw budget) counts as failed and keeps a zero roll.  See the
+    module docstring for the four differences from "des".
+
     Returns (list of (2,128,end-start) float64 arrays, failed_simulations); with ``return_tensor`` (built-in back end)
     the rolls stay on the device as one (B,2,128,end-start) fp32 tensor."""
     if simulate is None:
@@ -175,10 +281,12 @@ def matrix_to_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None,
                            "simulate=callable (it receives the DesSpec the reference would construct Sim from)")
     start, end = int(start), int(end)
     if isinstance(simulate, str):
-        if simulate != "des":
-            raise ops.GdmError(f"matrix_to_midi: unknown back end {simulate!r} (the built-in one is \"des\")")
-        return _matrix_to_midi_des(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor,
-                                   midi_path, max_events)
+        if simulate not in ("des", "des_batch"):
+            raise ops.GdmError(f"matrix_to_midi: unknown back end {simulate!r} (the built-in ones are \"des\" and "
+                               "\"des_batch\")")
+        back_end = _matrix_to_midi_des if simulate == "des" else _matrix_to_midi_des_batch
+        return back_end(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor, midi_path,
+                        max_events)
     if return_tensor:
         raise ops.GdmError("matrix_to_midi: return_tensor needs the built-in back end (simulate=\"des\")")
     h = _midi_scan(gen1_output, gen2_output, adj_size)
@@ -200,13 +308,7 @@ def matrix_to_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None,
 def _matrix_to_midi_des(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor, midi_path,
                         max_events):
     from . import sim_log_to_midi, simulation_v3
-    if end - start <= 0:
-        raise ValueError("negative dimensions are not allowed")          # np.zeros((2, 128, end - start)) upstream
-    if ops.des_roll_width(start, end) != end - start:
-        # generate_piano_roll's `[:, start:end]` of planes that are only end - start wide: upstream's assignment
-        # into the (2, 128, end - start) output fails to broadcast and the bare except re-raises ValueError
-        raise ValueError("Error in simulation thread, using blank piano roll instead. (start/end: the reference's "
-                         "final slice does not leave end - start columns; use start == 0 or end >= 128)")
+    _check_midi_window(start, end)
     h = _midi_scan(gen1_output, gen2_output, adj_size)
     if h["g2"].shape[1] < 16:
         raise ops.GdmError("matrix_to_midi: gen2_output needs at least 16 columns (gen2_output[10:16] drive the MIDI)")
@@ -233,6 +335,75 @@ def _matrix_to_midi_des(gen1_output, gen2_output, adj_size, instrument, start, e
     if return_tensor:
         return rolls, failed
     return [r for r in rolls.double().cpu().numpy()], failed
+
+
+def _check_midi_window(start, end):
+    if end - start <= 0:
+        raise ValueError("negative dimensions are not allowed")          # np.zeros((2, 128, end - start)) upstream
+    if ops.des_roll_width(start, end) != end - start:
+        # generate_piano_roll's `[:, start:end]` of planes that are only end - start wide: upstream's assignment
+        # into the (2, 128, end - start) output fails to broadcast and the bare except re-raises ValueError
+        raise ValueError("Error in simulation thread, using blank piano roll instead. (start/end: the reference's "
+                         "final slice does not leave end - start columns; use start == 0 or end >= 128)")
+
+
+def _matrix_to_midi_des_batch(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor,
+                              midi_path, max_events):
+    from . import sim_log_to_midi
+    _check_midi_window(start, end)
+    pro = batched_prologue_midi(gen1_output, gen2_output, adj_size, instrument)
+    h = pro.h
+    if h["g2"].shape[1] < 16:
+        raise ops.GdmError("matrix_to_midi: gen2_output needs at least 16 columns (gen2_output[10:16] drive the MIDI)")
+    dev = h["g1"].device
+    log = pro.simulate_on(dev, max_events=max_events, max_records=sim_log_to_midi.MAX_LINES + 1)
+    good = (log.stop_reason != ops.DES_STOP_ERROR) & (log.stop_reason != ops.DES_STOP_BUDGET)
+    lines = torch.clamp(log.n_records, max=sim_log_to_midi.MAX_LINES + 1)             # lines_read, on the device
+    save = (good & ((lines % 100 == 0) | bool(generate))).to(torch.int32)
+    tails = torch.from_numpy(np.ascontiguousarray(h["g2"][:, 10:])).to(dev)
+    planes, track, track_len, status = ops.des_log_to_roll(
+        log.value, log.event_id, log.node, log.kind, log.rec_ptr, tails, torch.from_numpy(pro.instruments).to(dev),
+        torch.from_numpy(pro.note_levels).to(dev), save, start, end)
+    # the one read-back: stop reasons with the tracks
+    words = torch.cat([status, track_len, good.to(torch.int32), save, track.reshape(-1)]).cpu().numpy()
+    b = h["b"]
+    status, track_len, good, save = words[:b], words[b:2 * b], words[2 * b:3 * b], words[3 * b:4 * b]
+    for i in range(b):
+        if status[i] >> 8:
+            raise ValueError(f"Error in processing log file (sample {i}: {ops.DES_MIDI_ERRORS[int(status[i]) >> 8]})")
+    failed = int(b - good.sum())
+    if generate:
+        done = np.flatnonzero(save)
+        if len(done):
+            last = int(done[-1])
+            tr = words[4 * b:].reshape(b, ops.DES_MIDI_TRACK_CAP, 4)[last, :track_len[last]]
+            sim_log_to_midi.write_midi(tr, midi_path or "adj_sim_outputs/midi/generation.mid")
+    if return_tensor:
+        return planes, failed
+    return [r for r in planes.double().cpu().numpy()], failed
+
+
+def _batch_to_mel(pro, max_events):
+    """The built-in batched back end behind matrix_to_wav: BatchedPrologue -> ((B, 128, 216) dB device tensor, (notes,
+    n_notes, clip_len) device tensors).  Simulator, log -> notes, synth and mel are enqueued without a read-back in
+    between; the status words and stop reasons come back once, and a sample the reference would raise for raises."""
+    from . import sim_log_process_music, util
+    dev = pro.h["g1"].device
+    log = pro.simulate_on(dev, max_events=max_events, max_records=sim_log_process_music.MAX_LINES + 1)
+    notes, n_notes, clip_len, status = ops.des_log_to_notes(log.value, log.event_id, log.node, log.kind, log.rec_ptr,
+                                                            torch.from_numpy(pro.note_levels).to(dev))
+    frames = ops.synth_frames(notes, n_notes, clip_len)
+    mel = util._db_from_frames(frames, pro.h["b"], ops.SYNTH_FRAMES, ops.SYNTH_RATE, ops.SYNTH_NFFT, 128, 20, 8300, 80)
+    words = torch.stack([status, log.stop_reason]).cpu()
+    for i, reason in enumerate(words[1].tolist()):
+        if reason in (ops.DES_STOP_ERROR, ops.DES_STOP_BUDGET):
+            from . import simulation_v3
+            raise ValueError(f"matrix_to_wav: the simulation of sample {i} stopped with "
+                             f"{simulation_v3.STOP_REASONS[reason]!r} (a node without destination, a customer routed "
+                             "to a source, or a service distribution that never turns positive; the reference raises "
+                             "or never returns)")
+    sim_log_process_music.raise_for_status(words[0])
+    return mel, (notes, n_notes, clip_len)
 
 
 def _wav_scan(matrices, size):
@@ -295,15 +466,23 @@ def matrix_to_wav(matrices, size=20, use_same_instrument=None, start=0, end=174,
     three batched device stages follow without a host round trip between them: log -> notes, notes -> the (B*216, 2048)
     STFT frame matrix of the integer synth, frames -> mel dB.  A clip without notes is the reference's "blank wav":
     -100 dB everywhere.  Exceptions of the prologue and of ``run_spec`` propagate (the reference has no ``try``
-    either).  The reference's 0.5 s wall-clock cap has no counterpart: the core stops after ``max_events`` events."""
+    either).  The reference's 0.5 s wall-clock cap has no counterpart: the core stops after ``max_events`` events.
+    simulate="des_batch": batched prologue, ONE device simulator launch for all B samples (each from its own snapshot
+    of numpy's stream, 5001-record cap), then the same three stages reading the device log in place.  A sample whose
+    simulation errors raises ValueError after all stages are enqueued (one read-back).  See the module docstring for
+    the four differences from "des"."""
     if simulate is None:
         raise ops.GdmError("matrix_to_wav: pass simulate=\"des\" for the built-in DES / synth back end or "
                            "simulate=callable (it receives the DesSpec the reference would construct Sim from)")
+    if isinstance(simulate, str) and simulate == "des_batch":
+        mel, _notes = _batch_to_mel(batched_prologue_wav(matrices, size, use_same_instrument), max_events)
+        return mel[:, :, start:end].to(device)
     h = _wav_scan(matrices, size)
     specs = _interleaved_specs(h, _wav_draws, lambda h_, i, r, src, sd: _wav_spec(h_, i, r, src, sd, use_same_instrument))
     if isinstance(simulate, str):
         if simulate != "des":
-            raise ops.GdmError(f"matrix_to_wav: unknown back end {simulate!r} (the built-in one is \"des\")")
+            raise ops.GdmError(f"matrix_to_wav: unknown back end {simulate!r} (the built-in ones are \"des\" and "
+                               "\"des_batch\")")
         mel, _notes = _specs_to_mel(specs, h["g1"].device, max_events)
         return mel[:, :, start:end].to(device)
     spectrograms = [torch.as_tensor(simulate(spec, index=i)) for i, spec in enumerate(specs)]

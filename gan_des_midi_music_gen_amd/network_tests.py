@@ -15,7 +15,8 @@ Module trees and state_dict keys equal the reference's (``gen.{i}.0`` = Linear, 
 ``conv1/conv2/fc``), so the committed ``mmgan_64_64_epoch_*.pth`` files load with ``strict=True``.  The nn children
 are parameter containers only; every forward runs through the HIP kernels of include/gdm.h.
 
-The DES bridge ``matrix_to_midi`` (network_tests.py:189) is opt-in: ``MultiModalGAN`` takes ``fake_provider="des"`` for
+The DES bridge ``matrix_to_midi`` (network_tests.py:189) is opt-in: ``MultiModalGAN`` takes ``fake_provider="des"`` (or
+"des_batch": the simulation batched on the device, matrix_to_midi(simulate="des_batch")) for
 the built-in bridge (matrix_sim_process.matrix_to_midi(simulate="des"): DES core + one batched log -> MIDI -> piano-roll
 launch) or an injected ``fake_provider(gen_output1, gen_output2, count) -> (rolls (B,2,128,T) tensor,
 failed_sim_count)``; without one, forward raises.
@@ -163,14 +164,16 @@ def _no_bridge(*_a, **_k):
                        "fake_provider=callable(gen_output1, gen_output2, count) -> (rolls, failed_sim_count)")
 
 
-def des_fake_provider(adj_size, instrument, start, end, generate=False, midi_path=None):
+def des_fake_provider(adj_size, instrument, start, end, generate=False, midi_path=None, batched=False):
     """The built-in bridge as a fake_provider: the reference's matrix_to_midi call (network_tests.py:189 / :204) with
-    the DES core and the batched log -> MIDI -> piano-roll kernel behind it; the rolls stay on the device."""
+    the DES core and the batched log -> MIDI -> piano-roll kernel behind it; the rolls stay on the device.
+    batched: simulate all samples in one device launch (matrix_to_midi(simulate="des_batch"))."""
     from .matrix_sim_process import matrix_to_midi
+    simulate = "des_batch" if batched else "des"
 
     def provider(gen_output1, gen_output2, count):
         return matrix_to_midi(gen_output1, gen_output2, adj_size=adj_size, instrument=instrument, start=start, end=end,
-                              count=0 if count is None else count, generate=generate, simulate="des",
+                              count=0 if count is None else count, generate=generate, simulate=simulate,
                               return_tensor=True, midi_path=midi_path)
     return provider
 
@@ -192,11 +195,13 @@ class MultiModalGAN(nn.Module):
         self.midi_path = midi_path          # where generate_midi's built-in bridge writes (default: upstream's path)
         self.generate_provider = None
         if isinstance(fake_provider, str):
-            if fake_provider != "des":
-                raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridge is \"des\")")
-            fake_provider = des_fake_provider(adj_size, instrument, start, end)
+            if fake_provider not in ("des", "des_batch"):
+                raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridges are \"des\" and "
+                                 "\"des_batch\")")
+            batched = fake_provider == "des_batch"
+            fake_provider = des_fake_provider(adj_size, instrument, start, end, batched=batched)
             self.generate_provider = des_fake_provider(adj_size, instrument, start, end, generate=True,
-                                                       midi_path=midi_path)
+                                                       midi_path=midi_path, batched=batched)
         self.fake_provider = fake_provider if fake_provider is not None else _no_bridge
 
     def forward(self, noise1, noise2, input_tensor, count, make_dot_png=True):
@@ -236,7 +241,8 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
         Either feeds every epoch with ``batches(batch_size)``: unshuffled, drop_last, as the reference's DataLoader
         (network_tests.py:229-230).  At most one of train_loader / midi_dir / pickle_file.
     fake_provider(g1_out, g2_out, count) -> ((B,2,128,T) tensor, failed): the DES bridge; "des" -> the built-in one
-        (DES core + batched log -> MIDI -> piano-roll kernel); None -> synthetic rolls.
+        (DES core + batched log -> MIDI -> piano-roll kernel); "des_batch" -> the same with the simulation batched on
+        the device (matrix_sim_process lists what differs); None -> synthetic rolls.
     save_dir: if given, per-epoch ``losses/*.pkl`` and ``models/mmgan_{a}_{b}_epoch_{e}.pth`` are written there with
         the reference's file names; model_path: state_dict to resume from (optimizer state is not saved, as upstream).
     criterion: "bce" | "mse" | "l1" -- the reference picks one by moving a comment (network_tests.py:248-250:
@@ -264,9 +270,11 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
     roll_size = (2, 128, sequence_length)
     start = 100
     if isinstance(fake_provider, str):
-        if fake_provider != "des":
-            raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridge is \"des\")")
-        fake_provider = des_fake_provider(adj_size, 0, start, start + sequence_length)
+        if fake_provider not in ("des", "des_batch"):
+            raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridges are \"des\" and "
+                             "\"des_batch\")")
+        fake_provider = des_fake_provider(adj_size, 0, start, start + sequence_length,
+                                          batched=fake_provider == "des_batch")
     mmgan = MultiModalGAN(z_dim=noise_dim, adj_size=adj_size, roll_size=roll_size, input_dim=max_beat_length,
                           output_dim=gen2_output_dim, instrument=0, start=start, end=start + sequence_length,
                           device=device, fake_provider=fake_provider)
@@ -372,8 +380,9 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--sequence-length", type=int, default=50)
     ap.add_argument("--sample-size", type=int, default=300)
-    ap.add_argument("--fake-provider", choices=("des",), default=None,
-                    help="des: the built-in DES bridge; default: synthetic fake rolls")
+    ap.add_argument("--fake-provider", choices=("des", "des_batch"), default=None,
+                    help="des: the built-in DES bridge; des_batch: the same with the simulation batched on the "
+                         "device; default: synthetic fake rolls")
     ap.add_argument("--save-dir", default=None)
     ap.add_argument("--max-steps", type=int, default=None, help="steps per epoch at most")
     a = ap.parse_args(argv)

@@ -931,6 +931,76 @@ def des_routing(g, s, dim, src_mask, residue_col):
     return out
 
 
+# ---- batched DES simulator on the device (csrc/des_batch.hip; the event logic is csrc/des_sim.h) ---------------------------
+DES_STOP_EMPTY, DES_STOP_CUSTOMERS, DES_STOP_EVENTS, DES_STOP_ERROR, DES_STOP_RECORDS, DES_STOP_BUDGET = range(6)
+DES_BATCH_MAX_DIM = 128         # GDM_DES_BATCH_MAX_DIM
+
+
+def des_batch_workspace_bytes(b, dim, max_queue_cap):
+    n = _lib.load().gdm_des_batch_workspace_bytes(int(b), int(dim), int(max_queue_cap))
+    if n < 0:
+        raise GdmError(f"des_run_batch: B={b}, dim={dim}, max_queue_cap={max_queue_cap} out of range")
+    return n
+
+
+def des_run_batch(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *, max_queue_cap,
+                  max_events=200000, max_records=5001, workspace_tensor=None):
+    """B simulations in one launch (+ the pack step).  Device tensors: adj (B,dim,dim) f64 (``des_routing``'s output),
+    loc, scale (B,dim) f64, queue_cap (B,dim) i32, seed, customers (B) i64; the generator states mt_key (B,624) i32
+    (uint32 bit patterns), mt_pos, has_gauss (B) i32, gauss (B) f64 are UPDATED IN PLACE.  Returns (value, event_id,
+    node, kind, rec_ptr, n_records, stop_reason): the CSR record arrays hold B * max_records entries, of which
+    rec_ptr[B] are records; nothing is read back."""
+    _need_gpu(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss)
+    if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
+        raise GdmError("des_run_batch: adj must be (B, dim, dim)")
+    b, dim = adj.shape[0], adj.shape[1]
+    for t, shape, dt in ((adj, (b, dim, dim), torch.float64), (loc, (b, dim), torch.float64),
+                         (scale, (b, dim), torch.float64), (queue_cap, (b, dim), torch.int32), (seed, (b,), torch.int64),
+                         (customers, (b,), torch.int64), (mt_key, (b, 624), torch.int32), (mt_pos, (b,), torch.int32),
+                         (has_gauss, (b,), torch.int32), (gauss, (b,), torch.float64)):
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise GdmError(f"des_run_batch: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
+                           f"{tuple(t.shape)}")
+    max_records = int(max_records)
+    if max_records < 1:
+        raise GdmError("des_run_batch: the device simulator needs a record cap (max_records >= 1)")
+    dev = adj.device
+    n = b * max_records
+    value = torch.empty(n, dtype=torch.float64, device=dev)
+    event_id = torch.empty(n, dtype=torch.int64, device=dev)
+    node = torch.empty(n, dtype=torch.int32, device=dev)
+    kind = torch.empty(n, dtype=torch.int32, device=dev)
+    rec_ptr = torch.empty(b + 1, dtype=torch.int64, device=dev)
+    n_records = torch.empty(b, dtype=torch.int64, device=dev)
+    stop = torch.empty(b, dtype=torch.int32, device=dev)
+    need = des_batch_workspace_bytes(b, dim, max_queue_cap)
+    ws = workspace(need, dev) if workspace_tensor is None else workspace_tensor
+    _call("gdm_des_run_batch", _p(adj), b, dim, _p(loc), _p(scale), _p(queue_cap), _p(seed), _p(customers),
+          int(max_queue_cap), int(max_events), max_records, _p(mt_key), _p(mt_pos), _p(has_gauss), _p(gauss), _p(value),
+          _p(event_id), _p(node), _p(kind), n, _p(rec_ptr), _p(n_records), _p(stop), _p(ws), ws.numel(), _stream())
+    return value, event_id, node, kind, rec_ptr, n_records, stop
+
+
+def des_pack(n_records, rec_ptr, value, event_id, node, kind, max_records):
+    """The pack step of ``des_run_batch`` alone, in place (device tensors as ``des_run_batch`` returns them)."""
+    _need_gpu(n_records, rec_ptr, value, event_id, node, kind)
+    b = n_records.numel()
+    if rec_ptr.numel() != b + 1 or min(t.numel() for t in (value, event_id, node, kind)) < b * int(max_records):
+        raise GdmError("des_pack: rec_ptr must hold B + 1 offsets and the record arrays B * max_records entries")
+    _call("gdm_des_pack", b, int(max_records), _p(n_records), _p(rec_ptr), _p(value), _p(event_id), _p(node), _p(kind),
+          _stream())
+
+
+def des_math_probe(x):
+    """(des_log(x), sqrt(-2 des_log(x) / x)) of a float64 device tensor: the portable math of the simulator alone."""
+    _need_gpu(x)
+    if x.dtype != torch.float64 or not x.is_contiguous():
+        raise GdmError("des_math_probe: x must be a contiguous float64 tensor")
+    lg, fac = torch.empty_like(x), torch.empty_like(x)
+    _call("gdm_des_math_probe", _p(x), x.numel(), _p(lg), _p(fac), _stream())
+    return lg, fac
+
+
 def piano_roll_raster(row_ptr, ev_step, ev_vel, n_files, width):
     """CSR note messages (int32 device tensors) -> (roll, dur) (n_files, 128, width) fp32."""
     _need_gpu(row_ptr, ev_step, ev_vel)

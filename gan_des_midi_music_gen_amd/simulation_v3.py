@@ -19,7 +19,14 @@ Differences, on purpose:
   * only what the bridges construct is supported: 'normal' distributions, ``logging_mode='Music'``, probability routing
     (no 'queue' / 'branch' nodes, no animation, no metric history) -- anything else raises NotImplementedError;
   * the log records are also kept as arrays (``sim.music_log``), so a caller need not go through the log file.
+
+``run_batch`` / ``run_batch_host`` simulate B specs of one size at once, every sample FROM ITS OWN snapshot of numpy's
+global stream (``gdm_des_run_batch`` on a HIP device: one wave per sample, csrc/des_batch.hip; ``gdm_des_run_batch_host``
+on the host).  Both run the event logic of csrc/des_sim.h, the same source ``gdm_des_run`` is compiled from.  With
+portable math (``math=1``, the only one on the device) the host entry is the device's oracle, bit for bit; against the
+reference the event structure is the same and values differ in their last bits (libm's ``log`` is not portable).
 """
+import collections
 import ctypes
 import os
 
@@ -30,7 +37,8 @@ from . import _lib
 ARRIVAL, DEPARTURE, PROCESSING = 0, 1, 2
 KIND_NAMES = ("arrival", "departure", "processing")
 EVENT_DTYPE = np.dtype([("value", np.float64), ("event_id", np.int64), ("node", np.int32), ("kind", np.int32)])
-STOP_REASONS = ("event list empty", "number_of_customers reached", "max_events reached", "error")
+STOP_REASONS = ("event list empty", "number_of_customers reached", "max_events reached", "error", "max_records reached",
+                "draw budget exhausted")         # GDM_DES_STOP_*; the last two: the batch entries only
 
 
 class Sim:
@@ -85,7 +93,7 @@ class Sim:
         while True:
             k = np.ascontiguousarray(key, dtype=np.uint32).copy()
             c_pos, c_has, c_gauss = ctypes.c_int(int(pos)), ctypes.c_int(int(has_gauss)), ctypes.c_double(float(gauss))
-            out = np.zeros(cap, dtype=EVENT_DTYPE)
+            out = np.empty(cap, dtype=EVENT_DTYPE)        # only out[:n_out] is returned
             n_out, reason = ctypes.c_int64(0), ctypes.c_int(0)
             rc = lib.gdm_des_run(self.adj_matrix.ctypes.data, dim, self.loc.ctypes.data, self.scale.ctypes.data,
                                  self.queue_list.ctypes.data, int(seed), int(number_of_customers), self.max_events,
@@ -121,3 +129,152 @@ def run_spec(spec, max_events=200000, generate_log=False, log_path="logs/"):
               max_sim_time=spec.max_sim_time, max_events=max_events)
     sim.run(number_of_customers=spec.num_customers)
     return sim.music_log, sim.stop_reason
+
+
+# ---- batched simulation: every sample from its own generator state -----------------------------------------------------
+BatchLog = collections.namedtuple("BatchLog", "value event_id node kind rec_ptr n_records stop_reason mt_key mt_pos "
+                                              "has_gauss gauss")
+BatchLog.__doc__ = """Records of B simulations in the CSR layout of ``ops.des_log_to_roll`` / ``ops.des_log_to_notes``
+(sample b: [rec_ptr[b], rec_ptr[b+1])), n_records (B), stop_reason (B, index into STOP_REASONS) and the generator
+states after the runs (mt_key (B,624) uint32 -- int32 bit patterns on a device --, mt_pos, has_gauss, gauss (B))."""
+
+
+def pack_states(states, b):
+    """B ``np.random.get_state()`` tuples (or one for all; None: the current global state) -> (key (B,624) uint32, pos
+    (B) int32, has_gauss (B) int32, gauss (B) float64)."""
+    if states is None:
+        states = np.random.get_state()
+    if isinstance(states, tuple) and len(states) == 5 and isinstance(states[0], str):
+        states = [states] * b
+    if len(states) != b:
+        raise ValueError(f"run_batch: {len(states)} generator states for {b} samples")
+    for st in states:
+        if st[0] != "MT19937":
+            raise ValueError("run_batch: generator states must be numpy legacy MT19937 states (np.random.get_state())")
+    key = np.ascontiguousarray([np.asarray(st[1], dtype=np.uint32) for st in states], dtype=np.uint32).reshape(b, 624)
+    pos = np.ascontiguousarray([int(st[2]) for st in states], dtype=np.int32)
+    has = np.ascontiguousarray([int(st[3]) for st in states], dtype=np.int32)
+    gauss = np.ascontiguousarray([float(st[4]) for st in states], dtype=np.float64)
+    return key, pos, has, gauss
+
+
+def state_of(log, b):
+    """Sample b's generator state after the run, as ``np.random.set_state`` takes it."""
+    key = np.asarray(log.mt_key[b].cpu() if hasattr(log.mt_key, "cpu") else log.mt_key[b])
+    return ("MT19937", key.view(np.uint32).copy(), int(log.mt_pos[b]), int(log.has_gauss[b]), float(log.gauss[b]))
+
+
+def sample_log(log, b):
+    """Sample b's records of a host BatchLog as an EVENT_DTYPE array (what ``Sim.music_log`` holds)."""
+    lo, hi = int(log.rec_ptr[b]), int(log.rec_ptr[b + 1])
+    out = np.empty(hi - lo, dtype=EVENT_DTYPE)
+    for name in ("value", "event_id", "node", "kind"):
+        out[name] = np.asarray(getattr(log, name)[lo:hi])
+    return out
+
+
+def run_batch_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, math=1, max_events=200000,
+                   max_records=5001, max_queue_cap=None):
+    """``gdm_des_run_batch_host`` on numpy arrays: adj (B,dim,dim), loc, scale, queue_cap (B,dim), seed, customers (B).
+    math 0 = libm (the reference's bits), 1 = portable (the device's bits).  max_records 0 = no cap.  -> BatchLog of
+    numpy arrays; the record arrays are cut to rec_ptr[B]."""
+    lib = _lib.load()
+    adj = np.ascontiguousarray(adj, dtype=np.float64)
+    b, dim = adj.shape[0], adj.shape[1]
+    assert adj.shape == (b, dim, dim), adj.shape
+    loc = np.ascontiguousarray(loc, dtype=np.float64).reshape(b, dim)
+    scale = np.ascontiguousarray(scale, dtype=np.float64).reshape(b, dim)
+    queue_cap = np.ascontiguousarray(queue_cap, dtype=np.int32).reshape(b, dim)
+    seed = np.ascontiguousarray(seed, dtype=np.int64).reshape(b)
+    customers = np.ascontiguousarray(customers, dtype=np.int64).reshape(b)
+    key, pos, has, gauss = (np.array(a) for a in pack_states(states, b))
+    max_events, max_records = int(max_events), int(max_records)
+    if max_queue_cap is None:
+        max_queue_cap = max(1, int(queue_cap.max()))
+    per = 4 * max_events + 4 * dim + 64                    # at most four records per processed event
+    cap = b * (min(per, max_records) if max_records > 0 else per)
+    while True:
+        value, eid = np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.int64)
+        node, kind = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+        rec_ptr, n_rec, stop = np.zeros(b + 1, dtype=np.int64), np.zeros(b, dtype=np.int64), np.zeros(b, dtype=np.int32)
+        k, p, h, g = key.copy(), pos.copy(), has.copy(), gauss.copy()
+        rc = lib.gdm_des_run_batch_host(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data,
+                                        queue_cap.ctypes.data, seed.ctypes.data, customers.ctypes.data,
+                                        int(max_queue_cap), int(math), max_events, max_records, k.ctypes.data,
+                                        p.ctypes.data, h.ctypes.data, g.ctypes.data, value.ctypes.data, eid.ctypes.data,
+                                        node.ctypes.data, kind.ctypes.data, cap, rec_ptr.ctypes.data, n_rec.ctypes.data,
+                                        stop.ctypes.data)
+        if rc == -3 and int(rec_ptr[-1]) > cap:            # GDM_EWORKSPACE: again from the ORIGINAL generator states
+            cap = int(rec_ptr[-1])
+            continue
+        _lib.check(rc, "gdm_des_run_batch_host")
+        n = int(rec_ptr[-1])
+        return BatchLog(value[:n], eid[:n], node[:n], kind[:n], rec_ptr, n_rec, stop, k, p, h, g)
+
+
+def spec_arrays(specs):
+    """[DesSpec] of one size -> (adj, loc, scale, queue_cap, seed, customers) numpy arrays with a leading B."""
+    if len(specs) == 0:
+        raise ValueError("run_batch: no specs")
+    dim = np.asarray(specs[0].sim_matrix).shape[0]
+    for sp in specs:
+        if np.asarray(sp.sim_matrix).shape != (dim, dim) or len(sp.distributions) != dim or len(sp.queue_list) != dim:
+            raise ValueError("run_batch: every spec of a batch must have the same number of nodes")
+        if any(d[0] != "normal" for d in sp.distributions):
+            raise NotImplementedError("run_batch: the deterministic core implements 'normal' distributions only")
+        if np.asarray(sp.seeds).size != 1:
+            raise ValueError("run_batch: one seed (one run) per spec")
+    adj = np.ascontiguousarray([np.asarray(sp.sim_matrix, dtype=np.float64) for sp in specs])
+    loc = np.ascontiguousarray([[float(d[1]) for d in sp.distributions] for sp in specs], dtype=np.float64)
+    scale = np.ascontiguousarray([[float(d[2]) for d in sp.distributions] for sp in specs], dtype=np.float64)
+    qcap = np.ascontiguousarray([list(sp.queue_list) for sp in specs], dtype=np.int32)
+    seed = np.ascontiguousarray([int(np.asarray(sp.seeds).reshape(-1)[0]) for sp in specs], dtype=np.int64)
+    customers = np.ascontiguousarray([int(sp.num_customers) for sp in specs], dtype=np.int64)
+    return adj, loc, scale, qcap, seed, customers
+
+
+def run_batch_device(adj, loc, scale, queue_cap, seed, customers, states=None, *, device, max_events=200000,
+                     max_records=5001, max_queue_cap=None, workspace_tensor=None):
+    """``gdm_des_run_batch``: the arrays of ``run_batch_host`` (numpy, or device tensors that stay where they are --
+    ``adj`` straight from ``ops.des_routing``) -> BatchLog of device tensors.  Nothing is read back."""
+    import torch
+    from . import ops
+    dev = torch.device(device)
+
+    def up(a, dt):
+        if torch.is_tensor(a):
+            return a.to(device=dev, dtype=dt).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(dt).contiguous()
+
+    b = adj.shape[0]
+    if max_queue_cap is None:
+        if torch.is_tensor(queue_cap):
+            raise ValueError("run_batch_device: pass max_queue_cap with a device queue_cap (it sizes the workspace)")
+        max_queue_cap = max(1, int(np.asarray(queue_cap).max()))
+    key, pos, has, gauss = pack_states(states, b)
+    k, p, h, g = up(key.view(np.int32), torch.int32), up(pos, torch.int32), up(has, torch.int32), up(gauss, torch.float64)
+    out = ops.des_run_batch(up(adj, torch.float64), up(loc, torch.float64), up(scale, torch.float64),
+                            up(queue_cap, torch.int32), up(seed, torch.int64), up(customers, torch.int64), k, p, h, g,
+                            max_queue_cap=max_queue_cap, max_events=max_events, max_records=max_records,
+                            workspace_tensor=workspace_tensor)
+    return BatchLog(*out, k, p, h, g)
+
+
+def run_batch(specs, *, device=None, max_events=200000, max_records=5001, states=None):
+    """B ``matrix_sim_process.DesSpec`` of one size, each simulated from its own generator state (``states``: B
+    ``np.random.get_state()`` tuples, or one for all; None: numpy's current global state -- which is left untouched).
+    device=None: the host mirror with portable math (``gdm_des_run_batch_host``, math=1) -> BatchLog of numpy arrays;
+    a HIP device: the kernel (``gdm_des_run_batch``) -> BatchLog of device tensors, bit-identical to the host's."""
+    arrays = spec_arrays(specs)
+    if device is None:
+        return run_batch_host(*arrays, states, math=1, max_events=max_events, max_records=max_records)
+    return run_batch_device(*arrays, states, device=device, max_events=max_events, max_records=max_records)
+
+
+def math_probe_host(x):
+    """(des_log(x), sqrt(-2 des_log(x) / x)) on the host: the portable math of the batch simulator alone."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    lg, fac = np.empty_like(x), np.empty_like(x)
+    _lib.check(_lib.load().gdm_des_math_probe_host(x.ctypes.data, x.size, lg.ctypes.data, fac.ctypes.data),
+               "gdm_des_math_probe_host")
+    return lg, fac

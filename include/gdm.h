@@ -376,6 +376,57 @@ int gdm_des_run(const double* adj, int dim, const double* loc, const double* sca
                 int64_t number_of_customers, int64_t max_events, uint32_t* mt_key, int* mt_pos, int* has_gauss,
                 double* cached_gauss, gdm_des_event* out, int64_t out_capacity, int64_t* n_out, int* stop_reason);
 
+/* ---- the same simulator for a batch of B specs of one dim (csrc/des_sim.h is the one source of the event logic) -------
+ * Sample b is simulated exactly as gdm_des_run simulates it FROM ITS OWN generator state (mt_key (B,624), mt_pos,
+ * has_gauss, cached_gauss (B): in and out per sample): nothing is handed from one sample to the next.  All arrays have a
+ * leading B: adj (B,dim,dim) -- what gdm_des_routing writes --, loc, scale (B,dim) f64, queue_cap (B,dim) i32, seed,
+ * number_of_customers (B) i64.  max_queue_cap = the ring capacity per server (a sample with a larger queue_cap errors).
+ * max_events >= 1 caps the processed events; every generator draw counts against a budget of
+ * 64 * (max_events + dim + 1) 32-bit words per sample (stop reason 5: a service distribution that never turns positive
+ * ends there instead of spinning).  max_records: the sample stops (reason 4) as soon as that many records are written,
+ * a prefix of the uncapped log; 0 = no cap (host only).
+ * Records come out in the CSR layout gdm_des_log_to_roll / gdm_des_log_to_notes take: value, event_id, node, kind
+ * (n_records_cap entries each) and rec_ptr (B + 1); n_records (B) i64, stop_reason (B) i32 = GDM_DES_STOP_*.  A sample
+ * that errors (reason 3: bad spec, no destination, a customer routed to a source, a capacity overrun) has an empty log
+ * and leaves its neighbours alone.
+ * gdm_des_run_batch_host: host arrays; math 0 = libm's log / sqrt (numpy's bits, as gdm_des_run), 1 = the portable
+ *   log / sqrt of des_sim.h.  GDM_EWORKSPACE when n_records_cap is too small (rec_ptr[B] then holds the count needed).
+ * gdm_des_run_batch: device arrays, always portable math: bit-identical to the host entry with math = 1.  One wave per
+ *   sample + a one-workgroup pack step.  max_records >= 1 is required and n_records_cap >= B * max_records (the bound
+ *   the consumers are given as n_records: nothing is read back in between).  workspace: 16-byte aligned device memory
+ *   of gdm_des_batch_workspace_bytes(B, dim, max_queue_cap) bytes (generator states, rings, routing tables; -1 for
+ *   arguments out of range).
+ * gdm_des_pack: the pack step of gdm_des_run_batch on its own (device arrays): records of sample b at b * max_records,
+ *   n_records (B) counts (clamped to 0..max_records) -> rec_ptr (B + 1) and the records closed up in place.
+ * gdm_des_math_probe[_host]: log_out[i] = des_log(x[i]), factor_out[i] = sqrt(-2 des_log(x[i]) / x[i]) -- the portable
+ *   math of the polar method on its own, device and host form (they must agree bit for bit).                         */
+#define GDM_DES_STOP_EMPTY 0
+#define GDM_DES_STOP_CUSTOMERS 1
+#define GDM_DES_STOP_EVENTS 2
+#define GDM_DES_STOP_ERROR 3
+#define GDM_DES_STOP_RECORDS 4
+#define GDM_DES_STOP_BUDGET 5
+#define GDM_DES_BATCH_MAX_DIM 128
+#define GDM_DES_BATCH_MAX_QUEUE_CAP 65536
+#define GDM_DES_BATCH_MAX_EVENTS ((int64_t)1 << 40)
+int gdm_des_run_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                           const int32_t* queue_cap, const int64_t* seed, const int64_t* number_of_customers,
+                           int max_queue_cap, int math, int64_t max_events, int64_t max_records, uint32_t* mt_key,
+                           int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss, double* value, int64_t* event_id,
+                           int32_t* node, int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records,
+                           int32_t* stop_reason);
+int64_t gdm_des_batch_workspace_bytes(int B, int dim, int max_queue_cap);
+int gdm_des_run_batch(const double* adj, int B, int dim, const double* loc, const double* scale,
+                      const int32_t* queue_cap, const int64_t* seed, const int64_t* number_of_customers,
+                      int max_queue_cap, int64_t max_events, int64_t max_records, uint32_t* mt_key, int32_t* mt_pos,
+                      int32_t* has_gauss, double* cached_gauss, double* value, int64_t* event_id, int32_t* node,
+                      int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int gdm_des_pack(int B, int64_t max_records, const int64_t* n_records, int64_t* rec_ptr, double* value,
+                 int64_t* event_id, int32_t* node, int32_t* kind, void* stream);
+int gdm_des_math_probe_host(const double* x, int64_t n, double* log_out, double* factor_out);
+int gdm_des_math_probe(const double* x, int64_t n, double* log_out, double* factor_out, void* stream);
+
 /* ---- generic convolution lowering helpers (model 2 discriminator, model 1 generator) ----------------------------
  * im2col for Conv2d fwd / dW and col2im (gather form, deterministic) for Conv2d dX and ConvTranspose2d fwd.
  * Activations are channels-last (B,H,W,C) unless `src_planar` (NCHW fp32 input planes, e.g. the piano-roll).
