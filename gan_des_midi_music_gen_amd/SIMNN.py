@@ -186,8 +186,7 @@ _WAV_CHUNK = 1 << 22          # samples rendered per gdm_synth_pcm launch (8 MB 
 
 def _des_song(matrix, midi_path, wav_path, max_seconds, batched=False):
     """matrix_to_wav(simulate="des" / "des_batch") for one matrix, keeping the note list for the two files."""
-    import struct
-    from . import matrix_sim_process as msp, ops, sim_log_process_music as slpm, sim_log_to_midi
+    from . import matrix_sim_process as msp, ops, sim_log_process_music as slpm, sim_log_to_midi, util
     if batched:
         mel, (notes, n_notes, clip_len) = msp._batch_to_mel(msp.batched_prologue_wav(matrix, 20, None), 200000)
     else:
@@ -208,9 +207,7 @@ def _des_song(matrix, midi_path, wav_path, max_seconds, batched=False):
         if d:
             os.makedirs(d, exist_ok=True)
         with open(wav_path, "wb") as f:
-            f.write(b"RIFF" + struct.pack("<I", 36 + 2 * total) + b"WAVEfmt " +
-                    struct.pack("<IHHIIHH", 16, 1, 1, ops.SYNTH_RATE, 2 * ops.SYNTH_RATE, 2, 16) +
-                    b"data" + struct.pack("<I", 2 * total))
+            f.write(util.wav_header(total, ops.SYNTH_RATE))
             for first in range(0, total, _WAV_CHUNK):
                 count = min(_WAV_CHUNK, total - first)
                 pcm = torch.zeros(count, dtype=torch.int16) if blank else \
@@ -276,11 +273,17 @@ def _song_batches(spec, batch_size, shuffle):
 def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5, 0.999), display_step=5, save_step=5,
           z_dim=100, model_path="models/", input_hw=None, fake_provider=None, device=None, seed=None,
           compute_dtype=None, elide_dead_backward=False, max_steps=None, save=True, log=print, audio_file=None,
-          window_size=5, hop_length_audio=5, shuffle=True):
+          window_size=5, hop_length_audio=5, shuffle=True, maestro_dir=None, maestro_meta=None):
     """The reference's ``__main__`` training loop (SIMNN.py:234-348) on the fused MI355X step.
 
-    dataloader: iterable of real batches (B,H,W) fp32 (the reference's MaestroDataset/DataLoader); if None, seeded
-        synthetic spectrogram windows are used (``max_steps`` batches, default 10).
+    dataloader: iterable of real batches (B,H,W) fp32 (the reference's ``DataLoader(MaestroDataset(batch_size=30),
+        batch_size=1, shuffle=True, collate_fn=my_collate)``, both in ``datasets``); if None, seeded synthetic
+        spectrogram windows are used (``max_steps`` batches, default 10).
+    maestro_dir: a MAESTRO folder to train on instead -- the reference's default configuration, built here:
+        ``datasets.MaestroDataset(batch_size, input_folder=maestro_dir, meta_data_file=maestro_meta)``.  Every epoch
+        visits the files in a ``torch.randperm`` order (in index order with ``shuffle=False``) and each step trains on
+        one file's windows, at most ``batch_size`` of them, as that DataLoader deals them.  The windows are rendered by
+        the integer synth that renders the "des" fakes.  ``input_hw`` is (128, 216).
     audio_file: a WAV file to train on instead (``datasets.InputSong(audio_file, window_size, hop_length_audio)``, the
         reference's single-song configuration): every epoch deals the song's windows in batches of ``batch_size``,
         shuffled unless ``shuffle=False``.  ``input_hw`` then defaults to the (128, frames) of the song's windows
@@ -294,10 +297,16 @@ def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5,
     """
     from .train import SimnnTrainer
     device = torch.device(device if device is not None else "cuda")
-    song = None
-    if audio_file is not None:
-        if dataloader is not None:
-            raise ValueError("train() takes audio_file or dataloader, not both")
+    song = maestro = None
+    if (audio_file is not None) + (dataloader is not None) + (maestro_dir is not None) > 1:
+        raise ValueError("train() takes one of audio_file, dataloader and maestro_dir")
+    if maestro_dir is not None:
+        from .datasets import MaestroDataset
+        if input_hw is not None and tuple(input_hw) != (128, 216):
+            raise ValueError(f"input_hw = {tuple(input_hw)} but the windows of a MAESTRO file are (128, 216)")
+        input_hw = (128, 216)
+        maestro = MaestroDataset(batch_size, input_folder=maestro_dir, meta_data_file=maestro_meta, device=device)
+    elif audio_file is not None:
         from .datasets import InputSong
         song = InputSong(audio_file, window_size, hop_length_audio, device=device).spectrograms()
         song_hw = tuple(song.shape[1:])
@@ -327,6 +336,9 @@ def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5,
     for epoch in range(n_epochs):
         if song is not None:
             batches = _song_batches(song, batch_size, shuffle)
+        elif maestro is not None:
+            order = torch.randperm(len(maestro)).tolist() if shuffle else range(len(maestro))
+            batches = (maestro[i] for i in order)
         elif dataloader is None:
             n = max_steps if max_steps is not None else 10
             batches = (synthetic.spectrogram_batch(batch_size, input_hw, seed=1234 + i) for i in range(n))
@@ -361,6 +373,8 @@ def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="Train model 1 (the reference's SIMNN.py __main__ loop).")
     ap.add_argument("--audio-file", default=None, help="WAV file to train on (default: seeded synthetic windows)")
+    ap.add_argument("--maestro-dir", default=None,
+                    help="MAESTRO folder (maestro-v3.0.0.json and its MIDI files) to train on, one file per step")
     ap.add_argument("--epochs", type=int, default=1)
     ap.add_argument("--batch-size", type=int, default=30)
     ap.add_argument("--max-steps", type=int, default=None)
@@ -370,7 +384,7 @@ def main(argv=None):
                          "the device (default: seeded synthetic windows)")
     a = ap.parse_args(argv)
     train(audio_file=a.audio_file, n_epochs=a.epochs, batch_size=a.batch_size, max_steps=a.max_steps,
-          save=not a.no_save, fake_provider=a.fake_provider)
+          save=not a.no_save, fake_provider=a.fake_provider, maestro_dir=a.maestro_dir)
 
 
 if __name__ == "__main__":

@@ -128,6 +128,7 @@ SIGNATURES = {
     "gdm_des_log_to_notes": (_I, [_P, _P, _P, _P, _P, _L, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
     "gdm_synth_frames": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "gdm_synth_pcm": (_I, [_P, _I, _P, _P, _P, _L, _L, _P, _P]),
+    "gdm_synth_windows": (_I, [_P, _P, _L, _P, _I, _P, _P, _I, _L, _L, _P, _P, _P, _P]),
     "gdm_maxpool2_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "gdm_maxpool2_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
 }

@@ -15,6 +15,11 @@
 // Then every thread produces 8 samples -- the voices in the outer loop, the 8 running sums in registers -- and stores
 // them with 16-byte stores.  LDS: 16 bytes per voice the list can hold (notes_cap of them, 5000 at most: 80 KB) + the
 // 4 KB wave table.
+//
+// gdm_synth_windows renders W windows of F clips of ANY length (a MIDI performance: tens of thousands of notes) in one
+// launch.  Its note rows carry sample times and ascend in s_on, so a workgroup never scans the clip: two binary searches
+// bound the rows that can sound in its 2048 samples, and it walks them in tiles of 1024 rows, each compacted into a
+// fixed 16 KB list and added to the same eight register sums.  No cap on notes or on simultaneous voices.
 #include "gdm_common.h"
 #include "buffer_ops.h"
 
@@ -32,11 +37,28 @@ typedef short short8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ int64_t tick_to_sample(int64_t tick) { return (tick * 735) >> 3; }
 
-// Stage the wave table and the voices that sound anywhere in [lo, hi] (hi - lo < 2^13).  A listed voice is
+// A voice that sounds somewhere in [lo, lo + 2^13), as the list holds it:
 //   x = phase at sample lo (mod 2^32),  y = inc[p],  z = s_on - lo clamped to [-A, 2^13],
 //   w = (s_off - lo clamped to [-R, 2^20]) + R  |  v << 24
 // The clamps change nothing inside the range: from A samples after s_on the attack is full, and a note-off beyond the
-// range is simply "not yet".  Returns the number of listed voices (<= n <= kMaxNotes: the list cannot overflow).
+// range is simply "not yet".  They are written as comparisons so that no difference of two times is formed that could
+// leave 64 bits, whatever the rows hold (|lo| <= 2^62).
+__device__ __forceinline__ int4 voice_entry(int64_t s_on, int64_t s_off, int64_t pitch, int64_t velocity, int64_t lo,
+                                            const uint32_t* __restrict__ inc) {
+  const uint32_t step = inc[pitch & 127];
+  const uint32_t vel = (uint32_t)(velocity & 127);
+  const int64_t on_rel = s_on < lo - kA ? (int64_t)-kA : (s_on > lo + (1 << 13) ? (int64_t)1 << 13 : s_on - lo);
+  const int64_t off_rel = s_off < lo - kR ? (int64_t)-kR : (s_off > lo + (1 << 20) ? (int64_t)1 << 20 : s_off - lo);
+  int4 e;
+  e.x = (int)(step * (uint32_t)((uint64_t)lo - (uint64_t)s_on));
+  e.y = (int)step;
+  e.z = (int)on_rel;
+  e.w = (int)((uint32_t)(off_rel + kR) | (vel << 24));
+  return e;
+}
+
+// Stage the wave table and the voices that sound anywhere in [lo, hi] (hi - lo < 2^13), times given in ticks.  Returns
+// the number of listed voices (<= n <= kMaxNotes: the list cannot overflow).
 __device__ int stage_voices(const int64_t* __restrict__ notes, int n, int64_t lo, int64_t hi,
                             const int16_t* __restrict__ wave, const uint32_t* __restrict__ inc, int4* s_voice,
                             int16_t* s_wave, int* s_count) {
@@ -48,16 +70,8 @@ __device__ int stage_voices(const int64_t* __restrict__ notes, int n, int64_t lo
     const int64_t s_on = tick_to_sample(notes[4 * (int64_t)k + 0]);
     const int64_t s_off = tick_to_sample(notes[4 * (int64_t)k + 1]);
     if (s_on > hi || s_off + kR <= lo) continue;
-    const uint32_t step = inc[notes[4 * (int64_t)k + 2] & 127];
-    const uint32_t vel = (uint32_t)(notes[4 * (int64_t)k + 3] & 127);
-    const int64_t on_rel = min(max(s_on - lo, (int64_t)-kA), (int64_t)1 << 13);
-    const int64_t off_rel = min(max(s_off - lo, (int64_t)-kR), (int64_t)1 << 20);
-    int4 e;
-    e.x = (int)(step * (uint32_t)(uint64_t)(lo - s_on));
-    e.y = (int)step;
-    e.z = (int)on_rel;
-    e.w = (int)((uint32_t)(off_rel + kR) | (vel << 24));
-    s_voice[atomicAdd(s_count, 1)] = e;
+    s_voice[atomicAdd(s_count, 1)] =
+        voice_entry(s_on, s_off, notes[4 * (int64_t)k + 2], notes[4 * (int64_t)k + 3], lo, inc);
   }
   __syncthreads();
   return *s_count;
@@ -165,6 +179,78 @@ __global__ __launch_bounds__(kThreads) void synth_pcm_kernel(const int64_t* __re
   }
 }
 
+// One workgroup per (2048-sample chunk, window) of gdm_synth_windows.  Rows [r0, r1) are the window's clip; of them only
+// [begin, end) can sound in [lo, hi]: rows from `end` on start after hi (s_on ascends), rows before `begin` have all
+// ended before lo (off_max is the running maximum of s_off).  Everything read from device memory is clamped before it
+// bounds a loop or forms an address: the clip index to [0, F), the row range to [0, n_total], the searches to the range.
+constexpr int kTile = GDM_SYNTH_TILE;
+constexpr int64_t kTimeMax = (int64_t)1 << 62;
+
+__global__ __launch_bounds__(kThreads) void synth_windows_kernel(const int64_t* __restrict__ notes,
+                                                                 const int64_t* __restrict__ off_max, int64_t n_total,
+                                                                 const int64_t* __restrict__ note_ptr, int F,
+                                                                 const int32_t* __restrict__ win_clip,
+                                                                 const int64_t* __restrict__ win_start, int64_t win_len,
+                                                                 int64_t out_stride, const int16_t* __restrict__ wave,
+                                                                 const uint32_t* __restrict__ inc,
+                                                                 int16_t* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) int4 s_voice[kTile];
+  __shared__ int16_t s_wave[GDM_SYNTH_WAVE];
+  __shared__ int s_count;
+  const int tid = threadIdx.x, w = blockIdx.y;
+  const int clip = min(max(win_clip[w], 0), F - 1);
+  const int64_t r0 = min(max(note_ptr[clip], (int64_t)0), n_total);
+  const int64_t r1 = min(max(note_ptr[clip + 1], r0), n_total);
+  const int64_t c0 = (int64_t)blockIdx.x * kChunk;                   // first output sample of this workgroup
+  const int64_t lo = min(max(win_start[w], -kTimeMax), kTimeMax) + c0, hi = lo + kChunk - 1;
+  int64_t a = r0, b = r1;                                            // end: the first row with s_on > hi
+  while (a < b) {
+    const int64_t m = a + ((b - a) >> 1);
+    if (notes[4 * m] > hi) b = m; else a = m + 1;
+  }
+  const int64_t end = a;
+  a = r0, b = end;                                                   // begin: the first row with off_max + R > lo
+  while (a < b) {
+    const int64_t m = a + ((b - a) >> 1);
+    if (off_max[m] > lo - kR) b = m; else a = m + 1;
+  }
+  const int64_t begin = a;
+  if (tid == 0) s_count = 0;
+  for (int i = tid; i < GDM_SYNTH_WAVE; i += kThreads) s_wave[i] = wave[i];
+  int t[kPer], acc[kPer];
+#pragma unroll
+  for (int e = 0; e < kPer; ++e) {
+    t[e] = tid * kPer + e;
+    acc[e] = 0;
+  }
+  __syncthreads();
+  for (int64_t base = begin; base < end; base += kTile) {            // uniform over the workgroup
+    const int64_t stop = min(base + kTile, end);
+    for (int64_t k = base + tid; k < stop; k += kThreads) {
+      const int64_t s_on = notes[4 * k + 0], s_off = notes[4 * k + 1];
+      if (s_on > hi || s_off <= lo - kR) continue;
+      s_voice[atomicAdd(&s_count, 1)] = voice_entry(s_on, s_off, notes[4 * k + 2], notes[4 * k + 3], lo, inc);
+    }
+    __syncthreads();
+    add_voices(s_voice, s_count, s_wave, t, acc);                    // <= kTile entries: the list cannot overflow
+    __syncthreads();
+    if (tid == 0) s_count = 0;                                       // ordered before the next tile's adds by its barrier
+    __syncthreads();
+  }
+  const int64_t i0 = c0 + tid * kPer;
+  int16_t* o = out + (int64_t)w * out_stride;
+  if (i0 + kPer <= win_len) {
+    short8 v;
+#pragma unroll
+    for (int e = 0; e < kPer; ++e) v[e] = (short)clamp16(acc[e]);
+    *reinterpret_cast<short8*>(o + i0) = v;
+  } else {
+#pragma unroll
+    for (int e = 0; e < kPer; ++e)
+      if (i0 + e < win_len) o[i0 + e] = (int16_t)clamp16(acc[e]);
+  }
+}
+
 int tables_ok(const char* who, const void* notes, int notes_cap, const void* n_notes, const void* wave, const void* inc) {
   GDM_REQUIRE(notes && n_notes && wave && inc, "%s: null pointer", who);
   GDM_REQUIRE(notes_cap > 0 && notes_cap <= GDM_DES_NOTES_MAX, "%s: %d notes per clip (1 .. %d fit the voice list)", who,
@@ -201,5 +287,33 @@ extern "C" int gdm_synth_pcm(const int64_t* notes, int notes_cap, const int32_t*
                      notes_cap * sizeof(int4),
                      (hipStream_t)stream, notes, notes_cap, n_notes, wave, inc, first, count, out);
   GDM_LAUNCH_OK("gdm_synth_pcm");
+  return GDM_OK;
+}
+
+extern "C" int gdm_synth_windows(const int64_t* notes, const int64_t* off_max, int64_t n_total, const int64_t* note_ptr,
+                                 int F, const int32_t* win_clip, const int64_t* win_start, int W, int64_t win_len,
+                                 int64_t out_stride, const int16_t* wave, const uint32_t* inc, int16_t* out,
+                                 void* stream) {
+  GDM_REQUIRE(n_total >= 0, "gdm_synth_windows: n_total = %lld", (long long)n_total);
+  GDM_REQUIRE((notes && off_max) || n_total == 0, "gdm_synth_windows: null pointer (notes / off_max of %lld rows)",
+              (long long)n_total);
+  GDM_REQUIRE(note_ptr && win_clip && win_start && wave && inc && out, "gdm_synth_windows: null pointer");
+  GDM_REQUIRE(((uintptr_t)notes & 7) == 0 && ((uintptr_t)off_max & 7) == 0 && ((uintptr_t)note_ptr & 7) == 0 &&
+                  ((uintptr_t)win_start & 7) == 0 && ((uintptr_t)win_clip & 3) == 0 && ((uintptr_t)wave & 1) == 0 &&
+                  ((uintptr_t)inc & 3) == 0,
+              "gdm_synth_windows: notes / off_max / note_ptr / win_clip / win_start / wave / inc must be aligned to "
+              "their elements");
+  GDM_REQUIRE(((uintptr_t)out & 15) == 0, "gdm_synth_windows: out must be 16-byte aligned (16-byte stores)");
+  GDM_REQUIRE(F >= 1, "gdm_synth_windows: F = %d clips (at least 1)", F);
+  GDM_REQUIRE(W >= 1 && W <= 65535, "gdm_synth_windows: W = %d windows (1 .. 65535)", W);
+  GDM_REQUIRE(win_len >= 1 && win_len <= ((int64_t)1 << 30), "gdm_synth_windows: win_len = %lld (1 .. 2^30 samples)",
+              (long long)win_len);
+  GDM_REQUIRE(out_stride >= win_len && out_stride % 8 == 0,
+              "gdm_synth_windows: out_stride = %lld (at least win_len = %lld and a multiple of 8: 16-byte stores)",
+              (long long)out_stride, (long long)win_len);
+  hipLaunchKernelGGL(synth_windows_kernel, dim3((unsigned)((win_len + kChunk - 1) / kChunk), W), dim3(kThreads), 0,
+                     (hipStream_t)stream, notes, off_max, n_total, note_ptr, F, win_clip, win_start, win_len, out_stride,
+                     wave, inc, out);
+  GDM_LAUNCH_OK("gdm_synth_windows");
   return GDM_OK;
 }

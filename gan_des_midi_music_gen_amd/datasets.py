@@ -8,6 +8,7 @@ config 1").
     MaestroDatasetPickle(pickle_file_name, sequence_length=100, beats_length=50, device='cpu')  datasets.py:73-87
     MaestroDatasetTorch(root_dir, sequence_length=100, beats_length=50, device='cpu')           datasets.py:90-100
     MaestroWindows.from_midi(root_dir_or_list, sample_size=300, sequence_length=50, ...)        notebook cells 10-11
+    MaestroDataset(batch_size, input_folder=..., device='cuda'), my_collate                     GAN_DES/datasets.py:55-100
 
 ``generate_piano_roll`` keeps the reference's signature and return value (numpy ``piano_roll (128, W)``, ``durations
 (128, W)``, ``beats (beats_length,)``); ``generate_piano_rolls`` is the batched form the training data path wants: a list
@@ -35,11 +36,23 @@ reference's file, ``MaestroDatasetPickle`` reads one, ``MaestroDatasetTorch`` / 
 
 ``InputSong`` reads a WAV file (``util.load_wav``, host), uploads its sample bytes once and computes the mel-dB windows
 of the whole song on the device straight from them (``util.melspectrogram_db_from_pcm``): the decoded, overlapping
-float windows the reference keeps in ``self.audio_files`` are never built.  MaestroDataset (FluidSynth) stays outside.
+float windows the reference keeps in ``self.audio_files`` are never built.
+
+``MaestroDataset`` is model 1's default data path upstream: a MIDI file of MAESTRO rendered to audio, cut into 5 s
+windows, at most ``k`` of them kept, their mel-dB tensors stacked.  Upstream renders through FluidSynth and a WAV file
+on disk; here the host turns the file into a note list in samples (``midi_notes``: exact integer time, FIFO pairing, the
+sustain pedal) and the device renders only the chosen windows with the package's integer synth -- the renderer of the DES
+bridge's fakes, so reals and fakes of a training run share one -- straight into the buffer the mel chain reads
+(``ops.synth_windows``, ``util.melspectrogram_db_from_synth_windows``).  Nothing is written to disk; ``midi_to_wav``
+writes the audio for whoever wants to hear it.  FluidSynth's sound font is not imitated: PARITY UNPINNED, as for the
+bridge (include/gdm.h defines the synth and the MIDI rules).
 """
+import collections
 import glob
+import json
 import os
 import pickle
+import random
 import struct
 
 import numpy as np
@@ -54,11 +67,14 @@ _SYS_BYTES = {0xF1: 1, 0xF2: 2, 0xF3: 1}
 
 
 class MidiData:
-    """Messages of all tracks as parallel arrays: absolute tick, track index, kind, two data values."""
+    """Messages of all tracks as parallel arrays: absolute tick, track index, kind, two data values, and ``status``:
+    the status byte of a channel or system message (running status resolved), 0xFF for a meta event, 0xF0 / 0xF7 for a
+    system exclusive one (None if the producer did not record it)."""
 
-    def __init__(self, fmt, ticks_per_beat, tick, track, kind, a, b):
+    def __init__(self, fmt, ticks_per_beat, tick, track, kind, a, b, status=None):
         self.format, self.ticks_per_beat = fmt, ticks_per_beat
         self.tick, self.track, self.kind, self.a, self.b = tick, track, kind, a, b
+        self.status = status
 
 
 def read_midi(path_or_bytes):
@@ -74,7 +90,7 @@ def read_midi(path_or_bytes):
     if division & 0x8000:
         raise ValueError("SMPTE time division is not supported")
     pos = 8 + hlen
-    tick, track, kind, av, bv = [], [], [], [], []
+    tick, track, kind, av, bv, sv = [], [], [], [], [], []
     n_tr = 0
     while pos + 8 <= len(data) and n_tr < ntrks:
         tag = data[pos:pos + 4]
@@ -95,7 +111,7 @@ def read_midi(path_or_bytes):
                     break
             now += delta
             lead = data[pos]
-            k, a, b = _K_OTHER, 0, 0
+            k, a, b, st = _K_OTHER, 0, 0, lead
             if lead == 0xFF:                                  # meta event: type, length, body
                 mtype = data[pos + 1]
                 pos += 2
@@ -131,6 +147,7 @@ def read_midi(path_or_bytes):
                     pos += 1
                 elif not status:
                     raise ValueError("MIDI data byte without a running status")
+                st = status
                 if status >= 0xF0:
                     pos += _SYS_BYTES.get(status, 0)
                 else:
@@ -147,10 +164,12 @@ def read_midi(path_or_bytes):
             kind.append(k)
             av.append(a)
             bv.append(b)
+            sv.append(st)
         pos = end
         n_tr += 1
     return MidiData(fmt, division, np.asarray(tick, dtype=np.int64), np.asarray(track, dtype=np.int32),
-                    np.asarray(kind, dtype=np.int8), np.asarray(av, dtype=np.int64), np.asarray(bv, dtype=np.int64))
+                    np.asarray(kind, dtype=np.int8), np.asarray(av, dtype=np.int64), np.asarray(bv, dtype=np.int64),
+                    np.asarray(sv, dtype=np.uint8))
 
 
 def message_seconds(md):
@@ -600,3 +619,199 @@ class InputSong(torch.utils.data.Dataset):
         if not -n <= i < n:
             raise IndexError(f"window {item} of a song with {n}")
         return self.spectrograms()[i]
+
+
+# ---- model 1's MAESTRO route: MIDI file -> notes in samples -> windows of the integer synth -> mel dB ------------------
+MAX_CLIP_SAMPLES = 1 << 40          # the synth's sample range (gdm_synth_pcm, GDM_DES_NOTES_ELONG)
+MAX_CLIP_NOTES = 1 << 18            # the kernel's int32 voice sum is proven below that: 2^18 * 8128 < 2^31
+_WAV_CHUNK = 1 << 22                # samples midi_to_wav renders per launch (8 MB of PCM)
+
+
+def midi_notes(midi_input, *, pedal=True):
+    """A Standard MIDI File (path, bytes or MidiData) -> (notes (n, 4) int64, clip_len): rows (s_on, s_off, pitch,
+    velocity) IN SAMPLES at 44 100 Hz, sorted by s_on (stable), as ``ops.synth_windows`` takes them.  The rules are
+    defined here and in include/gdm.h, as the synth is:
+
+    Time.  Tracks are merged as in ``message_seconds`` (stable by absolute tick; a tempo applies to the messages after
+    its set_tempo, 500 000 before the first).  With U = the running sum of delta_ticks * tempo in force, a message
+    sounds at sample ``U * 441 // (ticks_per_beat * 10000)``: Python integers, no float anywhere.  At tempo 1 000 000
+    and 480 ticks per beat -- the bridge's own files -- that is ``(tick * 735) >> 3``.  ValueError if U * 441 reaches
+    2^63.
+    Pairing.  A note_on with velocity > 0 opens a note on its (channel, pitch); a note_off, or a note_on with velocity
+    0, closes the OLDEST open note of that (channel, pitch); a close without an open note is ignored; notes still open
+    at the end close at the file's last message (the latest end_of_track counts as one).
+    Sustain pedal (controller 64 per channel, value >= 64 = down).  A close that arrives while the pedal is down is
+    deferred: the note ends at the earliest of the pedal's release on its channel, the next note_on of its (channel,
+    pitch), and the file's last message.  ``pedal=False`` ignores controller 64.
+    All channels sound the same voice, program changes are ignored, pitch and velocity are kept as stored (0..127).
+    clip_len = max(s_off) + the synth's release (8192), or 5 * 44100 for a file without notes (the bridge's blank clip).
+    ValueError for a clip beyond 2^40 samples and for 2^18 notes or more."""
+    md = midi_input if isinstance(midi_input, MidiData) else read_midi(midi_input)
+    if md.format == 2:
+        raise TypeError("can't merge tracks in type 2 (asynchronous) file")
+    if md.status is None:
+        raise ValueError("midi_notes needs MidiData.status (read_midi records it)")
+    order = np.argsort(md.tick, kind="stable")
+    ticks, kinds = md.tick[order].tolist(), md.kind[order].tolist()
+    av, bv, sv = md.a[order].tolist(), md.b[order].tolist(), md.status[order].tolist()
+    den = md.ticks_per_beat * 10000
+    if den <= 0:
+        raise ValueError("ticks_per_beat must be positive")
+    rows = []                                            # [s_on, s_off or None, pitch, velocity] in note_on order
+    open_rows = collections.defaultdict(collections.deque)      # (channel, pitch) -> rows waiting for their close
+    held = collections.defaultdict(list)                 # channel -> rows whose close the pedal defers
+    down = [False] * 16
+    u = prev = s = 0
+    tempo = DEFAULT_TEMPO
+    for tk, k, a, b, st in zip(ticks, kinds, av, bv, sv):
+        u += (tk - prev) * tempo
+        prev = tk
+        if u * 441 >= 1 << 63:
+            raise ValueError("the file's running time passes 2^63 / 441 us * ticks per beat")
+        s = u * 441 // den
+        if k == _K_TEMPO:
+            tempo = a
+        elif k == _K_ON and b > 0:
+            ch = st & 15
+            if held[ch]:                                 # the key is struck again: its held notes end here
+                for r in held[ch]:
+                    if r[2] == a:
+                        r[1] = s
+                held[ch] = [r for r in held[ch] if r[2] != a]
+            rows.append([s, None, a, b])
+            open_rows[ch, a].append(rows[-1])
+        elif k in (_K_ON, _K_OFF):
+            ch = st & 15
+            if open_rows[ch, a]:
+                r = open_rows[ch, a].popleft()
+                if down[ch]:
+                    held[ch].append(r)
+                else:
+                    r[1] = s
+        elif pedal and st >> 4 == 0xB and a == 64:
+            ch = st & 15
+            down[ch] = b >= 64
+            if not down[ch]:
+                for r in held[ch]:
+                    r[1] = s
+                held[ch] = []
+    for r in rows:                                       # open or held at the end: the file's last message
+        if r[1] is None:
+            r[1] = s
+    if len(rows) >= MAX_CLIP_NOTES:
+        raise ValueError(f"{len(rows)} notes in one file (fewer than 2^18 keep the synth's int32 voice sum exact)")
+    if not rows:
+        return np.zeros((0, 4), dtype=np.int64), 5 * ops.SYNTH_RATE
+    clip_len = max(r[1] for r in rows) + ops.SYNTH_RELEASE
+    if clip_len > MAX_CLIP_SAMPLES:
+        raise ValueError(f"a clip of {clip_len} samples (2^40 at most)")
+    notes = np.asarray(rows, dtype=np.int64)
+    return notes[np.argsort(notes[:, 0], kind="stable")], int(clip_len)
+
+
+def running_off_max(notes):
+    """The ``off_max`` column of ``ops.synth_windows`` for ONE clip's rows: the running maximum of s_off."""
+    return np.maximum.accumulate(np.asarray(notes, dtype=np.int64).reshape(-1, 4)[:, 1])
+
+
+def _upload_clips(clips, device):
+    """[(n_i, 4) note rows] -> (notes, off_max, note_ptr) device tensors of ``ops.synth_windows``."""
+    notes = np.concatenate([c.reshape(-1, 4) for c in clips]) if clips else np.zeros((0, 4), np.int64)
+    off_max = np.concatenate([running_off_max(c) for c in clips]) if clips else np.zeros(0, np.int64)
+    note_ptr = np.zeros(len(clips) + 1, dtype=np.int64)
+    np.cumsum([len(c) for c in clips], out=note_ptr[1:])
+    dev = torch.device(device)
+    return tuple(torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64)).to(dev) for x in (notes, off_max, note_ptr))
+
+
+def midi_to_wav(midi_input, wav_path, *, pedal=True, max_seconds=None, device="cuda"):
+    """Stands where ``FluidSynth.midi_to_audio`` stands upstream (GAN_DES/datasets.py:82): the whole clip of
+    ``midi_notes`` as a mono 16-bit 44 100 Hz WAV file, rendered by the integer synth in bounded chunks (one
+    ``ops.synth_windows`` window of 2^22 samples per launch); ``max_seconds`` cuts it.  Returns the samples written."""
+    notes, clip_len = midi_notes(midi_input, pedal=pedal)
+    total = clip_len
+    if max_seconds is not None:
+        total = max(1, min(total, int(max_seconds * ops.SYNTH_RATE)))
+    rows, off_max, note_ptr = _upload_clips([notes], device)
+    win_clip = torch.zeros(1, dtype=torch.int32, device=rows.device)
+    d = os.path.dirname(wav_path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(wav_path, "wb") as f:
+        f.write(util.wav_header(total, ops.SYNTH_RATE))
+        for first in range(0, total, _WAV_CHUNK):
+            count = min(_WAV_CHUNK, total - first)
+            start = torch.full((1,), first, dtype=torch.int64, device=rows.device)
+            pcm = ops.synth_windows(rows, off_max, note_ptr, win_clip, start, count)
+            f.write(pcm[0, :count].cpu().numpy().astype("<i2").tobytes())
+    return total
+
+
+def choose_windows(n, k):
+    """Which of a file's n windows an item keeps: all of them, or -- if there are more than k -- the k that upstream's
+    ``random.sample(splits, k)`` picks, in its order.  Sampling positions instead of the list draws the same numbers
+    from Python's global ``random`` stream and leaves it in the same state."""
+    return random.sample(range(n), k) if n > k else list(range(n))
+
+
+class MaestroDataset(torch.utils.data.Dataset):
+    """The reference's MAESTRO dataset (GAN_DES/datasets.py:55-100): item ``index`` = the (n, 128, 216) fp32 mel-dB
+    tensor, on ``device``, of at most ``k = batch_size`` five-second windows of MIDI file ``data[str(index)]`` of the
+    metadata JSON (``meta_data_file``, default ``{input_folder}/maestro-v3.0.0.json``).  ``INPUT_FOLDER``,
+    ``meta_data_file``, ``k`` and ``data`` are upstream's attributes; ``input_folder`` replaces the hard-wired path.
+
+    Per item: ``midi_notes`` on the file, ``util.song_windows(clip_len, 44100, 5, 5, mode="split")`` (upstream's
+    split_audio_data: the last window twice when the length is a multiple of five seconds, one short window for a clip
+    under five seconds), ``choose_windows``, then one synth launch for the chosen windows only and the mel chain of the
+    WAV route.  The audio is the package's integer synth, not FluidSynth's sound font (see the module docstring).
+    Use ``num_workers=0`` in a DataLoader: the items are device tensors."""
+
+    def __init__(self, batch_size, *, input_folder="../data/maestro-v3.0.0", meta_data_file=None, device="cuda",
+                 pedal=True, windows_per_chunk=64):
+        self.INPUT_FOLDER = input_folder
+        self.meta_data_file = meta_data_file if meta_data_file is not None else f"{input_folder}/maestro-v3.0.0.json"
+        self.k = batch_size
+        self.device, self.pedal = torch.device(device), pedal
+        self.windows_per_chunk = max(1, int(windows_per_chunk))
+        with open(self.meta_data_file) as json_file:
+            self.data = json.load(json_file)["midi_filename"]
+
+    def __len__(self):
+        return len(self.data)
+
+    def plan(self, index):
+        """(note rows, [(start, length) of the windows item ``index`` keeps]); draws from ``random`` as the item does."""
+        notes, clip_len = midi_notes(f"{self.INPUT_FOLDER}/{self.data[str(index)]}", pedal=self.pedal)
+        windows = util.song_windows(clip_len, ops.SYNTH_RATE, 5, 5, mode="split")
+        return notes, [windows[i] for i in choose_windows(len(windows), self.k)]
+
+    def spectrograms(self, indices=None):
+        """The items of ``indices`` (default: every file) concatenated -- what ``my_collate`` builds of them -- with ONE
+        synth launch for all windows of all files; the windows are drawn per file, in order."""
+        indices = range(len(self)) if indices is None else indices
+        plans = [self.plan(int(i)) for i in indices]
+        if not plans:
+            raise ValueError("spectrograms() of no file")
+        lengths = [length for _notes, wins in plans for _start, length in wins]
+        win_clip = np.concatenate([np.full(len(wins), c, dtype=np.int32) for c, (_n, wins) in enumerate(plans)])
+        win_start = np.asarray([start for _notes, wins in plans for start, _length in wins], dtype=np.int64)
+        rows, off_max, note_ptr = _upload_clips([notes for notes, _wins in plans], self.device)
+        # one launch renders every window at the longest length: what a shorter clip has beyond its end is silence
+        pcm = ops.synth_windows(rows, off_max, note_ptr, torch.from_numpy(win_clip).to(self.device),
+                                torch.from_numpy(win_start).to(self.device), max(lengths))
+        parts, a = [], 0
+        while a < len(lengths):                          # runs of one window length, bounded for the frame matrix
+            b = a + 1
+            while b < len(lengths) and lengths[b] == lengths[a] and b - a < self.windows_per_chunk:
+                b += 1
+            parts.append(util.melspectrogram_db_from_synth_windows(pcm[a:b], b - a, lengths[a], pcm.shape[1]))
+            a = b
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def __getitem__(self, index):
+        return self.spectrograms([index])
+
+
+def my_collate(batch):
+    """The reference's collate function (GAN_DES/datasets.py:94-100): items of different window counts, concatenated."""
+    return torch.cat(batch)

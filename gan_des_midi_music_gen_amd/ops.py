@@ -1215,6 +1215,42 @@ def synth_pcm(notes, n_notes, first, count, *, tables=None, out=None):
     return out
 
 
+def synth_windows(notes, off_max, note_ptr, win_clip, win_start, win_len, *, tables=None, out=None):
+    """W windows of F clips as 16-bit PCM in one launch (gdm_synth_windows, include/gdm.h): notes (n, 4) int64 rows
+    (s_on, s_off, pitch, velocity) in SAMPLES, the clips back to back and ascending in s_on within a clip; off_max (n,)
+    int64 the running maximum of s_off within each clip; note_ptr (F + 1,) int64; win_clip (W,) int32; win_start (W,)
+    int64; every window ``win_len`` samples long.  Returns the (W, out_stride) int16 device tensor, out_stride =
+    win_len rounded up to a multiple of 8 (or the row length of ``out``, a contiguous (W, out_stride) int16 tensor
+    with out_stride >= win_len and out_stride % 8 == 0); columns from win_len on are not written."""
+    _need_gpu(notes, off_max, note_ptr, win_clip, win_start)
+    n = notes.shape[0] if notes.dim() == 2 else -1
+    if notes.dtype != torch.int64 or notes.dim() != 2 or notes.shape[1] != 4 or not notes.is_contiguous():
+        raise GdmError("synth_windows: notes must be a contiguous (n, 4) int64 tensor")
+    if off_max.dtype != torch.int64 or off_max.shape != (n,) or not off_max.is_contiguous():
+        raise GdmError("synth_windows: off_max must be a contiguous (n,) int64 tensor")
+    if note_ptr.dtype != torch.int64 or note_ptr.dim() != 1 or note_ptr.numel() < 2 or not note_ptr.is_contiguous():
+        raise GdmError("synth_windows: note_ptr must be a contiguous int64 tensor of F + 1 offsets")
+    w = win_clip.numel()
+    if win_clip.dtype != torch.int32 or win_clip.dim() != 1 or not win_clip.is_contiguous() or \
+            win_start.dtype != torch.int64 or win_start.shape != (w,) or not win_start.is_contiguous():
+        raise GdmError("synth_windows: win_clip (W,) int32 and win_start (W,) int64 must be contiguous and of one length")
+    wave, inc = synth_tables(notes.device) if tables is None else tables
+    _need_gpu(wave, inc)
+    if wave.dtype != torch.int16 or wave.shape != (SYNTH_WAVE,) or inc.dtype != torch.int32 or inc.shape != (128,) or \
+            not wave.is_contiguous() or not inc.is_contiguous():
+        raise GdmError(f"synth_windows: tables must be (wave int16[{SYNTH_WAVE}], inc int32[128] holding uint32 bits)")
+    win_len = int(win_len)
+    if out is None:
+        out = torch.empty((w, (max(win_len, 0) + 7) // 8 * 8), dtype=torch.int16, device=notes.device)
+    else:
+        _need_gpu(out)
+        if out.dtype != torch.int16 or out.dim() != 2 or out.shape[0] != w or not out.is_contiguous():
+            raise GdmError(f"synth_windows: out must be a contiguous ({w}, out_stride) int16 tensor")
+    _call("gdm_synth_windows", _p(notes), _p(off_max), n, _p(note_ptr), note_ptr.numel() - 1, _p(win_clip),
+          _p(win_start), w, win_len, out.shape[1], _p(wave), _p(inc), _p(out), _stream())
+    return out
+
+
 # ---- mel-spectrogram featuriser kernels (GAN_DES/util.py:37-61) -------------------------------------------------------
 def stft_frames(x, hop, n_fft):
     """x (B, L) fp32 -> (B * frames, n_fft) centred, reflect-padded frames; frames = 1 + L // hop."""

@@ -105,6 +105,25 @@ def melspectrogram_db_from_pcm(pcm, wav, mix, starts, win_len, sr=44100, n_fft=2
     return _db_from_frames(frames_m, len(starts), frames, sr, n_fft, n_mels, fmin, fmax, top_db)
 
 
+def melspectrogram_db_from_synth_windows(pcm, n_windows, win_len, out_stride, sr=44100, n_fft=2048, n_mels=128, fmin=20,
+                                         fmax=8300, top_db=80):
+    """The mel-dB tensors of the windows ``ops.synth_windows`` rendered: ``pcm`` is its (n_windows, out_stride) int16
+    buffer, read as one mono 16-bit song whose windows start ``out_stride`` samples apart; ``win_len`` is the length a
+    window has in the clip, cut to ``mel_geometry(win_len)`` as ``get_melspectrogram_db_tensor`` cuts it ->
+    (n_windows, n_mels, 216) dB.  The chain of the WAV route (``melspectrogram_db_from_pcm``) from its first launch on,
+    so the result is the one a WAV file holding these samples gives."""
+    n_windows, out_stride = int(n_windows), int(out_stride)
+    if pcm.dtype != torch.int16 or pcm.numel() != n_windows * out_stride or not pcm.is_contiguous():
+        raise ops.GdmError(f"melspectrogram_db_from_synth_windows: pcm must be a contiguous ({n_windows}, {out_stride}) "
+                           "int16 tensor")
+    hop, kept = mel_geometry(int(win_len))
+    if kept > out_stride:
+        raise ValueError(f"windows of {win_len} samples do not fit rows of {out_stride}")
+    frames_m, frames = ops.pcm_stft_frames(pcm.view(torch.uint8).reshape(-1), ops.PCM_S16, 1, 0, n_windows * out_stride,
+                                           0, out_stride, n_windows, -1, kept, hop, n_fft)
+    return _db_from_frames(frames_m, n_windows, frames, sr, n_fft, n_mels, fmin, fmax, top_db)
+
+
 def _window_table(starts):
     """Window starts -> (start0, stride, n_regular, tail_start) of gdm_pcm_stft_frames (scalars, so that the C entry can
     check every window against the buffer)."""
@@ -210,6 +229,13 @@ def load_wav(path_or_bytes):
     if n_frames == 0:
         raise ValueError("empty data chunk")
     return WavData(data[:n_frames * block_align], fmt, channels, rate, n_frames)
+
+
+def wav_header(n_samples, sample_rate=44100):
+    """The 44 bytes in front of ``n_samples`` mono 16-bit samples: RIFF/WAVE, one fmt chunk, the data chunk's head."""
+    return (b"RIFF" + struct.pack("<I", 36 + 2 * n_samples) + b"WAVEfmt " +
+            struct.pack("<IHHIIHH", 16, 1, 1, sample_rate, 2 * sample_rate, 2, 16) +
+            b"data" + struct.pack("<I", 2 * n_samples))
 
 
 def upload_pcm(wav, device="cuda"):

@@ -601,7 +601,42 @@ int gdm_pcm_stft_frames(const void* pcm, int fmt, int channels, int mix, int64_t
  *   gdm_pcm_stft_frames.  A clip with n_notes = 0 (or clip_len <= 1024) gives zero frames.  One workgroup per (b, f).
  * gdm_synth_pcm: out[i] = sample(first + i), i < count, of ONE clip (notes, n_notes point at it), as 16-bit PCM.
  * Checked before the launch: notes_cap <= 5000 (the voice list in LDS), alignment (frames / out: 16 bytes), the sample
- * range.  n_notes is clamped to [0, notes_cap] on the device; no other device value forms an address.              */
+ * range.  n_notes is clamped to [0, notes_cap] on the device; no other device value forms an address.
+ *
+ * gdm_synth_windows: W windows of F clips of any length as 16-bit PCM, one launch (a MIDI performance rendered for the
+ *   mel featuriser: datasets.MaestroDataset, datasets.midi_to_wav).  notes (n_total, 4) i64 = (s_on, s_off, pitch,
+ *   velocity) with the times IN SAMPLES at 44 100 Hz, the rows of the F clips back to back, note_ptr (F + 1) i64 the
+ *   offset of each clip's rows; within a clip the rows ascend in s_on, and off_max[k] is the maximum of s_off over the
+ *   clip's rows up to and including k (non-decreasing within a clip).  Window w is samples [win_start[w], win_start[w]
+ *   + win_len) of clip win_clip[w] (i32):
+ *     out[w * out_stride + i] = the int32 sum over the clip's voices of the formula above at s = win_start[w] + i,
+ *     clamped to [-32768, 32767], for i < win_len; out[w * out_stride + win_len ..] is not written.
+ *   A sample where no voice sounds (before the first note, beyond the clip's end, a clip without rows) is 0.
+ *   One workgroup per (2048 samples, window).  It does not scan the clip: rows from the first with s_on > hi on, and
+ *   rows before the first with off_max + R > lo, cannot sound in its samples [lo, hi]; two binary searches find both,
+ *   and the rows between are taken in tiles of GDM_SYNTH_TILE, each filtered into a fixed list in LDS.  No limit on
+ *   the rows of a clip or on simultaneous voices; the integer sum does not depend on the order, so every bit is defined.
+ *   The int32 sum is the caller's to keep: fewer than 2^18 voices at one sample cannot overflow it (2^18 * 8128 < 2^31).
+ *   Checked before the launch: null pointers (notes / off_max may be null iff n_total = 0), alignment (out: 16 bytes,
+ *   every table: its element), 1 <= F, 1 <= W <= 65535, 1 <= win_len <= 2^30, out_stride >= win_len and
+ *   out_stride % 8 == 0, n_total >= 0.  On the device win_clip is clamped to [0, F), both ends of a clip's row range
+ *   to [0, n_total] with start <= end, the searches stay inside that range, and win_start is taken within +-2^62; no
+ *   other value read from device memory forms an address.  If the rows do not ascend or off_max is not the running
+ *   maximum, voices may be missed, nothing else.
+ *
+ * A Standard MIDI File -> those rows (datasets.midi_notes; host, exact integer arithmetic):
+ *   time: tracks merged stably by absolute tick; with U = the running sum of delta_ticks * tempo in force (us per beat;
+ *     500 000 until the first set_tempo; a set_tempo applies to the messages after it), a message sounds at sample
+ *     U * 441 / (ticks_per_beat * 10000), rounded down.  Tempo 1 000 000 at 480 ticks per beat gives sample(tick) above.
+ *   pairing: a note_on with velocity > 0 opens a note on its (channel, pitch); a note_off, or a note_on with velocity
+ *     0, closes the OLDEST open note of that (channel, pitch) and is ignored when there is none; notes still open at
+ *     the end close at the file's last message (the end_of_track with the largest tick included).
+ *   sustain pedal (controller 64 per channel, value >= 64 = down): a close that arrives while the pedal is down is
+ *     deferred; the note ends at the earliest of the pedal's release on its channel, the next note_on of its
+ *     (channel, pitch), and the file's last message.
+ *   All channels sound the one voice, program changes are ignored, pitch and velocity are kept as stored.
+ *   clip_len = max(s_off) + GDM_SYNTH_RELEASE, or 5 * 44100 for a file without notes; refused: U * 441 >= 2^63,
+ *   clip_len > 2^40, 2^18 notes or more.                                                                           */
 #define GDM_DES_NOTES_MAX 5000
 #define GDM_DES_NOTES_ENODE 1  /* a note for a node without note level (KeyError upstream) */
 #define GDM_DES_NOTES_EPITCH 2 /* note outside 0..127 (mido refuses the message) */
@@ -612,6 +647,7 @@ int gdm_pcm_stft_frames(const void* pcm, int fmt, int channels, int mix, int64_t
 #define GDM_SYNTH_WAVE 2048
 #define GDM_SYNTH_FRAMES 216
 #define GDM_SYNTH_NFFT 2048
+#define GDM_SYNTH_TILE 1024 /* rows a gdm_synth_windows workgroup filters at a time (16 KB of LDS) */
 int gdm_des_log_to_notes(const double* value, const int64_t* event_id, const int32_t* node, const int32_t* kind,
                          const int64_t* rec_ptr, int64_t n_records, const int32_t* note_levels, int dim, int B,
                          int64_t* notes, int notes_cap, int32_t* n_notes, int64_t* clip_len, int32_t* status,
@@ -620,6 +656,9 @@ int gdm_synth_frames(const int64_t* notes, int notes_cap, const int32_t* n_notes
                      const int16_t* wave, const uint32_t* inc, float* frames, void* stream);
 int gdm_synth_pcm(const int64_t* notes, int notes_cap, const int32_t* n_notes, const int16_t* wave, const uint32_t* inc,
                   int64_t first, int64_t count, int16_t* out, void* stream);
+int gdm_synth_windows(const int64_t* notes, const int64_t* off_max, int64_t n_total, const int64_t* note_ptr, int F,
+                      const int32_t* win_clip, const int64_t* win_start, int W, int64_t win_len, int64_t out_stride,
+                      const int16_t* wave, const uint32_t* inc, int16_t* out, void* stream);
 
 #ifdef __cplusplus
 }
