@@ -46,6 +46,16 @@ __global__ __launch_bounds__(256) void power_spectrum_kernel(const float* __rest
   }
 }
 
+// NaN as torch.clamp / amax / maximum treat it (AmplitudeToDB): it passes the amin clamp and takes over the window maximum,
+// hence the floor.  The library is built with -fno-honor-nans -- fmaxf drops a NaN operand and a float select may assume
+// there is none -- so NaN is told by its bits and chosen among bit patterns; NaN-free values take the fmaxf they always took.
+__device__ __forceinline__ uint32_t f2u(float v) { return __builtin_bit_cast(uint32_t, v); }
+__device__ __forceinline__ bool nan_bits(uint32_t u) { return (u & 0x7fffffffu) > 0x7f800000u; }
+__device__ __forceinline__ float max_nan(float a, float b) {
+  const uint32_t ua = f2u(a), ub = f2u(b), um = f2u(fmaxf(a, b));
+  return __builtin_bit_cast(float, nan_bits(ua) ? ua : nan_bits(ub) ? ub : um);
+}
+
 // One workgroup per window: mel (frames, n_mels) -> dB, raised to (window max - top_db), written as (n_mels, frames).
 __global__ __launch_bounds__(1024) void power_to_db_kernel(const float* __restrict__ mel, int frames, int n_mels,
                                                            float top_db, float amin, float* __restrict__ out) {
@@ -56,21 +66,24 @@ __global__ __launch_bounds__(1024) void power_to_db_kernel(const float* __restri
   float mx = -INFINITY;
   for (int i = t; i < n; i += 1024) {
     const int f = i / n_mels, k = i % n_mels;              // coalesced read along the mel axis
-    const float d = 10.0f * log10f(fmaxf(m[i], amin));
+    const float p = m[i];
+    const uint32_t up = f2u(p), ud = f2u(10.0f * log10f(fmaxf(p, amin)));
+    const float d = __builtin_bit_cast(float, nan_bits(up) ? up : ud);
     db_s[k * ld + f] = d;
-    mx = fmaxf(mx, d);
+    mx = max_nan(mx, d);
   }
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  for (int o = 32; o > 0; o >>= 1) mx = max_nan(mx, __shfl_xor(mx, o, 64));
   if ((t & 63) == 0) red[t >> 6] = mx;
   __syncthreads();
   mx = red[0];
 #pragma unroll
-  for (int w = 1; w < 16; ++w) mx = fmaxf(mx, red[w]);
-  const float floor_db = top_db >= 0.f ? mx - top_db : -INFINITY;
+  for (int w = 1; w < 16; ++w) mx = max_nan(mx, red[w]);
+  const uint32_t um = f2u(mx), uf = f2u(top_db >= 0.f ? mx - top_db : -INFINITY);
+  const float floor_db = __builtin_bit_cast(float, top_db >= 0.f && nan_bits(um) ? um : uf);
   float* o = out + (int64_t)blockIdx.x * n;
   for (int i = t; i < n; i += 1024) {
     const int k = i / frames, f = i % frames;              // coalesced write along the time axis
-    o[i] = fmaxf(db_s[k * ld + f], floor_db);
+    o[i] = max_nan(db_s[k * ld + f], floor_db);
   }
 }
 

@@ -42,7 +42,9 @@ def _dft_matrix(n_fft, device):
         # reduce k*n modulo N in integers first: the angle stays exact for large products
         kn = (torch.outer(n.long(), k.long()) % n_fft).to(torch.float64)
         ang = 2.0 * math.pi * kn / n_fft
-        m = torch.cat([torch.cos(ang), torch.sin(ang)], dim=1) * win[:, None]
+        # (sin(float64 pi) is 1.2e-16, not 0: the sine columns k = 0 and k = N/2 are exact zeros)
+        sin = torch.where((2.0 * kn) % n_fft == 0, torch.zeros_like(ang), torch.sin(ang))
+        m = torch.cat([torch.cos(ang), sin], dim=1) * win[:, None]
         _CONST[key] = m.to(torch.float32).to(device).contiguous()
     return _CONST[key]
 
