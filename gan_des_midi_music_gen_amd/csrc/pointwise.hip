@@ -104,7 +104,8 @@ __global__ void adam_prep_kernel(float* __restrict__ hyper) {
 // Instead of two transposing passes around Adam (gradient -> parameter order, new weight -> operand order: 235 MB of
 // HBM traffic per step) the transposes happen inside this kernel, through LDS: a workgroup owns a (128 p x 32 c) tile
 // of one row n, reads the gradient tile along c (128-byte runs), updates p/m/v along p (512-byte runs) and writes the
-// new weight back along c.
+// new weight back along c.  With C == 32 a tile of the gradient and of the copy is one contiguous run, moved 16 bytes
+// per access (adam_pc.h).
 // (the Adam arithmetic is the same expression order as adam_dev_kernel: bit-identical results)
 template <typename TS>
 __global__ __launch_bounds__(256) void adam_dev_pc_kernel(float* __restrict__ p, const float* __restrict__ g_pc,
@@ -447,7 +448,7 @@ extern "C" int gdm_adam_step_dev_pc(float* p, const float* g_pc, float* m, float
   hipStream_t s = (hipStream_t)stream;
   if (advance_step) hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, s, hyper);
   const dim3 grid((P + 127) / 128, (C + 31) / 32, N);
-  const int vec_ok = (P % 4 == 0) && ((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+  const int vec_ok = adam_pc_flags(p, m, v, g_pc, shadow_pc, C, P);
   if (shadow_dtype == GDM_BF16)
     hipLaunchKernelGGL(adam_dev_pc_kernel<__bf16>, grid, dim3(256), 0, s, p, g_pc, m, v, C, P, (__bf16*)shadow_pc, hyper,
                        vec_ok);

@@ -40,7 +40,11 @@ __global__ __launch_bounds__(256, 8) void simnn_adam_kernel(float* __restrict__ 
   STAMP_DECL;
   // hyper's step counter and BOTH slots are read at once (one round trip, not a dependent chain of three -- with 2 k
   // workgroups streaming, a round trip is ~2 us), and a tile workgroup looks at them only after it has issued its
-  // gradient gather.
+  // gradient gather and the p / m / v loads of its first rows (adam_pc.h: the other rows' loads are pipelined behind
+  // them, so a workgroup waits for HBM once, not for the gradient and then again for p / m / v).
+  // Resource report (-Rpass-analysis=kernel-resource-usage, gfx950): bf16 copy 64 VGPRs, no scratch, no VGPR spill,
+  // 2 SGPR spills, 8 waves per SIMD; fp32 copy 63 VGPRs, 2 VGPRs spilled (12 bytes of scratch per lane: one address,
+  // stored once per thread and reloaded by the scalar fallback only), 8 waves per SIMD.
   const int step = __float_as_int(hyper[0]) + 1;
   const int tag0 = rec[REC_SLOT0], tag1 = rec[REC_SLOT0 + 4];
   const float ss0 = __int_as_float(rec[REC_SLOT0 + 1]), bq0 = __int_as_float(rec[REC_SLOT0 + 2]);
@@ -139,10 +143,11 @@ __global__ __launch_bounds__(256, 8) void simnn_adam_kernel(float* __restrict__ 
   }
   {
     const int bx = blk % tiles_x, by = (blk / tiles_x) % tiles_y, bz = blk / (tiles_x * tiles_y);
-    adam_pc_gather(tile, g_pc, C, P, bx, by, bz);
+    AdamPcEarly early;
+    adam_pc_gather(tile, g_pc, p, m, v, C, P, vec_ok, bx, by, bz, early);
     resolve();
     __syncthreads();
-    adam_pc_update<T>(tile, p, m, v, C, P, shadow_pc, hyper, vec_ok, step_size, bc2_sqrt, bx, by, bz);
+    adam_pc_update<T>(tile, p, m, v, C, P, shadow_pc, hyper, vec_ok, step_size, bc2_sqrt, bx, by, bz, early);
   }
   __syncthreads();
   STAMP(4);
@@ -176,7 +181,7 @@ extern "C" int gdm_simnn_adam_step(float* p_big, const float* g_big_pc, float* m
   const int tx = (P + 127) / 128, ty = (C + 31) / 32;
   const int64_t nbig = (int64_t)tx * ty * N;
   GDM_REQUIRE(nbig < ((int64_t)1 << 30), "gdm_simnn_adam_step: parameter too large");
-  const int vec_ok = (P % 4 == 0) && ((((uintptr_t)p_big | (uintptr_t)m_big | (uintptr_t)v_big) & 15) == 0);
+  const int vec_ok = adam_pc_flags(p_big, m_big, v_big, g_big_pc, shadow_pc, C, P);
   const int small_vec_ok = ((((uintptr_t)p_small | (uintptr_t)g_small | (uintptr_t)m_small | (uintptr_t)v_small) & 15) == 0);
   DISPATCH_T(dtype, hipLaunchKernelGGL(simnn_adam_kernel<T>, dim3((unsigned)nbig), dim3(256), 0, (hipStream_t)stream, p_big,
                                        g_big_pc, m_big, v_big, C, P, (T*)shadow_pc, vec_ok, tx, ty, small_vec_ok, p_small, g_small,
