@@ -10,6 +10,7 @@ Same public names, constructor signatures, state_dict keys and training-loop sem
     generate_song(model_folder, bridge="des")                     SIMNN.py:201-216
     des_fake_provider(start=0, end=216, batched=False)            (this build: the DES bridge as a fake provider)
     sample_matrices(gen, n_samples)                               (this build: the batched form of generate_song)
+    generate_songs(model, n_samples, out_dir=...)                 (this build: n clips, each with its MIDI and WAV file)
     train(...)  /  python -m gan_des_midi_music_gen_amd.SIMNN     SIMNN.py:234-348 (the __main__ loop)
 
 The module tree holds ordinary ``nn.ConvTranspose2d / nn.BatchNorm2d / nn.Conv2d / nn.Linear`` children purely as
@@ -184,20 +185,15 @@ def generate_song(model_folder, device=None, bridge=None, compute_dtype=None, *,
 _WAV_CHUNK = 1 << 22          # samples rendered per gdm_synth_pcm launch (8 MB of PCM)
 
 
-def _des_song(matrix, midi_path, wav_path, max_seconds, batched=False):
-    """matrix_to_wav(simulate="des" / "des_batch") for one matrix, keeping the note list for the two files."""
-    from . import matrix_sim_process as msp, ops, sim_log_process_music as slpm, sim_log_to_midi, util
-    if batched:
-        mel, (notes, n_notes, clip_len) = msp._batch_to_mel(msp.batched_prologue_wav(matrix, 20, None), 200000)
-    else:
-        h = msp._wav_scan(matrix, 20)
-        specs = msp._interleaved_specs(h, msp._wav_draws,
-                                       lambda h_, i, r, src, sd: msp._wav_spec(h_, i, r, src, sd, None))
-        mel, (notes, n_notes, clip_len) = msp._specs_to_mel(specs, matrix.device, 200000)
+def _write_clip(notes, n_notes, i, count, total, midi_path, wav_path, max_seconds):
+    """The two files of clip i of a batch of note lists (notes, n_notes: device tensors; count = int(n_notes[i]) and
+    total = int(clip_len[i]) on the host): the MIDI file of its notes and its audio, mono 16-bit at 44 100 Hz, rendered
+    on the device in bounded chunks.  A blank clip is the reference's five seconds of silence; ``max_seconds`` cuts
+    the audio."""
+    from . import ops, sim_log_process_music as slpm, sim_log_to_midi, util
     if midi_path is not None:
-        sim_log_to_midi.write_midi(slpm.notes_to_track(notes[0, :int(n_notes[0])].cpu().numpy()), midi_path)
+        sim_log_to_midi.write_midi(slpm.notes_to_track(notes[i, :count].cpu().numpy()), midi_path)
     if wav_path is not None:
-        total = int(clip_len[0])
         blank = total == 0
         if blank:
             total = 5 * ops.SYNTH_RATE                                   # matrix_sim_process.py:103: np.zeros(5 * 44100)
@@ -209,11 +205,64 @@ def _des_song(matrix, midi_path, wav_path, max_seconds, batched=False):
         with open(wav_path, "wb") as f:
             f.write(util.wav_header(total, ops.SYNTH_RATE))
             for first in range(0, total, _WAV_CHUNK):
-                count = min(_WAV_CHUNK, total - first)
-                pcm = torch.zeros(count, dtype=torch.int16) if blank else \
-                    ops.synth_pcm(notes[:1], n_notes[:1], first, count).cpu()
+                chunk = min(_WAV_CHUNK, total - first)
+                pcm = torch.zeros(chunk, dtype=torch.int16) if blank else \
+                    ops.synth_pcm(notes[i:i + 1], n_notes[i:i + 1], first, chunk).cpu()
                 f.write(pcm.numpy().astype("<i2").tobytes())
+
+
+def _des_mel(matrices, batched):
+    """matrix_to_wav(simulate="des" / "des_batch") on (B, 20, 20) matrices, keeping the note lists:
+    -> (mel (B, 128, 216), (notes, n_notes, clip_len))."""
+    from . import matrix_sim_process as msp
+    if batched:
+        return msp._batch_to_mel(msp.batched_prologue_wav(matrices, 20, None), 200000)
+    h = msp._wav_scan(matrices, 20)
+    specs = msp._interleaved_specs(h, msp._wav_draws, lambda h_, i, r, src, sd: msp._wav_spec(h_, i, r, src, sd, None))
+    return msp._specs_to_mel(specs, matrices.device, 200000)
+
+
+def _des_song(matrix, midi_path, wav_path, max_seconds, batched=False):
+    """matrix_to_wav(simulate="des" / "des_batch") for one matrix, keeping the note list for the two files."""
+    mel, (notes, n_notes, clip_len) = _des_mel(matrix, batched)
+    _write_clip(notes, n_notes, 0, int(n_notes[0]), int(clip_len[0]), midi_path, wav_path, max_seconds)
     return mel[0]
+
+
+class SongBatch:
+    """What ``generate_songs`` returns: ``mel`` (n, 128, 216) dB on the device; ``notes`` (n, cap, 4), ``n_notes`` (n,),
+    ``clip_len`` (n,): the note lists and clip lengths in samples, device tensors; ``midi_paths``, ``wav_paths``: the
+    files written, None where none was."""
+
+    def __init__(self, mel, notes, n_notes, clip_len, midi_paths, wav_paths):
+        self.mel, self.notes, self.n_notes, self.clip_len = mel, notes, n_notes, clip_len
+        self.midi_paths, self.wav_paths = midi_paths, wav_paths
+
+
+def generate_songs(model, n_samples=None, *, noise=None, bridge="des_batch", out_dir=None, midi=True, wav=True,
+                   max_seconds=None, compute_dtype="bf16", device=None):
+    """``generate_song`` for a batch: n clips from a trained generator, each with its MIDI file and its audio.
+
+    model: a ``Generator`` or the path of a ``gen_*.pt`` checkpoint.  ``sample_matrices`` draws the n matrices (one
+    launch), then bridge "des_batch" simulates all of them in one device launch
+    (matrix_sim_process._batch_to_mel(batched_prologue_wav(...))) and "des" keeps the reference's interleaved order
+    (see matrix_sim_process for what differs).  With ``out_dir`` clip i is written to ``out_dir/song_{i:04d}.mid`` (midi)
+    and ``.wav`` (wav) exactly as ``generate_song`` writes its one clip; with out_dir=None nothing is written and the
+    path lists hold None.  -> SongBatch."""
+    if bridge not in ("des", "des_batch"):
+        raise ValueError(f"unknown bridge {bridge!r} (the built-in ones are \"des\" and \"des_batch\")")
+    matrices = sample_matrices(model, n_samples, noise=noise, compute_dtype=compute_dtype, device=device)
+    n = matrices.shape[0]
+    mel, (notes, n_notes, clip_len) = _des_mel(matrices.reshape(n, 20, 20), bridge == "des_batch")
+    midi_paths, wav_paths = [None] * n, [None] * n
+    if out_dir is not None:
+        counts, lengths = n_notes.cpu(), clip_len.cpu()                  # one read-back for all clips
+        for i in range(n):
+            stem = os.path.join(out_dir, f"song_{i:04d}")
+            midi_paths[i] = stem + ".mid" if midi else None
+            wav_paths[i] = stem + ".wav" if wav else None
+            _write_clip(notes, n_notes, i, int(counts[i]), int(lengths[i]), midi_paths[i], wav_paths[i], max_seconds)
+    return SongBatch(mel, notes, n_notes, clip_len, midi_paths, wav_paths)
 
 
 def des_fake_provider(start=0, end=216, max_events=200000, batched=False):
@@ -369,7 +418,8 @@ def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5,
 
 
 def main(argv=None):
-    """``python -m gan_des_midi_music_gen_amd.SIMNN``: the reference's ``__main__`` training loop."""
+    """``python -m gan_des_midi_music_gen_amd.SIMNN``: the reference's ``__main__`` training loop, or with
+    ``--generate N --checkpoint gen_*.pt --out-dir DIR`` N clips from a trained generator."""
     import argparse
     ap = argparse.ArgumentParser(description="Train model 1 (the reference's SIMNN.py __main__ loop).")
     ap.add_argument("--audio-file", default=None, help="WAV file to train on (default: seeded synthetic windows)")
@@ -382,7 +432,24 @@ def main(argv=None):
     ap.add_argument("--fake-provider", choices=["des", "des_batch"], default=None,
                     help="des: fakes from the built-in DES bridge; des_batch: the same with the simulation batched on "
                          "the device (default: seeded synthetic windows)")
+    ap.add_argument("--generate", type=int, default=None, metavar="N",
+                    help="do not train: write N clips (MIDI + WAV) from --checkpoint into --out-dir (generate_songs)")
+    ap.add_argument("--checkpoint", default=None, help="gen_*.pt generator checkpoint for --generate")
+    ap.add_argument("--out-dir", default="adj_sim_outputs/songs", help="where --generate writes song_NNNN.mid / .wav")
+    ap.add_argument("--max-seconds", type=float, default=None, help="cut the clips of --generate")
+    ap.add_argument("--seed", type=int, default=None, help="seed of --generate (torch and numpy)")
     a = ap.parse_args(argv)
+    if a.generate is not None:
+        if a.checkpoint is None or a.generate < 1:
+            ap.error("--generate N needs N >= 1 and --checkpoint gen_*.pt")
+        if a.seed is not None:
+            import numpy as np
+            torch.manual_seed(a.seed)
+            np.random.seed(a.seed)
+        songs = generate_songs(a.checkpoint, a.generate, out_dir=a.out_dir, max_seconds=a.max_seconds)
+        for path in (p for pair in zip(songs.midi_paths, songs.wav_paths) for p in pair):
+            print(path)
+        return
     train(audio_file=a.audio_file, n_epochs=a.epochs, batch_size=a.batch_size, max_steps=a.max_steps,
           save=not a.no_save, fake_provider=a.fake_provider, maestro_dir=a.maestro_dir)
 

@@ -37,6 +37,12 @@ class ConcatJob(_c.Structure):
     _fields_ = [("a", _P), ("b", _P), ("out", _P), ("M", _I), ("Ka", _I), ("Kb", _I)]
 
 
+class MmganGenEvalJob(_c.Structure):
+    """gdm_mmgan_gen_eval_job (include/gdm.h)."""
+    _fields_ = [("noise", _P), ("input", _P), ("pack", _P), ("pack_bytes", _Z), ("out", _P), ("tap_y", _P * 4),
+                ("tap_a", _P * 3)] + [(n, _I) for n in ("B", "z", "in_", "input_stride", "n4")]
+
+
 # name -> (restype, argtypes); must list every function declared in include/gdm.h (tests/test_abi.py checks that)
 SIGNATURES = {
     "gdm_last_error": (_c.c_char_p, []),
@@ -107,6 +113,10 @@ SIGNATURES = {
                                  _P]),
     "gdm_dcnn_fused_adam_crit": (_I, [_P, _I, _P, _P, _I, _I, _F, _F, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P,
                                       _Z, _P]),
+    "gdm_mmgan_gen_eval_supported": (_I, [_I, _I, _I, _I, _I]),
+    "gdm_mmgan_gen_eval_pack_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "gdm_mmgan_gen_eval_pack": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
+    "gdm_mmgan_gen_eval": (_I, [_P, _I, _I, _I, _I, _P]),
     "gdm_im2col": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "gdm_col2im": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     "gdm_permute_pc": (_I, [_P, _I, _I, _I, _I, _P, _I, _P]),

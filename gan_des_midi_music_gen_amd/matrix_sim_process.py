@@ -2,6 +2,8 @@
 
     matrix_to_midi(gen1_output, gen2_output, adj_size=(32,32), instrument=None, start=0, end=150, count=0,
                    generate=False)                      MMGAN_MIDI_DES/matrix_sim_process.py:15-195
+    matrix_to_midis(gen1_output, gen2_output, adj_size, instrument, start, end, simulate="des_batch", midi_paths=None)
+                                                        the generate=True route for a batch: every sample's track
     matrix_to_wav(matrices, size=20, use_same_instrument=None, start=0, end=174, device='cpu')
                                                         GAN_DES/matrix_sim_process.py:17-137
 
@@ -126,6 +128,8 @@ def _midi_draws(h, i):
 def _midi_spec(h, i, routing, src, seeds, instrument):
     dim = h["dim"]
     p = h["g2"][i]
+    if isinstance(instrument, (list, tuple, np.ndarray)):             # matrix_to_midis: one entry per sample
+        instrument = instrument[i]
     d_src = (np.abs(p[1] * 50), np.abs(p[2] * 50))
     d_srv = (np.abs(p[3] * 10), np.abs(p[4] * 10))
     dist = [["normal", *(d_src if src[k] else d_srv)] for k in range(dim)]
@@ -305,28 +309,40 @@ def matrix_to_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None,
     return midi_rolls, failed
 
 
-def _matrix_to_midi_des(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor, midi_path,
-                        max_events):
+def _des_run(gen1_output, gen2_output, adj_size, instrument, start, end, generate, max_events, raise_for_status=True):
+    """The body "des" shares between ``matrix_to_midi`` and ``matrix_to_midis`` -> (planes on the device, tracks, status
+    (B,), reasons (None or why the simulation failed), ok, save)."""
     from . import sim_log_to_midi, simulation_v3
     _check_midi_window(start, end)
     h = _midi_scan(gen1_output, gen2_output, adj_size)
     if h["g2"].shape[1] < 16:
         raise ops.GdmError("matrix_to_midi: gen2_output needs at least 16 columns (gen2_output[10:16] drive the MIDI)")
     specs = _interleaved_specs(h, _midi_draws, lambda h_, i, r, src, sd: _midi_spec(h_, i, r, src, sd, instrument))
-    logs, ok, insts, notes = [], [], [], []
+    logs, ok, insts, notes, reasons = [], [], [], [], []
     for spec in specs:
         try:
             log, _reason = simulation_v3.run_spec(spec, max_events=max_events)
             ok.append(True)
-        except (ValueError, KeyError):
+            reasons.append(None)
+        except (ValueError, KeyError) as e:
             log = np.zeros(0, dtype=simulation_v3.EVENT_DTYPE)
             ok.append(False)
+            reasons.append(f"error ({e})")
         logs.append(log)
         insts.append(spec.instruments)
         notes.append(spec.note_levels)
     save = [good and (bool(generate) or sim_log_to_midi.lines_read(len(lg)) % 100 == 0) for good, lg in zip(ok, logs)]
-    rolls, tracks = sim_log_to_midi.log_to_rolls(logs, h["g2"][:, 10:], insts, notes, start=start, end=end, save=save,
-                                                 device=h["g1"].device)
+    rolls, tracks, status = sim_log_to_midi.log_to_rolls(logs, h["g2"][:, 10:], insts, notes, start=start, end=end,
+                                                         save=save, device=h["g1"].device, return_status=True,
+                                                         raise_for_status=raise_for_status)
+    return rolls, tracks, status, reasons, ok, save
+
+
+def _matrix_to_midi_des(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor, midi_path,
+                        max_events):
+    from . import sim_log_to_midi
+    rolls, tracks, _status, _reasons, ok, save = _des_run(gen1_output, gen2_output, adj_size, instrument, start, end,
+                                                          generate, max_events)
     failed = len(ok) - sum(ok)
     if generate:
         done = [i for i, sv in enumerate(save) if sv]
@@ -347,8 +363,10 @@ def _check_midi_window(start, end):
                          "final slice does not leave end - start columns; use start == 0 or end >= 128)")
 
 
-def _matrix_to_midi_des_batch(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor,
-                              midi_path, max_events):
+def _des_batch_run(gen1_output, gen2_output, adj_size, instrument, start, end, generate, max_events):
+    """The body "des_batch" shares between ``matrix_to_midi`` and ``matrix_to_midis``: batched prologue, simulator, one
+    ``des_log_to_roll`` launch, ONE read-back -> (planes (B,2,128,W) on the device; status, track_len, good, save, stop
+    (B,) and tracks (B, cap, 4) int32 host arrays)."""
     from . import sim_log_to_midi
     _check_midi_window(start, end)
     pro = batched_prologue_midi(gen1_output, gen2_output, adj_size, instrument)
@@ -365,9 +383,19 @@ def _matrix_to_midi_des_batch(gen1_output, gen2_output, adj_size, instrument, st
         log.value, log.event_id, log.node, log.kind, log.rec_ptr, tails, torch.from_numpy(pro.instruments).to(dev),
         torch.from_numpy(pro.note_levels).to(dev), save, start, end)
     # the one read-back: stop reasons with the tracks
-    words = torch.cat([status, track_len, good.to(torch.int32), save, track.reshape(-1)]).cpu().numpy()
+    words = torch.cat([status, track_len, good.to(torch.int32), save, log.stop_reason.to(torch.int32),
+                       track.reshape(-1)]).cpu().numpy()
     b = h["b"]
-    status, track_len, good, save = words[:b], words[b:2 * b], words[2 * b:3 * b], words[3 * b:4 * b]
+    status, track_len, good, save, stop = (words[k * b:(k + 1) * b] for k in range(5))
+    return planes, status, track_len, good, save, stop, words[5 * b:].reshape(b, ops.DES_MIDI_TRACK_CAP, 4)
+
+
+def _matrix_to_midi_des_batch(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor,
+                              midi_path, max_events):
+    from . import sim_log_to_midi
+    planes, status, track_len, good, save, _stop, tracks = _des_batch_run(gen1_output, gen2_output, adj_size, instrument,
+                                                                          start, end, generate, max_events)
+    b = len(status)
     for i in range(b):
         if status[i] >> 8:
             raise ValueError(f"Error in processing log file (sample {i}: {ops.DES_MIDI_ERRORS[int(status[i]) >> 8]})")
@@ -376,11 +404,60 @@ def _matrix_to_midi_des_batch(gen1_output, gen2_output, adj_size, instrument, st
         done = np.flatnonzero(save)
         if len(done):
             last = int(done[-1])
-            tr = words[4 * b:].reshape(b, ops.DES_MIDI_TRACK_CAP, 4)[last, :track_len[last]]
-            sim_log_to_midi.write_midi(tr, midi_path or "adj_sim_outputs/midi/generation.mid")
+            sim_log_to_midi.write_midi(tracks[last, :track_len[last]], midi_path or "adj_sim_outputs/midi/generation.mid")
     if return_tensor:
         return planes, failed
     return [r for r in planes.double().cpu().numpy()], failed
+
+
+@dataclass
+class MidiBatch:
+    """What ``matrix_to_midis`` returns: ``rolls`` (B,2,128,end-start) fp32 on the device (zero for a failed sample);
+    ``tracks``: per sample the (len, 4) int32 track (kind, a, b, time) or None; ``ok`` (B,) bool; ``reasons``: None for
+    an ok sample, else the simulator's stop reason or the ``ops.DES_MIDI_ERRORS`` text; ``paths``: the files written
+    (``generate_midis``; None where nothing was written)."""
+    rolls: torch.Tensor
+    tracks: list
+    ok: np.ndarray
+    reasons: list
+    paths: list = None
+
+
+def matrix_to_midis(gen1_output, gen2_output, adj_size, instrument, start, end, *, simulate="des_batch", midi_paths=None,
+                    max_events=200000):
+    """``matrix_to_midi(..., generate=True)`` for a batch that keeps EVERY sample's track instead of the last one's
+    (upstream overwrites one generation.mid per sample, MMGAN_MIDI_DES/sim_log_to_midi.py): the same prologue, the same
+    simulations and the same ``des_log_to_roll`` launch as the built-in back ends "des" / "des_batch", hence the same
+    rolls under the same ``np.random.seed``, with one read-back.  instrument: None, one program for all samples, or a
+    list of B (None or a program).  midi_paths: B paths (file i is ``write_midi(tracks[i], midi_paths[i])`` for every
+    ok sample) or None to write nothing.  A failed simulation or a per-sample MIDI error marks that sample failed --
+    zero roll, no track, no file, its reason in ``reasons`` -- and nothing is raised for it.  -> MidiBatch."""
+    from . import sim_log_to_midi, simulation_v3
+    start, end = int(start), int(end)
+    if simulate not in ("des", "des_batch"):
+        raise ops.GdmError(f"matrix_to_midis: unknown back end {simulate!r} (the built-in ones are \"des\" and "
+                           "\"des_batch\")")
+    b = gen1_output.shape[0]
+    if midi_paths is not None and len(midi_paths) != b:
+        raise ops.GdmError(f"matrix_to_midis: {len(midi_paths)} midi_paths for {b} samples")
+    if simulate == "des_batch":
+        planes, status, track_len, good, _save, stop, track = _des_batch_run(gen1_output, gen2_output, adj_size,
+                                                                             instrument, start, end, True, max_events)
+        tracks = [track[i, :track_len[i]].copy() for i in range(b)]
+        reasons = [None if good[i] else simulation_v3.STOP_REASONS[int(stop[i])] for i in range(b)]
+    else:
+        planes, tracks, status, reasons = _des_run(gen1_output, gen2_output, adj_size, instrument, start, end, True,
+                                                   max_events, raise_for_status=False)[:4]
+    ok = np.array([reasons[i] is None for i in range(b)])
+    for i in np.flatnonzero(np.asarray(status) >> 8):
+        ok[i], reasons[i] = False, ops.DES_MIDI_ERRORS[int(status[i]) >> 8]
+    if not ok.all():
+        planes[torch.from_numpy(~ok).to(planes.device)] = 0.0
+    tracks = [tr if ok[i] else None for i, tr in enumerate(tracks)]
+    res = MidiBatch(planes, tracks, ok, reasons)
+    if midi_paths is not None:
+        res.paths = [sim_log_to_midi.write_midi(tracks[i], str(midi_paths[i])) if ok[i] else None for i in range(b)]
+    return res
 
 
 def _batch_to_mel(pro, max_events):

@@ -9,6 +9,8 @@
     MultiModalGAN(z_dim=100, hidden_dim=64, adj_size=(28, 28), roll_size=(2,128,50), input_dim=50, output_dim=16,
                   instrument=None, start=30, end=80, device='cpu')                             :163-206
     TestMultiModalGAN.test_training_loop(batch_size=16) / training_loop(...)                   :208-350
+    MultiModalGAN.sample(n) / .generate_midis(n)             (this build: the batched form of generate_midi, :199-206)
+    python -m ... --generate N --checkpoint FILE.pth --beats-from FILE.mid                      N files from a checkpoint
     training_loop(..., midi_dir=DIR | pickle_file=FILE) / python -m ... --midi-dir DIR         :229-230 on real data
 
 Module trees and state_dict keys equal the reference's (``gen.{i}.0`` = Linear, ``gen.{i}.1`` = BatchNorm1d,
@@ -67,6 +69,34 @@ def _run_gen_stack(module, x):
     return Fn.MlpBnSigmoidFn.apply(x, *flat, tuple(buffers), module.training, _dtype_of(module))
 
 
+def _eval_layers(module):
+    return [(blk[0].weight.detach(), blk[0].bias.detach(), blk[1].weight.detach(), blk[1].bias.detach(),
+             blk[1].running_mean, blk[1].running_var) for blk in module.gen]
+
+
+def _eval_geometry(module):
+    """(K1, H1, H2, H3, N4) if the one-launch eval kernel takes this generator, else None."""
+    from . import ops
+    if len(module.gen) != 4 or len({blk[1].eps for blk in module.gen}) != 1:
+        return None
+    dims = (module.gen[0][0].in_features, *[blk[0].out_features for blk in module.gen])
+    return dims if ops.mmgan_gen_eval_supported(*dims) else None
+
+
+def _eval_pack(module):
+    """The generator's weight pack for ops.mmgan_gen_eval, rebuilt when a parameter or a running statistic changed
+    (keyed on their data_ptr and _version, as model 1's _eval_cache).  The pack is a copy: it aliases no parameter."""
+    from . import ops
+    layers = _eval_layers(module)
+    ver = tuple(v for la in layers for t in la for v in (t.data_ptr(), t._version))
+    hit = module._eval_cache.get("pack")
+    if hit is not None and hit[0] == ver and hit[1].device == layers[0][0].device:
+        return hit[1], hit[2]
+    pack, dims = ops.mmgan_gen_eval_pack(layers, eps=module.gen[0][1].eps)
+    module._eval_cache["pack"] = (ver, pack, dims)
+    return pack, dims
+
+
 class Generator(nn.Module):
     """cat(noise, input_tensor) -> 4 x [Linear, BatchNorm1d, Sigmoid] -> (B, im_chan, adj0, adj1) DES matrix."""
 
@@ -82,6 +112,7 @@ class Generator(nn.Module):
                                im_chan * adj_size[0] * adj_size[1]])
         self.gen.apply(weights_init)
         self.compute_dtype = None
+        self._eval_cache = {}      # the one-launch eval kernel's weight pack (MultiModalGAN.sample), not module state
 
     def make_gen_block(self, input_dim, output_dim):
         return nn.Sequential(nn.Linear(input_dim, output_dim), nn.BatchNorm1d(output_dim), nn.Sigmoid())
@@ -108,6 +139,7 @@ class BeatGenerator(nn.Module):
         self.gen = _gen_stack([z_dim + input_dim, hidden_dim * 4, hidden_dim * 2, hidden_dim, output_dim])
         self.gen.apply(weights_init)
         self.compute_dtype = None
+        self._eval_cache = {}      # the one-launch eval kernel's weight pack (MultiModalGAN.sample), not module state
 
     def make_gen_block(self, input_dim, output_dim):
         return nn.Sequential(nn.Linear(input_dim, output_dim), nn.BatchNorm1d(output_dim), nn.Sigmoid())
@@ -224,6 +256,72 @@ class MultiModalGAN(nn.Module):
         provider = self.generate_provider if self.generate_provider is not None else self.fake_provider
         sim_output, _failed = provider(gen_output1.detach(), gen_output2.detach(), None)
         return sim_output
+
+
+    def sample(self, n_samples=None, *, noise1=None, noise2=None, input_tensor=None, gen1_input=None,
+               compute_dtype="bf16"):
+        """Draw n generator outputs in eval arithmetic: (gen_output1 (n,1,adj0,adj1), gen_output2 (n,output_dim)), fp32
+        and contiguous on the module's device -- what ``matrix_to_midi`` / ``matrix_to_midis`` read in place.
+
+        Noise that is not given is drawn with ``get_noise`` on the device (noise1, then noise2); generator 1's second
+        input half (``gen1_input``) and a missing ``input_tensor`` are then drawn as the generators' ``forward`` draws
+        them: ``torch.randn`` on the CPU, then moved.  input_tensor (the beats) is (n, input_dim) or (1, input_dim):
+        one vector for every sample, broadcast inside the kernel.  BatchNorm runs on its running statistics whatever
+        ``.training`` says and no state of the module changes: parameters, running statistics,
+        ``num_batches_tracked``, ``training`` and ``compute_dtype`` are as before.
+        compute_dtype "bf16" (default): both generators in ONE launch for any n (ops.mmgan_gen_eval); "fp32", or a
+        geometry the kernel does not take, walks the module forwards in eval mode (and restores ``training``)."""
+        from . import ops
+        g1, g2 = self.generator1, self.generator2
+        dev = g1.gen[0][0].weight.device
+        given = [t.shape[0] for t in (noise1, noise2, gen1_input) if t is not None]
+        if input_tensor is not None and input_tensor.shape[0] != 1:
+            given.append(input_tensor.shape[0])
+        n = int(n_samples) if n_samples is not None else (max(given) if given else None)
+        if n is None:
+            raise ValueError("sample needs n_samples or a noise tensor")
+        if n < 1 or any(k != n for k in given):
+            raise ValueError(f"sample: n_samples = {n} but the given tensors hold {given} rows")
+        noise1 = get_noise(n, g1.z_dim, device=dev) if noise1 is None else noise1.to(dev)
+        noise2 = get_noise(n, g2.z_dim, device=dev) if noise2 is None else noise2.to(dev)
+        gen1_input = (torch.randn(n, g1.input_tensor_dim) if gen1_input is None else gen1_input).to(dev)
+        input_tensor = (torch.randn(n, g2.input_tensor_dim) if input_tensor is None else input_tensor).to(dev)
+        geo = (_eval_geometry(g1), _eval_geometry(g2))
+        if Fn._NAMES[compute_dtype] == Fn.BF16 and None not in geo and geo[0][1:4] == geo[1][1:4]:
+            jobs = []
+            for g, noise, inp in ((g1, noise1, gen1_input), (g2, noise2, input_tensor)):
+                pack, dims = _eval_pack(g)
+                jobs.append(dict(noise=noise.float().contiguous(), input=inp.float().contiguous(), pack=pack, dims=dims))
+            out1, out2 = ops.mmgan_gen_eval(jobs)
+            return out1.view(n, -1, self.adj_size[0], self.adj_size[1]), out2
+        was = [(g.training, g.compute_dtype) for g in (g1, g2)]
+        try:
+            for g in (g1, g2):
+                g.eval()
+                g.compute_dtype = compute_dtype
+            with torch.no_grad():
+                out1 = g1(noise1, gen1_input)
+                out2 = g2(noise2, input_tensor.expand(n, -1))
+        finally:
+            for g, (training, cd) in zip((g1, g2), was):
+                g.train(training)
+                g.compute_dtype = cd
+        return out1.detach().contiguous(), out2.detach().contiguous()
+
+    def generate_midis(self, n_samples=None, *, noise1=None, noise2=None, input_tensor=None,
+                       out_dir="adj_sim_outputs/midi", name="generation_{:04d}.mid", bridge="des_batch",
+                       compute_dtype="bf16"):
+        """``generate_midi`` for a batch that keeps every sample: ``sample`` (one launch), then
+        ``matrix_sim_process.matrix_to_midis`` with the module's adj_size, instrument, start and end, which writes
+        ``out_dir/name.format(i)`` for every sample whose simulation and MIDI conversion succeeded.  Works whatever
+        ``fake_provider`` the module was built with: bridge names the built-in one, "des" or "des_batch".
+        Returns the MidiBatch (rolls, tracks, ok, reasons) with ``paths``: None where ``ok`` is false."""
+        from .matrix_sim_process import matrix_to_midis
+        out1, out2 = self.sample(n_samples, noise1=noise1, noise2=noise2, input_tensor=input_tensor,
+                                 compute_dtype=compute_dtype)
+        paths = [os.path.join(out_dir, name.format(i)) for i in range(out1.shape[0])]
+        return matrix_to_midis(out1, out2, self.adj_size, self.instrument, self.start, self.end, simulate=bridge,
+                               midi_paths=paths)
 
 
 def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per_epoch=None, fake_provider=None,
@@ -364,12 +462,49 @@ _CLI_OPTIONS = ("--midi-dir", "--pickle", "--epochs", "--batch-size", "--sequenc
                 "--fake-provider", "--save-dir", "--max-steps")
 
 
+def generate_main(argv):
+    """``--generate N --checkpoint FILE.pth --beats-from FILE.mid``: N MIDI files from a trained model 2, as the
+    reference's demo notebook makes one (mmgan.generate_midi(noise, noise, get_beats()[:50])): the checkpoint is loaded
+    ``strict=True`` into the 64x64 geometry of the committed mmgan_64_64_epoch_*.pth files, the beats are the first 50
+    of the file's beat grid (zero-padded), one line is printed per written file."""
+    import argparse
+    import numpy as np
+    from . import datasets
+    ap = argparse.ArgumentParser(prog="gan_des_midi_music_gen_amd.network_tests --generate", description=generate_main.__doc__)
+    ap.add_argument("--generate", type=int, required=True, metavar="N")
+    ap.add_argument("--checkpoint", required=True)
+    ap.add_argument("--beats-from", required=True, metavar="FILE.mid")
+    ap.add_argument("--out-dir", default="adj_sim_outputs/midi")
+    ap.add_argument("--instrument", type=int, default=0)
+    ap.add_argument("--start", type=int, default=100)
+    ap.add_argument("--end", type=int, default=150)
+    ap.add_argument("--seed", type=int, default=None)
+    a = ap.parse_args(argv)
+    if a.generate < 1:
+        ap.error("--generate needs N >= 1")
+    device = torch.device("cuda")
+    if a.seed is not None:
+        torch.manual_seed(a.seed)
+        np.random.seed(a.seed)
+    mmgan = MultiModalGAN(z_dim=50, adj_size=(64, 64), roll_size=(2, 128, 50), input_dim=50, output_dim=20,
+                          instrument=a.instrument, start=a.start, end=a.end, device=device)
+    mmgan.load_state_dict(torch.load(a.checkpoint, map_location=device, weights_only=True), strict=True)
+    beats = datasets._fit_beats(datasets.get_beats(datasets.read_midi(a.beats_from)), 50)
+    res = mmgan.generate_midis(a.generate, input_tensor=torch.as_tensor(np.asarray(beats), dtype=torch.float32)[None],
+                               out_dir=a.out_dir)
+    for i, path in enumerate(res.paths):
+        print(path if path is not None else f"sample {i}: no file ({res.reasons[i]})")
+    return 0
+
+
 def main(argv=None):
-    """``python -m gan_des_midi_music_gen_amd.network_tests``: with --midi-dir or --pickle, ``training_loop`` on that
-    data; without any of the options below, the reference's ``unittest.main()``."""
+    """``python -m gan_des_midi_music_gen_amd.network_tests``: with --generate, ``generate_main``; with --midi-dir or
+    --pickle, ``training_loop`` on that data; without any of the options below, the reference's ``unittest.main()``."""
     import argparse
     import sys
     argv = sys.argv[1:] if argv is None else list(argv)
+    if any(a.split("=")[0] == "--generate" for a in argv):
+        return generate_main(argv)
     if not any(a.split("=")[0] in _CLI_OPTIONS for a in argv):
         return unittest.main(argv=[sys.argv[0]] + argv)
     ap = argparse.ArgumentParser(prog="gan_des_midi_music_gen_amd.network_tests", description=main.__doc__)

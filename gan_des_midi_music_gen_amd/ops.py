@@ -751,6 +751,72 @@ def concat_cols_multi(pairs, outs=None):
     return res
 
 
+def mmgan_gen_eval_supported(k1, h1, h2, h3, n4):
+    return bool(_lib.load().gdm_mmgan_gen_eval_supported(int(k1), int(h1), int(h2), int(h3), int(n4)))
+
+
+def _ptr_array(ts):
+    return ctypes.cast((ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts]), ctypes.c_void_p)
+
+
+def mmgan_gen_eval_pack(layers, *, eps=1e-5, out=None):
+    """The weight pack of mmgan_gen_eval for one generator.  layers: 4 x (weight (N, K), bias, gamma, beta, running_mean,
+    running_var), fp32 contiguous.  Returns (pack, dims) with dims = (K1, H1, H2, H3, N4); the pack is a copy (hi/lo bf16
+    fragment images + per-column vectors), so rebuild it when a parameter or a running statistic changes."""
+    assert len(layers) == 4 and all(len(la) == 6 for la in layers)
+    flat = [t for la in layers for t in la]
+    _need_gpu(*flat, out)
+    for w, *vecs in layers:
+        assert w.dim() == 2 and all(v.shape == (w.shape[0],) for v in vecs)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in flat)
+    assert all(layers[i + 1][0].shape[1] == layers[i][0].shape[0] for i in range(3))
+    dims = (int(layers[0][0].shape[1]), *[int(la[0].shape[0]) for la in layers])
+    nbytes = _lib.load().gdm_mmgan_gen_eval_pack_bytes(*dims)
+    pack = out if out is not None else torch.empty(max(nbytes, 16), dtype=torch.uint8, device=flat[0].device)
+    cols = [_ptr_array([la[i] for la in layers]) for i in range(6)]
+    _call("gdm_mmgan_gen_eval_pack", *cols, *dims, float(eps), _p(pack), pack.numel(), _stream())
+    return pack, dims
+
+
+def mmgan_gen_eval(jobs, *, taps=False):
+    """Model 2's generators in eval mode, 1 or 2 of them in ONE launch for any batch size.  jobs: dicts with noise
+    (B, z), input ((B, in) or (1, in): broadcast), pack and dims from mmgan_gen_eval_pack, optional out (B, N4).
+    Returns one (B, N4) fp32 tensor per job, or with taps=True (out, [y1, y2, y3, y4], [a1, a2, a3]) per job: the fp32
+    pre-BatchNorm values and the hidden activations."""
+    assert 1 <= len(jobs) <= 2
+    arr = (_lib.MmganGenEvalJob * len(jobs))()
+    res = []
+    hidden = tuple(jobs[0]["dims"][1:4])
+    for a, j in zip(arr, jobs):
+        noise, inp, pack, dims = j["noise"], j["input"], j["pack"], tuple(j["dims"])
+        _need_gpu(noise, inp, pack, j.get("out"))
+        assert noise.dim() == 2 and inp.dim() == 2 and noise.dtype == torch.float32 and inp.dtype == torch.float32
+        assert noise.is_contiguous() and inp.is_contiguous() and pack.dtype == torch.uint8 and pack.is_contiguous()
+        b, z = noise.shape
+        assert inp.shape[0] in (1, b) and z + inp.shape[1] == dims[0] and dims[1:4] == hidden
+        n4 = dims[4]
+        widths = (*hidden, n4)
+        dev = noise.device
+        out = j.get("out")
+        if out is None:
+            out = torch.empty((b, n4), dtype=torch.float32, device=dev)
+        assert out.shape == (b, n4) and out.dtype == torch.float32 and out.is_contiguous()
+        ys = [torch.empty((b, n), dtype=torch.float32, device=dev) for n in widths] if taps else [None] * 4
+        acts = [torch.empty((b, n), dtype=torch.float32, device=dev) for n in hidden] if taps else [None] * 3
+        if "tap_buffers" in j:           # tests: caller-owned (sentinel-guarded) views for the taps
+            ys, acts = j["tap_buffers"]
+        a.noise, a.input, a.pack, a.pack_bytes, a.out = _p(noise), _p(inp), _p(pack), pack.numel(), _p(out)
+        for q in range(4):
+            a.tap_y[q] = ys[q].data_ptr() if ys[q] is not None else None
+        for q in range(3):
+            a.tap_a[q] = acts[q].data_ptr() if acts[q] is not None else None
+        a.B, a.z, a.in_, a.n4 = b, z, int(inp.shape[1]), n4
+        a.input_stride = 0 if (inp.shape[0] == 1 and b > 1) else int(inp.shape[1])
+        res.append((out, ys, acts) if taps else out)
+    _call("gdm_mmgan_gen_eval", ctypes.cast(arr, ctypes.c_void_p), len(jobs), *[int(h) for h in hidden], _stream())
+    return res
+
+
 def dcnn_fused_supported(t):
     return bool(_lib.load().gdm_dcnn_fused_supported(int(t)))
 

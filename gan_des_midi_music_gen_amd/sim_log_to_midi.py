@@ -166,14 +166,15 @@ def _upload_logs(logs, device, who):
 
 
 def log_to_rolls(logs, gen2_tails, instruments, note_levels, *, start=0, end=30, generate=False, save=None,
-                 sequence_length=100, device="cuda", return_saved=False):
+                 sequence_length=100, device="cuda", return_saved=False, return_status=False, raise_for_status=True):
     """B event logs -> (rolls (B, 2, 128, W) fp32 DEVICE tensor, tracks): one ``des_log_to_roll`` launch.
 
     logs: B ``EVENT_DTYPE`` arrays (``Sim.music_log``); gen2_tails: (B, >= 6) ``gen2_output[:, 10:]``; instruments,
     note_levels: B lists of ``dim`` numbers (``int()`` is applied, as upstream).  save: per-sample override of the
     reference's decision ``generate or line count % 100 == 0``.  tracks[i]: (n, 4) int32 (kind, a, b, time) -- the saved
     track, or the track as process_line left it when sample i is not saved (its planes are zero then).
-    A sample the reference would raise for raises ValueError here."""
+    A sample the reference would raise for raises ValueError here -- unless raise_for_status is False; return_status
+    adds the (B,) status words (error code in bits 8 and up, ``ops.DES_MIDI_ERRORS``) to the result."""
     logs, dev, up, records = _upload_logs(logs, device, "log_to_rolls")
     b = len(logs)
     tails = np.ascontiguousarray(gen2_tails.detach().float().cpu().numpy() if torch.is_tensor(gen2_tails)
@@ -192,9 +193,11 @@ def log_to_rolls(logs, gen2_tails, instruments, note_levels, *, start=0, end=30,
                                                            end, sequence_length)
     status, track_len, track = status.cpu().numpy(), track_len.cpu().numpy(), track.cpu().numpy()
     for i in range(b):
-        if status[i] >> 8:
+        if status[i] >> 8 and raise_for_status:
             raise ValueError(f"Error in processing log file (sample {i}: {ops.DES_MIDI_ERRORS[int(status[i]) >> 8]})")
     tracks = [track[i, :track_len[i]].copy() for i in range(b)]
+    if return_status:
+        return planes, tracks, status
     if return_saved:
         return planes, tracks, [bool(s & 1) for s in status]
     return planes, tracks

@@ -354,6 +354,40 @@ int gdm_dcnn_fused_adam_crit(const float* xa, int bsplit, const float* p0, const
                              float yb, void* pack, float* logits, float* loss, int accumulate_loss, float* dw1,
                              float* db1, float* dw2, float* db2, float* dwfc, float* dbfc, const gdm_dcnn_adam* opt,
                              int criterion, void* workspace, size_t workspace_bytes, void* stream);
+/* Both generators in eval mode, one launch for any batch (network_tests.py:58-123: Generator and BeatGenerator, four
+ * blocks Linear -> BatchNorm1d -> Sigmoid each; generate_midi, :199-206, calls them after .eval()).  BatchNorm on the
+ * running statistics is a per-column affine map, so rows are independent: a workgroup carries 16 rows through layers
+ * 1-3 in LDS and computes one slab of layer 4's columns.  A job is one generator; with two jobs the second one's
+ * workgroups ride in the same grid.  x = cat(noise (B, z), input (B, in)) is read from the two pointers (:87, :119);
+ * input_stride is the second one's row stride in floats, 0 = one vector for every row.  K1 = z + in.
+ * Arithmetic per layer as gdm_linear_bn_act_fwd in eval mode: split operands x = xh + xl, W = wh + wl in bf16, three
+ * MFMA products, fp32 accumulation and bias, (y - running_mean) * (invstd * gamma) + beta with invstd =
+ * 1 / sqrtf(running_var + eps), sigmoid; activations stay fp32 between layers.  A row's bits depend on neither B nor
+ * the row's position.  Only `out` (B, N4) and the taps are written: the running statistics and num_batches_tracked
+ * are not even passed.
+ * gdm_mmgan_gen_eval_supported: 1 <= K1 <= 512, hidden widths (256, 128, 64), 1 <= N4 <= 2^20.
+ * gdm_mmgan_gen_eval_pack: w, bias, gamma, beta, running_mean, running_var are HOST arrays of the four layers' device
+ * pointers (w[l] (N_l, K_l) fp32 row-major); the pack (16-byte aligned, gdm_mmgan_gen_eval_pack_bytes bytes, 0 for an
+ * unsupported geometry) receives hi/lo bf16 weight images in MFMA fragment order, zero-padded, and per column bias,
+ * invstd, gamma, beta, running_mean.  It is a copy: rebuild it when a parameter or a buffer changes.
+ * Taps (NULL = off; a kernel instance without them is launched when all are NULL): tap_y[l] the fp32 pre-BatchNorm
+ * values y_{l+1} (B, N_l) of the four layers, tap_a[l] the activations a_{l+1} of the three hidden ones.            */
+typedef struct gdm_mmgan_gen_eval_job {
+  const float *noise, *input;
+  const void* pack;
+  size_t pack_bytes;
+  float* out;
+  float* tap_y[4];
+  float* tap_a[3];
+  int B, z, in, input_stride, n4;
+} gdm_mmgan_gen_eval_job;
+int gdm_mmgan_gen_eval_supported(int k1, int h1, int h2, int h3, int n4);
+size_t gdm_mmgan_gen_eval_pack_bytes(int k1, int h1, int h2, int h3, int n4);
+int gdm_mmgan_gen_eval_pack(const float* const* w, const float* const* bias, const float* const* gamma,
+                            const float* const* beta, const float* const* running_mean, const float* const* running_var,
+                            int k1, int h1, int h2, int h3, int n4, float eps, void* pack, size_t pack_bytes,
+                            void* stream);
+int gdm_mmgan_gen_eval(const gdm_mmgan_gen_eval_job* jobs, int n_jobs, int h1, int h2, int h3, void* stream);
 
 /* ---- deterministic discrete-event simulator core (host code; SIMULATOR/simulation_v3.py:25-74, 426-743) -------------
  * One run of Sim(adj, distributions, queue_list, seeds=[seed], logging_mode='Music').run(number_of_customers) for 'normal'
