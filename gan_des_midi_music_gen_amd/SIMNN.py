@@ -175,9 +175,10 @@ def generate_song(model_folder, device=None, bridge=None, compute_dtype=None, *,
     with torch.no_grad():
         generated = gen(get_noise(1, 100, device=device)).detach()
     if isinstance(bridge, str):
-        if bridge not in ("des", "des_batch"):
-            raise ValueError(f"unknown bridge {bridge!r} (the built-in ones are \"des\" and \"des_batch\")")
-        return _des_song(generated.reshape(1, 20, 20), midi_path, wav_path, max_seconds, batched=bridge == "des_batch")
+        if bridge not in ("des", "des_batch", "des_device"):
+            raise ValueError(f"unknown bridge {bridge!r} (the built-in ones are \"des\", \"des_batch\" and "
+                             "\"des_device\")")
+        return _des_song(generated.reshape(1, 20, 20), midi_path, wav_path, max_seconds, batched=bridge)
     adj = generated.squeeze().cpu().numpy()
     return bridge(adj) if bridge is not None else adj
 
@@ -212,10 +213,13 @@ def _write_clip(notes, n_notes, i, count, total, midi_path, wav_path, max_second
 
 
 def _des_mel(matrices, batched):
-    """matrix_to_wav(simulate="des" / "des_batch") on (B, 20, 20) matrices, keeping the note lists:
+    """matrix_to_wav(simulate="des" / "des_batch" / "des_device") on (B, 20, 20) matrices (batched: True for
+    "des_batch", or a back end's name), keeping the note lists:
     -> (mel (B, 128, 216), (notes, n_notes, clip_len))."""
     from . import matrix_sim_process as msp
-    if batched:
+    if batched == "des_device":
+        return msp._batch_to_mel(msp.device_prologue_wav(matrices, 20, None), 200000)
+    if batched and batched != "des":
         return msp._batch_to_mel(msp.batched_prologue_wav(matrices, 20, None), 200000)
     h = msp._wav_scan(matrices, 20)
     specs = msp._interleaved_specs(h, msp._wav_draws, lambda h_, i, r, src, sd: msp._wav_spec(h_, i, r, src, sd, None))
@@ -246,14 +250,16 @@ def generate_songs(model, n_samples=None, *, noise=None, bridge="des_batch", out
     model: a ``Generator`` or the path of a ``gen_*.pt`` checkpoint.  ``sample_matrices`` draws the n matrices (one
     launch), then bridge "des_batch" simulates all of them in one device launch
     (matrix_sim_process._batch_to_mel(batched_prologue_wav(...))) and "des" keeps the reference's interleaved order
-    (see matrix_sim_process for what differs).  With ``out_dir`` clip i is written to ``out_dir/song_{i:04d}.mid`` (midi)
+    (see matrix_sim_process for what differs); "des_device" also makes the draws on the device, one stream per clip.
+    With ``out_dir`` clip i is written to ``out_dir/song_{i:04d}.mid`` (midi)
     and ``.wav`` (wav) exactly as ``generate_song`` writes its one clip; with out_dir=None nothing is written and the
     path lists hold None.  -> SongBatch."""
-    if bridge not in ("des", "des_batch"):
-        raise ValueError(f"unknown bridge {bridge!r} (the built-in ones are \"des\" and \"des_batch\")")
+    if bridge not in ("des", "des_batch", "des_device"):
+        raise ValueError(f"unknown bridge {bridge!r} (the built-in ones are \"des\", \"des_batch\" and "
+                         "\"des_device\")")
     matrices = sample_matrices(model, n_samples, noise=noise, compute_dtype=compute_dtype, device=device)
     n = matrices.shape[0]
-    mel, (notes, n_notes, clip_len) = _des_mel(matrices.reshape(n, 20, 20), bridge == "des_batch")
+    mel, (notes, n_notes, clip_len) = _des_mel(matrices.reshape(n, 20, 20), bridge)
     midi_paths, wav_paths = [None] * n, [None] * n
     if out_dir is not None:
         counts, lengths = n_notes.cpu(), clip_len.cpu()                  # one read-back for all clips
@@ -268,9 +274,10 @@ def generate_songs(model, n_samples=None, *, noise=None, bridge="des_batch", out
 def des_fake_provider(start=0, end=216, max_events=200000, batched=False):
     """The built-in DES bridge as the ``fake`` callable of ``SimnnTrainer.step`` / ``train(fake_provider=...)``:
     generated (B,1,20,20) device tensor -> (B,128,end-start) dB tensor on the same device (SIMNN.py:301).
-    batched: simulate on the device (matrix_to_wav(simulate="des_batch"))."""
+    batched: simulate on the device (matrix_to_wav(simulate="des_batch")); a back end's name ("des_batch",
+    "des_device") selects that one."""
     from . import matrix_sim_process as msp
-    simulate = "des_batch" if batched else "des"
+    simulate = batched if isinstance(batched, str) else ("des_batch" if batched else "des")
 
     def provider(generated):
         return msp.matrix_to_wav(generated, start=start, end=end, device=generated.device, simulate=simulate,
@@ -341,7 +348,8 @@ def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5,
         ``matrix_to_wav`` (SIMNN.py:301); "des": the built-in bridge (``des_fake_provider(0, input_hw[1])``; it needs
         ``input_hw[1] <= 216`` frames, the reference's ``start=0, end=216`` by default); if None, seeded synthetic
         windows are used.  "des_batch": the same bridge with the simulation on the device, one launch per batch
-        (``des_fake_provider(0, input_hw[1], batched=True)``; matrix_sim_process lists what differs from "des").
+        (``des_fake_provider(0, input_hw[1], batched=True)``; matrix_sim_process lists what differs from "des").  "des_device": the draws on the
+        device too, one stream per sample (``batched="des_device"``).
     Returns (gen, disc, gen_losses, disc_losses).
     """
     from .train import SimnnTrainer
@@ -365,13 +373,13 @@ def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5,
     elif input_hw is None:
         input_hw = (128, 216)
     if isinstance(fake_provider, str):
-        if fake_provider not in ("des", "des_batch"):
-            raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in ones are \"des\" and "
-                             "\"des_batch\")")
+        if fake_provider not in ("des", "des_batch", "des_device"):
+            raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in ones are \"des\", "
+                             "\"des_batch\" and \"des_device\")")
         if input_hw[0] != 128 or not 0 < input_hw[1] <= 216:
             raise ValueError(f"fake_provider=\"{fake_provider}\" makes (128, end - start <= 216) windows, input_hw is "
                              f"{tuple(input_hw)}")
-        fake_provider = des_fake_provider(0, input_hw[1], batched=fake_provider == "des_batch")
+        fake_provider = des_fake_provider(0, input_hw[1], batched=fake_provider)
     if seed is not None:
         torch.manual_seed(seed)
     gen = Generator().to(device)
@@ -429,15 +437,17 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=30)
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--no-save", action="store_true", help="write no generator checkpoints")
-    ap.add_argument("--fake-provider", choices=["des", "des_batch"], default=None,
+    ap.add_argument("--fake-provider", choices=["des", "des_batch", "des_device"], default=None,
                     help="des: fakes from the built-in DES bridge; des_batch: the same with the simulation batched on "
-                         "the device (default: seeded synthetic windows)")
+                         "the device; des_device: the draws on the device too (default: seeded synthetic windows)")
     ap.add_argument("--generate", type=int, default=None, metavar="N",
                     help="do not train: write N clips (MIDI + WAV) from --checkpoint into --out-dir (generate_songs)")
     ap.add_argument("--checkpoint", default=None, help="gen_*.pt generator checkpoint for --generate")
     ap.add_argument("--out-dir", default="adj_sim_outputs/songs", help="where --generate writes song_NNNN.mid / .wav")
     ap.add_argument("--max-seconds", type=float, default=None, help="cut the clips of --generate")
     ap.add_argument("--seed", type=int, default=None, help="seed of --generate (torch and numpy)")
+    ap.add_argument("--bridge", choices=["des", "des_batch", "des_device"], default="des_batch",
+                    help="DES bridge of --generate")
     a = ap.parse_args(argv)
     if a.generate is not None:
         if a.checkpoint is None or a.generate < 1:
@@ -446,7 +456,7 @@ def main(argv=None):
             import numpy as np
             torch.manual_seed(a.seed)
             np.random.seed(a.seed)
-        songs = generate_songs(a.checkpoint, a.generate, out_dir=a.out_dir, max_seconds=a.max_seconds)
+        songs = generate_songs(a.checkpoint, a.generate, out_dir=a.out_dir, max_seconds=a.max_seconds, bridge=a.bridge)
         for path in (p for pair in zip(songs.midi_paths, songs.wav_paths) for p in pair):
             print(path)
         return

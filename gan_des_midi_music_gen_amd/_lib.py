@@ -122,7 +122,9 @@ SIGNATURES = {
     "gdm_permute_pc": (_I, [_P, _I, _I, _I, _I, _P, _I, _P]),
     "gdm_des_scan": (_I, [_P, _L, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "gdm_des_routing": (_I, [_P, _L, _I, _I, _I, _P, _P, _P, _P]),
-    "gdm_des_run": (_I, [_P, _I, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _P, _L, _P, _P]),
+    "gdm_des_draws": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I] + [_P] * 16),
+    "gdm_des_draws_host": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I] + [_P] * 15),
+    "gdm_des_run": (_I,[_P, _I, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _P, _L, _P, _P]),
     "gdm_des_run_batch_host": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P,
                                     _P, _P]),
     "gdm_des_batch_workspace_bytes": (_L, [_I, _I, _I]),

@@ -52,6 +52,32 @@ because the launch costs 8-10 ms however small the batch is.  Four differences f
      to 5001 lines), so ``max_events`` is rarely reached;
   4. final stream position: after the call numpy's global stream is where the batched prologue left it (where
      ``midi_prologue`` / ``wav_prologue`` leave it), not where the last simulation would have.
+
+simulate="des_device" (opt-in; "des" and "des_batch" keep their behaviour and their bits) moves the last host stage of
+"des_batch" -- the draws and the float32 parameter arithmetic of ``_midi_spec`` / ``_wav_spec`` -- onto the device
+(``device_prologue_midi`` / ``device_prologue_wav``: scan, ``ops.des_draws`` (csrc/des_draws.hip, one wave per sample),
+routing), always simulates with the kernel and enqueues scan, draws, routing, simulator and log consumers without a
+host synchronisation; ONE read-back at the end carries the draw status words, the scan's finite flags, the stop
+reasons and the tracks.  The draws of "des_batch" cannot be reproduced bit for bit in parallel -- they run through ONE
+global stream, sample i+1 continuing from sample i's reseed -- so this is a back end of its own.  Differences from
+"des_batch":
+  1. per-sample streams: sample i draws from ``RandomState(int(base[i]))`` with the same calls in the same order as
+     ``_midi_draws`` / ``_wav_draws`` (numpy itself is the oracle: tests/test_des_draws.py), and its simulation starts
+     from where those draws leave that stream.  The samples are independent: permuting the batch (and ``base``)
+     permutes the results;
+  2. one host draw: ``base = np.random.randint(0, 2**32, size=B, dtype=np.uint32)`` (``draw_base_seeds``) is the only
+     call on numpy's global stream per bridge call, so ``np.random.seed`` stays the reproducibility handle;
+  3. status codes instead of mid-loop exceptions: what raises inside the reference's draws (an empty candidate list,
+     more than one thresholded source, a thresholded column >= dim; ``ops.DES_DRAWS_ERRORS``) marks the sample, the
+     simulator skips it (DES_STOP_ERROR, no records), and after the read-back ``matrix_to_midi`` / ``matrix_to_wav``
+     raise the reference's exception type for the first such sample while ``matrix_to_midis`` marks it failed with
+     the text in ``reasons``.  A non-finite generated matrix raises ValueError after the read-back as well;
+  4. final stream position: numpy's global stream ends exactly one ``randint`` call after where it started;
+  5. no host-mirror switch: the kernel simulates whatever B is.  The launch costs 8-10 ms and is the bridge's floor:
+     measured at B = 30 the bridge takes 11.4 ms against 21.8 ms (model 2) and 9.7 against 11.3 ms (model 1), at
+     B = 256 12.0 against 122 ms and 16.8 against 49 ms -- it pays from B = 30 on; below
+     that size it was not measured, and a handful of samples is where the host mirror of "des_batch" should win.
+At most 64 nodes (a row's candidate set is one 64-bit word), which covers both models (61 and 15).
 """
 from dataclasses import dataclass, field
 
@@ -241,6 +267,142 @@ def batched_prologue_wav(matrices, size=20, use_same_instrument=None):
     return _batched_prologue(h, _wav_draws, lambda h_, i, r, src, sd: _wav_spec(h_, i, r, src, sd, use_same_instrument))
 
 
+# ---- "des_device": the draws and parameters on the device, one stream per sample --------------------------------------
+DES_DEVICE_QUEUE_CAP = 2 * 127           # queue_list = [2 * 127] * dim: sizes the simulator's workspace without a read-back
+
+
+def draw_base_seeds(b):
+    """The ONE call "des_device" makes on numpy's global stream per bridge call: sample i draws from
+    ``RandomState(int(base[i]))``."""
+    return np.random.randint(0, 2 ** 32, size=b, dtype=np.uint32)
+
+
+def _instrument_override(instrument, b):
+    """None, one program, or a list of B (None or a program) -> (B,) int32 array, or None when nothing is overridden."""
+    if instrument is None:
+        return None
+    if isinstance(instrument, (list, tuple, np.ndarray)):
+        if len(instrument) != b:
+            raise ops.GdmError(f"des_device: {len(instrument)} instruments for {b} samples")
+        return np.array([ops.DES_DRAWS_NO_INSTRUMENT if x is None else int(x) for x in instrument], dtype=np.int32)
+    return np.full(b, int(instrument), dtype=np.int32)
+
+
+def des_draws_host(route, s, dim, base, zero_mask, scan_instruments, scan_note_levels, params, thr_mask=None,
+                   instrument_override=None):
+    """``gdm_des_draws_host`` on numpy arrays: the device kernel's source compiled for the host, the same bits (see
+    ``ops.des_draws`` for the arguments and the dict that comes back; mt_key is uint32 here)."""
+    from . import _lib
+    base = np.ascontiguousarray(base, dtype=np.uint32).reshape(-1)
+    b = base.size
+    zm = np.ascontiguousarray(zero_mask).view(np.uint64).reshape(b, dim)
+    inst = np.ascontiguousarray(scan_instruments, dtype=np.int32).reshape(b, dim)
+    notes = np.ascontiguousarray(scan_note_levels, dtype=np.int32).reshape(b, dim)
+    params = np.ascontiguousarray(params, dtype=np.float32).reshape(b, -1)
+    thr = None if thr_mask is None else np.ascontiguousarray(thr_mask, dtype=np.uint8).reshape(b, s)
+    over = None if instrument_override is None else np.ascontiguousarray(instrument_override, dtype=np.int32).reshape(b)
+    shapes = {"d": (b, dim), "": (b,), "k": (b, 624)}
+    np_dt = {torch.uint8: np.uint8, torch.int32: np.int32, torch.int64: np.int64, torch.float64: np.float64}
+    out = {name: np.zeros(shapes[kind], dtype=np.uint32 if name == "mt_key" else np_dt[dt])
+           for name, dt, kind in ops._DES_DRAWS_FIELDS}
+    ptr = lambda a: None if a is None else a.ctypes.data                                         # noqa: E731
+    rc = _lib.load().gdm_des_draws_host(int(route), b, int(s), int(dim), ptr(base), ptr(zm), ptr(thr), ptr(inst),
+                                        ptr(notes), ptr(params), params.shape[1], ptr(over),
+                                        *(ptr(out[name]) for name, _dt, _k in ops._DES_DRAWS_FIELDS))
+    _lib.check(rc, "gdm_des_draws_host")
+    return out
+
+
+def draws_error(status):
+    """Status word of one sample -> the exception the reference raises for it."""
+    kind, text = ops.DES_DRAWS_ERRORS[int(status)]
+    return kind(text)
+
+
+class DevicePrologue:
+    """What the device prologue leaves -- the fields of ``BatchedPrologue``, every one a device tensor: ``routing``
+    (B,dim,dim) f64, ``loc``, ``scale`` (B,dim) f64, ``queue_cap`` (B,dim) i32, ``seed``, ``customers`` (B) i64,
+    ``instruments``, ``note_levels`` (B,dim) i32, ``states`` = (mt_key (B,624) i32, mt_pos, has_gauss (B) i32, gauss (B)
+    f64): every sample's stream after its last draw; plus ``src`` (B,dim) u8, ``cols`` (B,dim) i32, ``status`` (B) i32
+    (``ops.DES_DRAWS_ERRORS``), ``flags`` (B) i32 of the scan and ``base`` (B,) uint32 on the host.  Nothing was read
+    back: ``status`` and ``flags`` travel with the consumer's one read-back (``readback_words`` / ``raise_for``)."""
+
+    def __init__(self, h, base, draws, routing):
+        self.h, self.base, self.routing = h, base, routing
+        for name, _dt, _kind in ops._DES_DRAWS_FIELDS:
+            setattr(self, name, draws[name])
+        self.states = (draws["mt_key"], draws["mt_pos"], draws["has_gauss"], draws["gauss"])
+        self.flags = h["flags"]
+
+    def simulate_on(self, device, max_events=200000, max_records=5001):
+        """``gdm_des_run_batch`` from the device streams, whatever B is -> BatchLog of device tensors.  The kernel
+        advances ``states`` in place: simulate once per prologue."""
+        from . import simulation_v3
+        return simulation_v3.run_batch_device(self.routing, self.loc, self.scale, self.queue_cap, self.seed,
+                                              self.customers, self.states, device=device, max_events=max_events,
+                                              max_records=max_records, max_queue_cap=DES_DEVICE_QUEUE_CAP)
+
+    simulate = simulate_on
+
+    def readback_words(self):
+        """int32 device tensors to append to the consumer's read-back: draw status, scan flags."""
+        return [self.status, self.flags]
+
+    @staticmethod
+    def check_flags(flags):
+        _check_finite(np.asarray(flags))
+
+    @staticmethod
+    def raise_for(status):
+        """Raise what the reference raises for the first sample with a draw status."""
+        for i in np.flatnonzero(np.asarray(status)):
+            raise draws_error(status[i])
+
+
+def _device_prologue(route, h, scan, params, override, base):
+    b, dim, dev = h["b"], h["dim"], h["g1"].device
+    if dim > ops.DES_DRAWS_MAX_DIM:
+        raise ops.GdmError(f"des_device: at most {ops.DES_DRAWS_MAX_DIM} nodes (a row's candidates are one 64-bit word)")
+    base = draw_base_seeds(b) if base is None else np.ascontiguousarray(base, dtype=np.uint32).reshape(b)
+    base_dev = torch.from_numpy(base.view(np.int32)).to(dev)
+    over = None if override is None else torch.from_numpy(override).to(dev)
+    draws = ops.des_draws(route, h["size"], dim, base_dev, scan, params, over)
+    routing = ops.des_routing(h["g1"], h["size"], dim, draws["src"], draws["cols"])
+    h["flags"] = scan["flags"]
+    return DevicePrologue(h, base, draws, routing)
+
+
+def device_prologue_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None, *, base=None):
+    """The MIDI route's prologue entirely on the device: scan, ``ops.des_draws`` (sample i on the stream
+    ``RandomState(base[i])``; base=None: ``draw_base_seeds``, the one call on numpy's global stream), routing.  No host
+    synchronisation, nothing read back -> DevicePrologue."""
+    size = adj_size[0]
+    dim = size - 3
+    g1 = gen1_output.detach()
+    if not g1.is_cuda:
+        raise ops.GdmError("matrix_sim_process runs the prologue on a HIP device; move the generator outputs there")
+    g1 = g1.float()
+    g2 = gen2_output.detach().to(device=g1.device, dtype=torch.float32).contiguous()
+    if g2.dim() != 2 or g2.shape[0] != g1.shape[0] or g2.shape[1] < 7:
+        raise ops.GdmError("des_device: gen2_output must be (B, n) with n >= 7 (columns 1..6 drive the simulator)")
+    scan = ops.des_scan(g1, size, dim, note_mod=True)
+    h = {"g1": g1, "size": size, "dim": dim, "b": g1.shape[0], "g2": g2}
+    return _device_prologue(ops.DES_DRAWS_MIDI, h, scan, g2, _instrument_override(instrument, g1.shape[0]), base)
+
+
+def device_prologue_wav(matrices, size=20, use_same_instrument=None, *, base=None):
+    """The wav route's prologue entirely on the device (see ``device_prologue_midi``) -> DevicePrologue."""
+    dim = size - 5
+    m = matrices.detach() if isinstance(matrices, torch.Tensor) else torch.as_tensor(np.asarray(matrices))
+    if not m.is_cuda:
+        raise ops.GdmError("matrix_sim_process runs the prologue on a HIP device; move the generated matrices there")
+    m = m.float()
+    scan = ops.des_scan(m, size, dim, threshold=0.75, norm_aux=True)
+    h = {"g1": m, "size": size, "dim": dim, "b": m.shape[0]}
+    return _device_prologue(ops.DES_DRAWS_WAV, h, scan, scan["aux"],
+                            _instrument_override(use_same_instrument, m.shape[0]), base)
+
+
 def _interleaved_specs(h, draws, spec_of):
     """The reference's order: a sample's spec is complete (and handed to the caller, who simulates) before the next
     sample draws anything."""
@@ -278,6 +440,10 @@ def matrix_to_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None,
     sample whose simulation errors (or exhausts its draw budget) counts as failed and keeps a zero roll.  See the
     module docstring for the four differences from "des".
 
+    simulate="des_device": "des_batch" with the draws and the parameter arithmetic on the device too, one independent
+    stream per sample, no host synchronisation before the one read-back; a sample whose draws the reference would
+    raise for raises here after that read-back (ValueError).  See the module docstring for the differences.
+
     Returns (list of (2,128,end-start) float64 arrays, failed_simulations); with ``return_tensor`` (built-in back end)
     the rolls stay on the device as one (B,2,128,end-start) fp32 tensor."""
     if simulate is None:
@@ -285,12 +451,14 @@ def matrix_to_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None,
                            "simulate=callable (it receives the DesSpec the reference would construct Sim from)")
     start, end = int(start), int(end)
     if isinstance(simulate, str):
-        if simulate not in ("des", "des_batch"):
-            raise ops.GdmError(f"matrix_to_midi: unknown back end {simulate!r} (the built-in ones are \"des\" and "
-                               "\"des_batch\")")
-        back_end = _matrix_to_midi_des if simulate == "des" else _matrix_to_midi_des_batch
-        return back_end(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor, midi_path,
-                        max_events)
+        if simulate not in ("des", "des_batch", "des_device"):
+            raise ops.GdmError(f"matrix_to_midi: unknown back end {simulate!r} (the built-in ones are \"des\", "
+                               "\"des_batch\" and \"des_device\")")
+        if simulate == "des":
+            return _matrix_to_midi_des(gen1_output, gen2_output, adj_size, instrument, start, end, generate,
+                                       return_tensor, midi_path, max_events)
+        return _matrix_to_midi_des_batch(gen1_output, gen2_output, adj_size, instrument, start, end, generate,
+                                         return_tensor, midi_path, max_events, device_draws=simulate == "des_device")
     if return_tensor:
         raise ops.GdmError("matrix_to_midi: return_tensor needs the built-in back end (simulate=\"des\")")
     h = _midi_scan(gen1_output, gen2_output, adj_size)
@@ -363,13 +531,22 @@ def _check_midi_window(start, end):
                          "final slice does not leave end - start columns; use start == 0 or end >= 128)")
 
 
-def _des_batch_run(gen1_output, gen2_output, adj_size, instrument, start, end, generate, max_events):
-    """The body "des_batch" shares between ``matrix_to_midi`` and ``matrix_to_midis``: batched prologue, simulator, one
-    ``des_log_to_roll`` launch, ONE read-back -> (planes (B,2,128,W) on the device; status, track_len, good, save, stop
-    (B,) and tracks (B, cap, 4) int32 host arrays)."""
+def _on(a, dev):
+    """numpy array or tensor -> contiguous tensor on ``dev``."""
+    return a.contiguous() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _des_batch_run(gen1_output, gen2_output, adj_size, instrument, start, end, generate, max_events,
+                   device_draws=False):
+    """The body "des_batch" and "des_device" share between ``matrix_to_midi`` and ``matrix_to_midis``: batched (or
+    device) prologue, simulator, one ``des_log_to_roll`` launch, ONE read-back -> (planes (B,2,128,W) on the device;
+    status, track_len, good, save, stop (B,) and tracks (B, cap, 4) int32 host arrays; draw status (B,) or None)."""
     from . import sim_log_to_midi
     _check_midi_window(start, end)
-    pro = batched_prologue_midi(gen1_output, gen2_output, adj_size, instrument)
+    if device_draws and gen2_output.shape[1] < 16:
+        raise ops.GdmError("matrix_to_midi: gen2_output needs at least 16 columns (gen2_output[10:16] drive the MIDI)")
+    pro = (device_prologue_midi if device_draws else batched_prologue_midi)(gen1_output, gen2_output, adj_size,
+                                                                              instrument)
     h = pro.h
     if h["g2"].shape[1] < 16:
         raise ops.GdmError("matrix_to_midi: gen2_output needs at least 16 columns (gen2_output[10:16] drive the MIDI)")
@@ -378,23 +555,31 @@ def _des_batch_run(gen1_output, gen2_output, adj_size, instrument, start, end, g
     good = (log.stop_reason != ops.DES_STOP_ERROR) & (log.stop_reason != ops.DES_STOP_BUDGET)
     lines = torch.clamp(log.n_records, max=sim_log_to_midi.MAX_LINES + 1)             # lines_read, on the device
     save = (good & ((lines % 100 == 0) | bool(generate))).to(torch.int32)
-    tails = torch.from_numpy(np.ascontiguousarray(h["g2"][:, 10:])).to(dev)
+    tails = _on(h["g2"][:, 10:], dev)
     planes, track, track_len, status = ops.des_log_to_roll(
-        log.value, log.event_id, log.node, log.kind, log.rec_ptr, tails, torch.from_numpy(pro.instruments).to(dev),
-        torch.from_numpy(pro.note_levels).to(dev), save, start, end)
-    # the one read-back: stop reasons with the tracks
-    words = torch.cat([status, track_len, good.to(torch.int32), save, log.stop_reason.to(torch.int32),
+        log.value, log.event_id, log.node, log.kind, log.rec_ptr, tails, _on(pro.instruments, dev),
+        _on(pro.note_levels, dev), save, start, end, check_rec_ptr=not device_draws)
+    # the one read-back: stop reasons (and the device prologue's status words) with the tracks
+    extra = pro.readback_words() if device_draws else []
+    words = torch.cat([status, track_len, good.to(torch.int32), save, log.stop_reason.to(torch.int32), *extra,
                        track.reshape(-1)]).cpu().numpy()
     b = h["b"]
     status, track_len, good, save, stop = (words[k * b:(k + 1) * b] for k in range(5))
-    return planes, status, track_len, good, save, stop, words[5 * b:].reshape(b, ops.DES_MIDI_TRACK_CAP, 4)
+    draw_status = None
+    if device_draws:
+        draw_status = words[5 * b:6 * b]
+        pro.check_flags(words[6 * b:7 * b])
+    tracks = words[(5 + len(extra)) * b:].reshape(b, ops.DES_MIDI_TRACK_CAP, 4)
+    return planes, status, track_len, good, save, stop, tracks, draw_status
 
 
 def _matrix_to_midi_des_batch(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor,
-                              midi_path, max_events):
+                              midi_path, max_events, device_draws=False):
     from . import sim_log_to_midi
-    planes, status, track_len, good, save, _stop, tracks = _des_batch_run(gen1_output, gen2_output, adj_size, instrument,
-                                                                          start, end, generate, max_events)
+    planes, status, track_len, good, save, _stop, tracks, draw_status = _des_batch_run(
+        gen1_output, gen2_output, adj_size, instrument, start, end, generate, max_events, device_draws)
+    if draw_status is not None:
+        DevicePrologue.raise_for(draw_status)
     b = len(status)
     for i in range(b):
         if status[i] >> 8:
@@ -428,23 +613,26 @@ def matrix_to_midis(gen1_output, gen2_output, adj_size, instrument, start, end, 
     """``matrix_to_midi(..., generate=True)`` for a batch that keeps EVERY sample's track instead of the last one's
     (upstream overwrites one generation.mid per sample, MMGAN_MIDI_DES/sim_log_to_midi.py): the same prologue, the same
     simulations and the same ``des_log_to_roll`` launch as the built-in back ends "des" / "des_batch", hence the same
-    rolls under the same ``np.random.seed``, with one read-back.  instrument: None, one program for all samples, or a
+    rolls under the same ``np.random.seed``, with one read-back ("des_device":
+    see the module docstring).  instrument: None, one program for all samples, or a
     list of B (None or a program).  midi_paths: B paths (file i is ``write_midi(tracks[i], midi_paths[i])`` for every
     ok sample) or None to write nothing.  A failed simulation or a per-sample MIDI error marks that sample failed --
     zero roll, no track, no file, its reason in ``reasons`` -- and nothing is raised for it.  -> MidiBatch."""
     from . import sim_log_to_midi, simulation_v3
     start, end = int(start), int(end)
-    if simulate not in ("des", "des_batch"):
-        raise ops.GdmError(f"matrix_to_midis: unknown back end {simulate!r} (the built-in ones are \"des\" and "
-                           "\"des_batch\")")
+    if simulate not in ("des", "des_batch", "des_device"):
+        raise ops.GdmError(f"matrix_to_midis: unknown back end {simulate!r} (the built-in ones are \"des\", "
+                           "\"des_batch\" and \"des_device\")")
     b = gen1_output.shape[0]
     if midi_paths is not None and len(midi_paths) != b:
         raise ops.GdmError(f"matrix_to_midis: {len(midi_paths)} midi_paths for {b} samples")
-    if simulate == "des_batch":
-        planes, status, track_len, good, _save, stop, track = _des_batch_run(gen1_output, gen2_output, adj_size,
-                                                                             instrument, start, end, True, max_events)
+    if simulate in ("des_batch", "des_device"):
+        planes, status, track_len, good, _save, stop, track, draw_status = _des_batch_run(
+            gen1_output, gen2_output, adj_size, instrument, start, end, True, max_events, simulate == "des_device")
         tracks = [track[i, :track_len[i]].copy() for i in range(b)]
         reasons = [None if good[i] else simulation_v3.STOP_REASONS[int(stop[i])] for i in range(b)]
+        for i in np.flatnonzero(draw_status if draw_status is not None else []):
+            reasons[i] = f"error ({draws_error(draw_status[i])})"
     else:
         planes, tracks, status, reasons = _des_run(gen1_output, gen2_output, adj_size, instrument, start, end, True,
                                                    max_events, raise_for_status=False)[:4]
@@ -468,10 +656,15 @@ def _batch_to_mel(pro, max_events):
     dev = pro.h["g1"].device
     log = pro.simulate_on(dev, max_events=max_events, max_records=sim_log_process_music.MAX_LINES + 1)
     notes, n_notes, clip_len, status = ops.des_log_to_notes(log.value, log.event_id, log.node, log.kind, log.rec_ptr,
-                                                            torch.from_numpy(pro.note_levels).to(dev))
+                                                            _on(pro.note_levels, dev),
+                                                            check_rec_ptr=not isinstance(pro, DevicePrologue))
     frames = ops.synth_frames(notes, n_notes, clip_len)
     mel = util._db_from_frames(frames, pro.h["b"], ops.SYNTH_FRAMES, ops.SYNTH_RATE, ops.SYNTH_NFFT, 128, 20, 8300, 80)
-    words = torch.stack([status, log.stop_reason]).cpu()
+    extra = pro.readback_words() if isinstance(pro, DevicePrologue) else []
+    words = torch.stack([status, log.stop_reason, *extra]).cpu()
+    if extra:                                    # the device prologue's own errors come first, as in the reference
+        pro.check_flags(words[3].numpy())
+        pro.raise_for(words[2].numpy())
     for i, reason in enumerate(words[1].tolist()):
         if reason in (ops.DES_STOP_ERROR, ops.DES_STOP_BUDGET):
             from . import simulation_v3
@@ -547,19 +740,23 @@ def matrix_to_wav(matrices, size=20, use_same_instrument=None, start=0, end=174,
     simulate="des_batch": batched prologue, ONE device simulator launch for all B samples (each from its own snapshot
     of numpy's stream, 5001-record cap), then the same three stages reading the device log in place.  A sample whose
     simulation errors raises ValueError after all stages are enqueued (one read-back).  See the module docstring for
-    the four differences from "des"."""
+    the four differences from "des".
+    simulate="des_device": "des_batch" with the draws and the parameter arithmetic on the device too, one independent
+    stream per sample; ValueError / IndexError of the reference's draws are raised after the one read-back.  See the
+    module docstring for the differences."""
     if simulate is None:
         raise ops.GdmError("matrix_to_wav: pass simulate=\"des\" for the built-in DES / synth back end or "
                            "simulate=callable (it receives the DesSpec the reference would construct Sim from)")
-    if isinstance(simulate, str) and simulate == "des_batch":
-        mel, _notes = _batch_to_mel(batched_prologue_wav(matrices, size, use_same_instrument), max_events)
+    if isinstance(simulate, str) and simulate in ("des_batch", "des_device"):
+        prologue = batched_prologue_wav if simulate == "des_batch" else device_prologue_wav
+        mel, _notes = _batch_to_mel(prologue(matrices, size, use_same_instrument), max_events)
         return mel[:, :, start:end].to(device)
     h = _wav_scan(matrices, size)
     specs = _interleaved_specs(h, _wav_draws, lambda h_, i, r, src, sd: _wav_spec(h_, i, r, src, sd, use_same_instrument))
     if isinstance(simulate, str):
         if simulate != "des":
-            raise ops.GdmError(f"matrix_to_wav: unknown back end {simulate!r} (the built-in ones are \"des\" and "
-                               "\"des_batch\")")
+            raise ops.GdmError(f"matrix_to_wav: unknown back end {simulate!r} (the built-in ones are \"des\", "
+                               "\"des_batch\" and \"des_device\")")
         mel, _notes = _specs_to_mel(specs, h["g1"].device, max_events)
         return mel[:, :, start:end].to(device)
     spectrograms = [torch.as_tensor(simulate(spec, index=i)) for i, spec in enumerate(specs)]

@@ -199,9 +199,10 @@ def _no_bridge(*_a, **_k):
 def des_fake_provider(adj_size, instrument, start, end, generate=False, midi_path=None, batched=False):
     """The built-in bridge as a fake_provider: the reference's matrix_to_midi call (network_tests.py:189 / :204) with
     the DES core and the batched log -> MIDI -> piano-roll kernel behind it; the rolls stay on the device.
-    batched: simulate all samples in one device launch (matrix_to_midi(simulate="des_batch"))."""
+    batched: simulate all samples in one device launch (matrix_to_midi(simulate="des_batch")); a back end's name
+    ("des_batch", "des_device") selects that one."""
     from .matrix_sim_process import matrix_to_midi
-    simulate = "des_batch" if batched else "des"
+    simulate = batched if isinstance(batched, str) else ("des_batch" if batched else "des")
 
     def provider(gen_output1, gen_output2, count):
         return matrix_to_midi(gen_output1, gen_output2, adj_size=adj_size, instrument=instrument, start=start, end=end,
@@ -227,10 +228,10 @@ class MultiModalGAN(nn.Module):
         self.midi_path = midi_path          # where generate_midi's built-in bridge writes (default: upstream's path)
         self.generate_provider = None
         if isinstance(fake_provider, str):
-            if fake_provider not in ("des", "des_batch"):
-                raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridges are \"des\" and "
-                                 "\"des_batch\")")
-            batched = fake_provider == "des_batch"
+            if fake_provider not in ("des", "des_batch", "des_device"):
+                raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridges are \"des\", "
+                                 "\"des_batch\" and \"des_device\")")
+            batched = fake_provider
             fake_provider = des_fake_provider(adj_size, instrument, start, end, batched=batched)
             self.generate_provider = des_fake_provider(adj_size, instrument, start, end, generate=True,
                                                        midi_path=midi_path, batched=batched)
@@ -314,7 +315,8 @@ class MultiModalGAN(nn.Module):
         """``generate_midi`` for a batch that keeps every sample: ``sample`` (one launch), then
         ``matrix_sim_process.matrix_to_midis`` with the module's adj_size, instrument, start and end, which writes
         ``out_dir/name.format(i)`` for every sample whose simulation and MIDI conversion succeeded.  Works whatever
-        ``fake_provider`` the module was built with: bridge names the built-in one, "des" or "des_batch".
+        ``fake_provider`` the module was built with: bridge names the built-in one, "des", "des_batch" or
+        "des_device".
         Returns the MidiBatch (rolls, tracks, ok, reasons) with ``paths``: None where ``ok`` is false."""
         from .matrix_sim_process import matrix_to_midis
         out1, out2 = self.sample(n_samples, noise1=noise1, noise2=noise2, input_tensor=input_tensor,
@@ -340,7 +342,8 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
         (network_tests.py:229-230).  At most one of train_loader / midi_dir / pickle_file.
     fake_provider(g1_out, g2_out, count) -> ((B,2,128,T) tensor, failed): the DES bridge; "des" -> the built-in one
         (DES core + batched log -> MIDI -> piano-roll kernel); "des_batch" -> the same with the simulation batched on
-        the device (matrix_sim_process lists what differs); None -> synthetic rolls.
+        the device (matrix_sim_process lists what differs); "des_device" -> the draws on the device too, one stream
+        per sample; None -> synthetic rolls.
     save_dir: if given, per-epoch ``losses/*.pkl`` and ``models/mmgan_{a}_{b}_epoch_{e}.pth`` are written there with
         the reference's file names; model_path: state_dict to resume from (optimizer state is not saved, as upstream).
     criterion: "bce" | "mse" | "l1" -- the reference picks one by moving a comment (network_tests.py:248-250:
@@ -368,11 +371,10 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
     roll_size = (2, 128, sequence_length)
     start = 100
     if isinstance(fake_provider, str):
-        if fake_provider not in ("des", "des_batch"):
-            raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridges are \"des\" and "
-                             "\"des_batch\")")
-        fake_provider = des_fake_provider(adj_size, 0, start, start + sequence_length,
-                                          batched=fake_provider == "des_batch")
+        if fake_provider not in ("des", "des_batch", "des_device"):
+            raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridges are \"des\", "
+                             "\"des_batch\" and \"des_device\")")
+        fake_provider = des_fake_provider(adj_size, 0, start, start + sequence_length, batched=fake_provider)
     mmgan = MultiModalGAN(z_dim=noise_dim, adj_size=adj_size, roll_size=roll_size, input_dim=max_beat_length,
                           output_dim=gen2_output_dim, instrument=0, start=start, end=start + sequence_length,
                           device=device, fake_provider=fake_provider)
@@ -479,6 +481,7 @@ def generate_main(argv):
     ap.add_argument("--start", type=int, default=100)
     ap.add_argument("--end", type=int, default=150)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--bridge", choices=("des", "des_batch", "des_device"), default="des_batch")
     a = ap.parse_args(argv)
     if a.generate < 1:
         ap.error("--generate needs N >= 1")
@@ -491,7 +494,7 @@ def generate_main(argv):
     mmgan.load_state_dict(torch.load(a.checkpoint, map_location=device, weights_only=True), strict=True)
     beats = datasets._fit_beats(datasets.get_beats(datasets.read_midi(a.beats_from)), 50)
     res = mmgan.generate_midis(a.generate, input_tensor=torch.as_tensor(np.asarray(beats), dtype=torch.float32)[None],
-                               out_dir=a.out_dir)
+                               out_dir=a.out_dir, bridge=a.bridge)
     for i, path in enumerate(res.paths):
         print(path if path is not None else f"sample {i}: no file ({res.reasons[i]})")
     return 0
@@ -515,9 +518,9 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--sequence-length", type=int, default=50)
     ap.add_argument("--sample-size", type=int, default=300)
-    ap.add_argument("--fake-provider", choices=("des", "des_batch"), default=None,
+    ap.add_argument("--fake-provider", choices=("des", "des_batch", "des_device"), default=None,
                     help="des: the built-in DES bridge; des_batch: the same with the simulation batched on the "
-                         "device; default: synthetic fake rolls")
+                         "device; des_device: the draws on the device too; default: synthetic fake rolls")
     ap.add_argument("--save-dir", default=None)
     ap.add_argument("--max-steps", type=int, default=None, help="steps per epoch at most")
     a = ap.parse_args(argv)

@@ -997,6 +997,61 @@ def des_routing(g, s, dim, src_mask, residue_col):
     return out
 
 
+# ---- per-sample draws and parameters on the device (csrc/des_draws.hip; the chain is csrc/des_draws.h) --------------------
+DES_DRAWS_MIDI, DES_DRAWS_WAV = 0, 1
+DES_DRAWS_MAX_DIM = 64          # DES_DRAWS_MAX_DIM
+DES_DRAWS_NO_INSTRUMENT = -2 ** 31
+# status -> (exception type the reference raises, text)
+DES_DRAWS_ERRORS = {
+    1: (ValueError, "'a' cannot be empty unless no samples are taken (a row without a candidate column for its residue)"),
+    2: (ValueError, "The truth value of an array with more than one element is ambiguous (more than one thresholded "
+                    "source cannot be processed)"),
+    3: (IndexError, "a thresholded source column is out of bounds for the routing matrix"),
+    4: (ValueError, "draw budget exhausted"),
+    5: (ValueError, "cannot convert 3000 * gen2_output[6] to an integer (NaN, infinity or beyond int64)"),
+}
+_DES_DRAWS_FIELDS = (("src", torch.uint8, "d"), ("cols", torch.int32, "d"), ("seed", torch.int64, ""),
+                     ("customers", torch.int64, ""), ("loc", torch.float64, "d"), ("scale", torch.float64, "d"),
+                     ("queue_cap", torch.int32, "d"), ("instruments", torch.int32, "d"), ("note_levels", torch.int32, "d"),
+                     ("mt_key", torch.int32, "k"), ("mt_pos", torch.int32, ""), ("has_gauss", torch.int32, ""),
+                     ("gauss", torch.float64, ""), ("status", torch.int32, ""))
+
+
+def des_draws(route, s, dim, base, scan, params, instrument_override=None, out=None):
+    """``gdm_des_draws``: base (B) i32 (uint32 bit patterns: sample b draws from RandomState(base[b])), ``scan`` the dict
+    ``des_scan`` returned (used in place, nothing is read back), params: gen2_output (B,n2) fp32 (route DES_DRAWS_MIDI) or
+    ``scan["aux"]`` (DES_DRAWS_WAV); instrument_override (B) i32 or None (DES_DRAWS_NO_INSTRUMENT = the scan's).  Returns a
+    dict of device tensors: src (B,dim) u8, cols (B,dim) i32, seed, customers (B) i64, loc, scale (B,dim) f64,
+    queue_cap, instruments, note_levels (B,dim) i32, mt_key (B,624) i32 (uint32 bit patterns), mt_pos, has_gauss (B)
+    i32, gauss (B) f64, status (B) i32 (keys of DES_DRAWS_ERRORS; 0 = ok).  ``out``: such a dict to write into."""
+    zmask, inst, notes, thr = scan["zero_mask"], scan["instruments"], scan["note_levels"], scan.get("thr_mask")
+    _need_gpu(base, zmask, inst, notes, thr, params, instrument_override)
+    b = base.numel()
+    if route not in (DES_DRAWS_MIDI, DES_DRAWS_WAV):
+        raise GdmError("des_draws: route must be DES_DRAWS_MIDI or DES_DRAWS_WAV")
+    if params.dtype != torch.float32 or params.shape[0] != b:
+        raise GdmError("des_draws: params must be a float32 tensor with one row (block) per sample")
+    params = params.contiguous().reshape(b, -1)
+    for t, shape, dt in ((base, (b,), torch.int32), (zmask, (b, dim), torch.int64), (inst, (b, dim), torch.int32),
+                         (notes, (b, dim), torch.int32)) + (((thr, (b, s), torch.uint8),) if thr is not None else ()) + \
+            (((instrument_override, (b,), torch.int32),) if instrument_override is not None else ()):
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise GdmError(f"des_draws: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
+                           f"{tuple(t.shape)}")
+    dev = base.device
+    shapes = {"d": (b, dim), "": (b,), "k": (b, 624)}
+    if out is None:
+        out = {name: torch.empty(shapes[kind], dtype=dt, device=dev) for name, dt, kind in _DES_DRAWS_FIELDS}
+    for name, dt, kind in _DES_DRAWS_FIELDS:
+        t = out[name]
+        _need_gpu(t)
+        if tuple(t.shape) != shapes[kind] or t.dtype != dt or not t.is_contiguous():
+            raise GdmError(f"des_draws: out[{name!r}] must be a contiguous {dt} tensor of shape {shapes[kind]}")
+    _call("gdm_des_draws", int(route), b, int(s), int(dim), _p(base), _p(zmask), _p(thr), _p(inst), _p(notes), _p(params),
+          params.shape[1], _p(instrument_override), *(_p(out[name]) for name, _dt, _k in _DES_DRAWS_FIELDS), _stream())
+    return out
+
+
 # ---- batched DES simulator on the device (csrc/des_batch.hip; the event logic is csrc/des_sim.h) ---------------------------
 DES_STOP_EMPTY, DES_STOP_CUSTOMERS, DES_STOP_EVENTS, DES_STOP_ERROR, DES_STOP_RECORDS, DES_STOP_BUDGET = range(6)
 DES_BATCH_MAX_DIM = 128         # GDM_DES_BATCH_MAX_DIM
@@ -1139,7 +1194,7 @@ def des_roll_width(start, end):
 
 
 def des_log_to_roll(value, event_id, node, kind, rec_ptr, tails, instruments, note_levels, save, start, end,
-                    sequence_length=100):
+                    sequence_length=100, *, check_rec_ptr=True):
     """Event records of B samples (CSR: rec_ptr (B+1) i64) -> (planes (B,2,128,W) fp32, track (B,512,4) i32, track_len
     (B) i32, status (B) i32), all device tensors; one launch (gdm_des_log_to_roll, include/gdm.h)."""
     _need_gpu(value, event_id, node, kind, rec_ptr, tails, instruments, note_levels, save)
@@ -1159,8 +1214,10 @@ def des_log_to_roll(value, event_id, node, kind, rec_ptr, tails, instruments, no
             raise GdmError("des_log_to_roll: instruments / note_levels must be contiguous (B, dim) int32")
     if save.dtype != torch.int32 or save.shape != (b,) or not save.is_contiguous():
         raise GdmError("des_log_to_roll: save must be a contiguous (B,) int32 tensor")
-    # argument validation (one small reduction + sync), not arithmetic of the path: offsets must ascend within [0, n]
-    if bool(((rec_ptr[1:] < rec_ptr[:-1]).any() | (rec_ptr[0] < 0) | (rec_ptr[-1] > n)).item()):
+    # argument validation (one small reduction + sync), not arithmetic of the path: offsets must ascend within [0, n].
+    # check_rec_ptr=False: the caller vouches for offsets that never left the device (``des_run_batch``'s pack step
+    # wrote them); the kernel clamps every offset to [0, n] either way
+    if check_rec_ptr and bool(((rec_ptr[1:] < rec_ptr[:-1]).any() | (rec_ptr[0] < 0) | (rec_ptr[-1] > n)).item()):
         raise GdmError(f"des_log_to_roll: rec_ptr must ascend within [0, {n}] (the number of records)")
     start, end = int(start), int(end)
     w = des_roll_width(start, end)
@@ -1201,7 +1258,7 @@ def synth_tables(device):
     return _synth_tables[key]
 
 
-def des_log_to_notes(value, event_id, node, kind, rec_ptr, note_levels):
+def des_log_to_notes(value, event_id, node, kind, rec_ptr, note_levels, *, check_rec_ptr=True):
     """Event records of B samples (CSR: rec_ptr (B+1) i64) -> (notes (B,5000,4) i64 of (on_tick, off_tick, pitch,
     velocity), n_notes (B) i32, clip_len (B) i64, status (B) i32), all device tensors; one launch
     (gdm_des_log_to_notes, include/gdm.h)."""
@@ -1216,7 +1273,7 @@ def des_log_to_notes(value, event_id, node, kind, rec_ptr, note_levels):
     if note_levels.dtype != torch.int32 or note_levels.dim() != 2 or note_levels.shape[0] != b or \
             not note_levels.is_contiguous():
         raise GdmError("des_log_to_notes: note_levels must be contiguous (B, dim) int32")
-    if bool(((rec_ptr[1:] < rec_ptr[:-1]).any() | (rec_ptr[0] < 0) | (rec_ptr[-1] > n)).item()):
+    if check_rec_ptr and bool(((rec_ptr[1:] < rec_ptr[:-1]).any() | (rec_ptr[0] < 0) | (rec_ptr[-1] > n)).item()):
         raise GdmError(f"des_log_to_notes: rec_ptr must ascend within [0, {n}] (the number of records)")
     dev = value.device
     notes = torch.zeros((b, DES_NOTES_MAX, 4), dtype=torch.int64, device=dev)

@@ -251,8 +251,14 @@ def run_batch_device(adj, loc, scale, queue_cap, seed, customers, states=None, *
         if torch.is_tensor(queue_cap):
             raise ValueError("run_batch_device: pass max_queue_cap with a device queue_cap (it sizes the workspace)")
         max_queue_cap = max(1, int(np.asarray(queue_cap).max()))
-    key, pos, has, gauss = pack_states(states, b)
-    k, p, h, g = up(key.view(np.int32), torch.int32), up(pos, torch.int32), up(has, torch.int32), up(gauss, torch.float64)
+    if isinstance(states, (tuple, list)) and len(states) == 4 and torch.is_tensor(states[0]):
+        # (mt_key (B,624) i32, mt_pos, has_gauss (B) i32, gauss (B) f64) already on the device (``ops.des_draws``):
+        # updated in place like every state the kernel is given
+        k, p, h, g = (up(t, dt) for t, dt in zip(states, (torch.int32, torch.int32, torch.int32, torch.float64)))
+    else:
+        key, pos, has, gauss = pack_states(states, b)
+        k, p, h, g = (up(key.view(np.int32), torch.int32), up(pos, torch.int32), up(has, torch.int32),
+                      up(gauss, torch.float64))
     out = ops.des_run_batch(up(adj, torch.float64), up(loc, torch.float64), up(scale, torch.float64),
                             up(queue_cap, torch.int32), up(seed, torch.int64), up(customers, torch.int64), k, p, h, g,
                             max_queue_cap=max_queue_cap, max_events=max_events, max_records=max_records,

@@ -508,6 +508,41 @@ int gdm_des_scan(const float* g, int64_t sample_stride, int B, int S, int dim, f
 int gdm_des_routing(const float* g, int64_t sample_stride, int B, int S, int dim, const uint8_t* src_mask,
                     const int32_t* residue_col, double* out, void* stream);
 
+/* ---- the draws between the two, per sample on a stream of its own ("des_device"; csrc/des_draws.h is the one source):
+ * sample b's stream is numpy's RandomState(base[b]) (init_genrand, position 624, no cached gauss).  On it, in the
+ * reference's order: the random sources np.random.choice(dim, size=k, replace=False) (MMGAN_MIDI_DES/
+ * matrix_sim_process.py:44, k = dim / 4; GAN_DES/matrix_sim_process.py:28, k = S / 8, drawn only when no column of
+ * thr_mask passes, :25-30), one np.random.choice(candidates) per row for the column that takes the rounding residue
+ * (:102 / :87; candidates = columns not zero in zero_mask, not sources, not the row itself), then the reseed pair
+ * np.random.seed(np.random.randint(0, 99999, size=1)); seeds = np.random.randint(0, 99999, size=1) (:114-115 / :105-106).
+ * route 0 (midi): params = gen2_output (B, n_params >= 7) fp32: loc / scale = |p[1] * 50|, |p[2] * 50| for a source and
+ *   |p[3] * 10|, |p[4] * 10| for a server (:72-74), customers = max(200, max(1000, int(3000 * p[6]))) (:13, :151-163).
+ * route 1 (wav): params = gdm_des_scan's aux (B, 2, dim), n_params = 2 dim: 30 r3, 15 r4 / 5 r3, 3 r4 (:57-59),
+ *   customers = 1000 (:110); needs thr_mask (B,S) and 1 <= S / 8 <= dim.
+ * All arithmetic is float32 widened to float64, as numpy's.  instrument_override (B) i32 or NULL: a program for every
+ * node of the sample, INT32_MIN = none (the scan's instruments).  Outputs: src (B,dim) u8, cols (B,dim) i32 -- what
+ * gdm_des_routing takes --, seed, customers (B) i64, loc, scale (B,dim) f64, queue_cap (B,dim) i32 = 254, instruments,
+ * note_levels (B,dim) i32, the stream after the last draw (mt_key (B,624), mt_pos, has_gauss (B) i32, cached_gauss (B)
+ * f64) -- what gdm_des_run_batch takes --, status (B) i32: 0 ok, 1 empty candidate list (ValueError upstream), 2 more
+ * than one thresholded source (ValueError, GAN_DES :30), 3 thresholded column >= dim (IndexError, :67), 4 draw budget
+ * exhausted, 5 int(3000 * p[6]) undefined (NaN, inf, beyond int64).  A sample with status != 0 has zero src / cols /
+ * seed, the stream of RandomState(base[b]) untouched, and scale -1, which makes gdm_des_run_batch end it with
+ * GDM_DES_STOP_ERROR and no records.  dim <= S <= 64.  gdm_des_draws: device arrays, one wave per sample;
+ * gdm_des_draws_host: host arrays, the same source, the same bits.                                                   */
+int gdm_des_draws(int route, int B, int S, int dim, const uint32_t* base, const uint64_t* zero_mask,
+                  const uint8_t* thr_mask_or_null, const int32_t* scan_instruments, const int32_t* scan_note_levels,
+                  const float* params, int n_params, const int32_t* instrument_override_or_null, uint8_t* src,
+                  int32_t* cols, int64_t* seed, int64_t* customers, double* loc, double* scale, int32_t* queue_cap,
+                  int32_t* instruments, int32_t* note_levels, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                  double* cached_gauss, int32_t* status, void* stream);
+int gdm_des_draws_host(int route, int B, int S, int dim, const uint32_t* base, const uint64_t* zero_mask,
+                       const uint8_t* thr_mask_or_null, const int32_t* scan_instruments,
+                       const int32_t* scan_note_levels, const float* params, int n_params,
+                       const int32_t* instrument_override_or_null, uint8_t* src, int32_t* cols, int64_t* seed,
+                       int64_t* customers, double* loc, double* scale, int32_t* queue_cap, int32_t* instruments,
+                       int32_t* note_levels, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                       double* cached_gauss, int32_t* status);
+
 /* ---- piano-roll rasteriser (the scatter of generate_piano_roll, MMGAN_MIDI_DES/datasets.py:29-45), batched over files.
  * Messages of row r = file * 128 + note are ev_*[row_ptr[r] .. row_ptr[r+1]) in file order; ev_step = one-second time
  * step of the message, ev_vel = velocity of a note_on (0..127) or -1 for a note_off.  Writes roll, dur (n_files,128,W)
