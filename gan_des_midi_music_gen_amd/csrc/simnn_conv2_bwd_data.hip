@@ -244,24 +244,11 @@ __global__ __launch_bounds__(256) void conv2_bwd_data_kernel(const T* __restrict
   rs.code2 = make_rsrc(code2, (uint32_t)B * H2 * W2 * 16);
   rs.dp1 = make_rsrc(dp1, DP1 ? (uint32_t)B * H1 * W1 * 16 * sizeof(T) : 0u);
   rs.code1 = make_rsrc(code1, FUSE ? (uint32_t)B * H1 * ((W1 + 3) >> 2) * 32 : 0u);
-  copy_to_lds(w_s, wb, C2<T>::WB_ELEMS);
-  if constexpr (sizeof(T) == 2) code2_tables_init((uint32_t*)tab_s);
-  if constexpr (MF) {
-    // argmax code (bits 1:0 position, bit 2 live) -> v_perm selectors that place the bf16 gradient (bytes 0,1 of the
-    // source) in the low (dx = 0) or high (dx = 1) half of the A dword of pooling row dy, or nowhere (0x0c = 0x00)
-    if (t < 8) {
-      const uint32_t none = 0x0c0c0c0cu, lo = 0x0c0c0100u, hi = 0x01000c0cu;
-      const bool live = t >= 4;
-      const int pos = t & 3;
-      tbl_s[2 * t] = (live && (pos >> 1) == 0) ? ((pos & 1) ? hi : lo) : none;
-      tbl_s[2 * t + 1] = (live && (pos >> 1) == 1) ? ((pos & 1) ? hi : lo) : none;
-    }
-    for (int i = t; i < XP_ONES / 2; i += 256) ((uint32_t*)(xp_s + 4 * XP_PLANE))[i] = 0x3f803f80u;   // bf16 1.0 pairs
-    // plane cells no step ever writes (row padding, columns the window does not reach) must hold finite values:
-    // they are read by lanes whose result columns are discarded
-    for (int i = t; i < 4 * XP_PLANE / 2; i += 256) ((uint32_t*)xp_s)[i] = 0u;
-  }
-
+  // kernel start = ONE memory round trip: the weight image's loads go out first, the first two steps' loads right
+  // behind them; the LDS-only set-up follows, and the image is stored (lds_image_finish waits for it alone) in front
+  // of the first barrier
+  LdsImage<T, C2<T>::WB_ELEMS> wimg;
+  lds_image_begin(wimg, wb);
   BdLane<FUSE, XVEC> ln;
 #pragma unroll
   for (int k = 0; k < BD_DCIT; ++k) {
@@ -320,6 +307,23 @@ __global__ __launch_bounds__(256) void conv2_bwd_data_kernel(const T* __restrict
   p1 = advance(p0);
   bd_issue<T, FUSE, XVEC>(rg_a, ln, p0.b, p0.c0, p0.rq, rs, H1, W1, H2, W2, x0, x1, bsplit, H, W);
   if constexpr (AHEAD2) bd_issue<T, FUSE, XVEC>(rg_b, ln, p1.b, p1.c0, p1.rq, rs, H1, W1, H2, W2, x0, x1, bsplit, H, W);
+  if constexpr (sizeof(T) == 2) code2_tables_init((uint32_t*)tab_s);
+  if constexpr (MF) {
+    // argmax code (bits 1:0 position, bit 2 live) -> v_perm selectors that place the bf16 gradient (bytes 0,1 of the
+    // source) in the low (dx = 0) or high (dx = 1) half of the A dword of pooling row dy, or nowhere (0x0c = 0x00)
+    if (t < 8) {
+      const uint32_t none = 0x0c0c0c0cu, lo = 0x0c0c0100u, hi = 0x01000c0cu;
+      const bool live = t >= 4;
+      const int pos = t & 3;
+      tbl_s[2 * t] = (live && (pos >> 1) == 0) ? ((pos & 1) ? hi : lo) : none;
+      tbl_s[2 * t + 1] = (live && (pos >> 1) == 1) ? ((pos & 1) ? hi : lo) : none;
+    }
+    for (int i = t; i < XP_ONES / 2; i += 256) ((uint32_t*)(xp_s + 4 * XP_PLANE))[i] = 0x3f803f80u;   // bf16 1.0 pairs
+    // plane cells no step ever writes (row padding, columns the window does not reach) must hold finite values:
+    // they are read by lanes whose result columns are discarded
+    for (int i = t; i < 4 * XP_PLANE / 2; i += 256) ((uint32_t*)xp_s)[i] = 0u;
+  }
+  lds_image_finish(wimg, w_s);
   __syncthreads();                                          // weight image complete
 
   // Wave w computes the 4 output rows of column tile w (16 columns).  A dc2 row fragment (one per tap column aw) feeds

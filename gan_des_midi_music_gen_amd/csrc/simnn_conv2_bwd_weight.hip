@@ -38,7 +38,6 @@ __global__ __launch_bounds__(256) void conv2_bwd_weight_kernel(const T* __restri
   T* dc_s = (T*)dyn_smem;
   T* p_s = dc_s + BW<T>::DC_ELEMS;
   const unsigned char* tab_s = (const unsigned char*)(p_s + BW<T>::P_ELEMS);     // bf16: code2 selector tables
-  if constexpr (sizeof(T) == 2) code2_tables_init((uint32_t*)(p_s + BW<T>::P_ELEMS));    // (first barrier: in the loop)
   const int t = threadIdx.x, l = t & 63, wv = t >> 6, lr = l & 15, lg = l >> 4;
   const int nrq = (H1 + ROWS - 1) / ROWS, G = gridDim.x;
   f32x4 acc[2][9];
@@ -119,6 +118,8 @@ __global__ __launch_bounds__(256) void conv2_bwd_weight_kernel(const T* __restri
   STAMP_DECL;
   issue(b, c0, rq, false);
   STAMP(4);
+  // (LDS-only set-up behind the first loads; first barrier: in the loop)
+  if constexpr (sizeof(T) == 2) code2_tables_init((uint32_t*)(p_s + BW<T>::P_ELEMS));
 
   // per-lane fragment addresses that never change: swizzled p1 band columns for (segment, kw, lo/hi)
   int pcol_off[2][3][2];
@@ -268,35 +269,56 @@ __global__ __launch_bounds__(256) void conv2_bwd_weight_kernel(const T* __restri
     s = sn; b = bn; c0 = c0n; rq = rqn; rq_first = rq_first_n; rq_end = rq_end_n;
   }
   STAMP_FLUSH;
-  // ---- cross-wave reduction in fixed order (wave 0 stores, waves 1..3 add in turn: each element is touched by the
-  //      same lane position in every wave) and slab write.  slab layout: [o 32][tap 9][ci 16] then 32 bias sums.
+  // ---- cross-wave reduction in fixed order and slab write.  slab layout: [o 32][tap 9][ci 16] then 32 bias sums.
+  // All four waves work at once, three taps at a time (the staging must fit the LDS of the step loop): every wave
+  // stores its accumulators of the chunk as whole f32x4 [wave][i, tap][lane]; after one barrier each thread reads the
+  // four waves' values of six slab elements -- all 24 reads issued before the first add -- and stores
+  // ((w0 + w1) + w2) + w3 straight into the slab, 48-float runs per output channel.  (Waves taking turns at a
+  // read-modify-write of one LDS image, then a copy to the slab, gave the same sums with every LDS access waited for
+  // by itself and three waves idle: ~7 us per launch that nothing hides, the workgroups all end together.)
   __syncthreads();
-  float* red = (float*)dyn_smem;   // 4608 floats (+ 2048 for the bias sums)
-#pragma unroll 1
-  for (int turn = 0; turn < 4; ++turn) {
-    if (wv == turn) {
+  constexpr int TPC = 3, STAGE_W = 2 * TPC * 64 * 4;      // taps per chunk; floats per wave of the staging image
+  f32x4* stage = (f32x4*)dyn_smem;
+  const float* stage_f = (const float*)dyn_smem;
+  float* bias_s = (float*)dyn_smem + 4 * STAGE_W;          // 2048 floats behind the staging image (host: sm covers both)
+  float* slab = slabs + (int64_t)blockIdx.x * (4608 + 32);
+  int red_src[6], red_dst[6];
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+  for (int k = 0; k < 6; ++k) {
+    const int j = t + 256 * k, o = j / (16 * TPC), rem = j % (16 * TPC);     // rem = tap of the chunk * 16 + ci
+    // accumulator element of (o, ci): tile i = o / 16, lane (lg = (o / 4) % 4, lr = ci), component r = o % 4
+    red_src[k] = ((((o >> 4) * TPC + (rem >> 4)) * 64 + ((o >> 2) & 3) * 16 + (rem & 15)) << 2) + (o & 3);
+    red_dst[k] = o * 144 + rem;
+  }
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
+  for (int c = 0; c < 9 / TPC; ++c) {
+    if (c > 0) __syncthreads();                            // the previous chunk has been read
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int idx = ((16 * i + 4 * lg + r) * 9 + tap) * 16 + lr;   // C row = o, C col = ci
-            red[idx] = turn == 0 ? acc[i][tap][r] : red[idx] + acc[i][tap][r];
-          }
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int tl = 0; tl < TPC; ++tl) stage[(wv * 2 * TPC + i * TPC + tl) * 64 + l] = acc[i][TPC * c + tl];
+    if (c == 0) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) bias_s[t * 8 + e] = bsum[e];
     }
     __syncthreads();
-  }
-  float* slab = slabs + (int64_t)blockIdx.x * (4608 + 32);
-  for (int i = t; i < 4608; i += 256) slab[i] = red[i];
-  __syncthreads();
+    float v[6][4];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) red[t * 8 + e] = bsum[e];
-  __syncthreads();
-  if (t < 32) {
+    for (int k = 0; k < 6; ++k)
+#pragma unroll
+      for (int w = 0; w < 4; ++w) v[k][w] = stage_f[red_src[k] + w * STAGE_W];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) slab[red_dst[k] + 16 * TPC * c] = ((v[k][0] + v[k][1]) + v[k][2]) + v[k][3];
+  }
+  if (t < 32) {                                            // bias sums: thread 4k + og holds channels 8 og .. 8 og + 7
     const int og = t >> 3, e = t & 7;
+    float bv[64];
+#pragma unroll
+    for (int k = 0; k < 64; ++k) bv[k] = bias_s[(4 * k + og) * 8 + e];
+    __builtin_amdgcn_sched_barrier(0);                     // all reads in flight before the first (ordered) add
     float s = 0.f;
-    for (int k = 0; k < 64; ++k) s += red[(4 * k + og) * 8 + e];
+#pragma unroll
+    for (int k = 0; k < 64; ++k) s += bv[k];
     slab[4608 + t] = s;
   }
 }
@@ -310,7 +332,7 @@ inline SegPlan bwd_weight_plan(int B, int H1, int W1) {
 template <typename T>
 void launch_bwd_weight(const void* dp2, const uint8_t* code2, const void* p1, int B, int H1, int W1, const SegPlan& pl,
                        float* slabs, hipStream_t s) {
-  const size_t red_bytes = (size_t)(4608 + 2048) * sizeof(float);
+  const size_t red_bytes = (size_t)(4 * 6 * 256 + 2048) * sizeof(float);   // epilogue: staging image + bias sums
   size_t sm = (size_t)(BW<T>::DC_ELEMS + BW<T>::P_ELEMS) * sizeof(T) + (sizeof(T) == 2 ? C2T_BYTES : 0);
   if (sm < red_bytes) sm = red_bytes;
   allow_lds(conv2_bwd_weight_kernel<T>, sm);

@@ -215,12 +215,15 @@ __global__ __launch_bounds__(256) void conv2_fwd_kernel(const T* __restrict__ p1
     __syncthreads();                                        // the band may be overwritten
     STAMP(4);
   };
-  copy_to_lds(w_s, wf, C2<T>::WF_ELEMS);
   float bo[2][4];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) bo[i][r] = bias[8 * lg + 4 * i + r];     // channel map of conv2_fwd_tile
+  // kernel start = ONE memory round trip: the weight image's loads go out first, the first two bands right behind them;
+  // the image is stored (lds_image_finish waits for it alone) in front of the first run()'s barrier
+  LdsImage<T, C2<T>::WF_ELEMS> wimg;
+  lds_image_begin(wimg, wf);
   P1Stage<T, ROWS + 2> sa, sb;
   // Workgroups are dealt round-robin over the 8 XCDs (each with its own L2): give every XCD a CONTIGUOUS run of tile
   // ids per round, so that the tiles that share halo rows / columns (vertical neighbours are n_ctiles ids apart) are
@@ -230,6 +233,7 @@ __global__ __launch_bounds__(256) void conv2_fwd_kernel(const T* __restrict__ p1
   if ((G & 7) == 0) u = (u & 7) * (G >> 3) + (u >> 3);
   issue(sa, u);
   issue(sb, u + G);
+  lds_image_finish(wimg, w_s);
   STAMP(5);
   for (; u + G < n_tiles; u += 2 * G) {
     run(sa, u, bo);

@@ -134,10 +134,34 @@ __device__ __forceinline__ float conv2_packed_value(const float* w, int i) {
   }
 }
 
-template <typename T>
-__device__ __forceinline__ void copy_to_lds(T* __restrict__ dst, const T* __restrict__ src, int nelems) {
-  const int chunks = nelems * (int)sizeof(T) / 16;
-  for (int i = threadIdx.x; i < chunks; i += 256) ((f32x4*)dst)[i] = ((const f32x4*)src)[i];
+// A packed weight image (ELEMS elements of T) on its way from global memory to LDS, as a begin / finish pair: begin
+// issues all of its 16-byte loads into registers -- a compile-time number of buffer loads outside any branch, lanes past
+// the end read zeros that are never stored --, finish stores them.  A kernel calls begin FIRST, then issues its first
+// activation prefetches, does its LDS-only set-up and calls finish just before its first barrier: memory operations
+// retire in order, so finish waits for the image alone (vmcnt(N), N = the activation loads issued behind it) and the
+// kernel's start costs one memory round trip.  As a loop of load -> wait -> ds_write in front of the first prefetch it
+// cost three dependent round trips and a fourth for the prefetch.
+template <typename T, int ELEMS> struct LdsImage {
+  static_assert(ELEMS * sizeof(T) % 16 == 0, "whole 16-byte chunks");
+  static constexpr int CHUNKS = ELEMS * (int)sizeof(T) / 16, ITERS = (CHUNKS + 255) / 256;
+  f32x4 v[ITERS];
+};
+template <typename T, int ELEMS>
+__device__ __forceinline__ void lds_image_begin(LdsImage<T, ELEMS>& im, const T* __restrict__ src) {
+  const rsrc_t r = make_rsrc(src, (uint32_t)(ELEMS * sizeof(T)));
+#pragma unroll
+  for (int k = 0; k < LdsImage<T, ELEMS>::ITERS; ++k) {
+    const int i = threadIdx.x + 256 * k;
+    im.v[k] = buf_load16(r, i < LdsImage<T, ELEMS>::CHUNKS ? (uint32_t)i * 16u : BUF_OOB);
+  }
+}
+template <typename T, int ELEMS>
+__device__ __forceinline__ void lds_image_finish(const LdsImage<T, ELEMS>& im, T* __restrict__ dst) {
+#pragma unroll
+  for (int k = 0; k < LdsImage<T, ELEMS>::ITERS; ++k) {
+    const int i = threadIdx.x + 256 * k;
+    if (i < LdsImage<T, ELEMS>::CHUNKS) ((f32x4*)dst)[i] = im.v[k];
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------- work plans
