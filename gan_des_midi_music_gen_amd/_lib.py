@@ -141,6 +141,9 @@ SIGNATURES = {
     "gdm_synth_frames": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "gdm_synth_pcm": (_I, [_P, _I, _P, _P, _P, _L, _L, _P, _P]),
     "gdm_synth_windows": (_I, [_P, _P, _L, _P, _I, _P, _P, _I, _L, _L, _P, _P, _P, _P]),
+    "gdm_s2w_prologue": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gdm_des_log_to_notes_pc": (_I, [_P, _P, _P, _P, _P, _L, _P, _P, _I, _I, _L, _L, _L, _P, _I, _P, _P, _P, _P]),
+    "gdm_synth_windows_gm": (_I, [_P, _P, _L, _P, _I, _P, _P, _I, _L, _L, _P, _P, _P, _P, _P]),
     "gdm_maxpool2_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "gdm_maxpool2_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
 }

@@ -192,9 +192,10 @@ extern "C" int gdm_des_run_batch_host(const double* adj, int B, int dim, const d
   GDM_REQUIRE(adj && loc && scale && queue_cap && seed && number_of_customers && mt_key && mt_pos && has_gauss &&
                   cached_gauss && rec_ptr && n_records && stop_reason,
               "gdm_des_run_batch_host: null pointer");
-  GDM_REQUIRE(B >= 1 && dim >= 1 && dim <= GDM_DES_BATCH_MAX_DIM && max_queue_cap >= 1 &&
+  // the host tables are heap vectors sized by dim (HostSim): only the kernel is bound to GDM_DES_BATCH_MAX_DIM
+  GDM_REQUIRE(B >= 1 && dim >= 1 && dim <= GDM_DES_BATCH_HOST_MAX_DIM && max_queue_cap >= 1 &&
                   max_queue_cap <= GDM_DES_BATCH_MAX_QUEUE_CAP,
-              "gdm_des_run_batch_host: B >= 1, 1 <= dim <= %d, 1 <= max_queue_cap <= %d", GDM_DES_BATCH_MAX_DIM,
+              "gdm_des_run_batch_host: B >= 1, 1 <= dim <= %d, 1 <= max_queue_cap <= %d", GDM_DES_BATCH_HOST_MAX_DIM,
               GDM_DES_BATCH_MAX_QUEUE_CAP);
   GDM_REQUIRE(max_events >= 1 && max_events <= GDM_DES_BATCH_MAX_EVENTS && max_records >= 0,
               "gdm_des_run_batch_host: max_events must be in 1..%lld and max_records >= 0",

@@ -20,6 +20,9 @@
 // launch.  Its note rows carry sample times and ascend in s_on, so a workgroup never scans the clip: two binary searches
 // bound the rows that can sound in its 2048 samples, and it walks them in tiles of 1024 rows, each compacted into a
 // fixed 16 KB list and added to the same eight register sums.  No cap on notes or on simultaneous voices.
+//
+// gdm_synth_windows_gm (the end of this file) is its sibling with a timbre per General MIDI family: a fifth column
+// holds the program, f = (program & 127) >> 3 picks one of 16 wave tables and one of 16 (attack, release) pairs.
 #include "gdm_common.h"
 #include "buffer_ops.h"
 
@@ -315,5 +318,164 @@ extern "C" int gdm_synth_windows(const int64_t* notes, const int64_t* off_max, i
                      (hipStream_t)stream, notes, off_max, n_total, note_ptr, F, win_clip, win_start, win_len, out_stride,
                      wave, inc, out);
   GDM_LAUNCH_OK("gdm_synth_windows");
+  return GDM_OK;
+}
+
+// ---- gdm_synth_windows_gm: the windows kernel with 16 timbres ------------------------------------------------------------
+// Same windows, tiles and searches as synth_windows_kernel.  What differs: rows of five columns; the family's wave table
+// and envelope per voice; `end_max` (the running maximum of s_off + R_row) where off_max stands, because the release now
+// varies per row.  All 16 tables (64 KB) and the envelopes are staged in LDS: the inner loop reads one table entry per
+// voice and sample at a data-dependent index -- per-lane LDS reads, where a global load would touch a cache line per
+// lane.  81 KB of LDS per workgroup: one workgroup of four waves per CU half, which the eight sums per thread keep busy.
+namespace {
+
+constexpr int kFam = GDM_SYNTH_GM_FAMILIES;
+constexpr int kEnvMax = GDM_SYNTH_GM_ENV_MAX;
+constexpr size_t kGmWaveBytes = (size_t)kFam * GDM_SYNTH_WAVE * sizeof(int16_t);
+constexpr size_t kGmLdsBytes = kGmWaveBytes + (size_t)kTile * sizeof(int4) + 2 * kFam * sizeof(int) + 16;
+static_assert(kEnvMax == kA * kR, "the default envelopes keep A_f * R_f at the one voice's A * R");
+
+// A voice that sounds somewhere in [lo, lo + 2^13):
+//   x = phase at sample lo (mod 2^32),  y = inc[p],  z = (s_on - lo clamped to [-2^21, 2^13]) << 4 | family,
+//   w = (s_off - lo clamped to [-2^21, 2^20]) + 2^21  |  v << 24
+// As in voice_entry the clamps change nothing inside the range (A_f, R_f <= 2^21) and are written as comparisons.
+__device__ __forceinline__ int4 voice_entry_gm(int64_t s_on, int64_t s_off, int64_t pitch, int64_t velocity, int family,
+                                               int64_t lo, const uint32_t* __restrict__ inc) {
+  const uint32_t step = inc[pitch & 127];
+  const uint32_t vel = (uint32_t)(velocity & 127);
+  const int64_t on_rel = s_on < lo - kEnvMax ? (int64_t)-kEnvMax : (s_on > lo + (1 << 13) ? (int64_t)1 << 13 : s_on - lo);
+  const int64_t off_rel =
+      s_off < lo - kEnvMax ? (int64_t)-kEnvMax : (s_off > lo + (1 << 20) ? (int64_t)1 << 20 : s_off - lo);
+  int4 e;
+  e.x = (int)(step * (uint32_t)((uint64_t)lo - (uint64_t)s_on));
+  e.y = (int)step;
+  e.z = (int)(on_rel * 16) | family;
+  e.w = (int)((uint32_t)(off_rel + kEnvMax) | (vel << 24));
+  return e;
+}
+
+__device__ __forceinline__ void add_voices_gm(const int4* s_voice, int n, const int16_t* s_waves, const int* s_env,
+                                              const int (&t)[kPer], int (&acc)[kPer]) {
+  for (int k = 0; k < n; ++k) {
+    const int4 v = s_voice[k];
+    const int family = v.z & (kFam - 1), on = v.z >> 4;
+    const int A = s_env[2 * family], R = s_env[2 * family + 1];
+    const int off = (int)((uint32_t)v.w & 0xFFFFFFu) - kEnvMax, vel = (int)((uint32_t)v.w >> 24);
+    const int16_t* wave = s_waves + family * GDM_SYNTH_WAVE;
+#pragma unroll
+    for (int e = 0; e < kPer; ++e) {
+      const int d = t[e] - on, past = t[e] - off;                   // samples since note-on / since note-off
+      if (d >= 0 && past < R) {
+        const uint32_t phase = (uint32_t)v.x + (uint32_t)v.y * (uint32_t)t[e];
+        const int e_att = min(d + 1, A);
+        const int e_rel = past < 0 ? R : R - past;
+        // |wave * vel| < 2^22 and e_att * e_rel <= 2^42; with A_f * R_f = 2^21 the product stays below 2^43.  Unsigned
+        // arithmetic, so that tables beyond that wrap instead of overflowing.
+        const uint64_t p = (uint64_t)(int64_t)((int)wave[phase >> 21] * vel) * (uint64_t)((int64_t)e_att * e_rel);
+        acc[e] += (int)((int64_t)p >> kShift);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void synth_windows_gm_kernel(
+    const int64_t* __restrict__ notes, const int64_t* __restrict__ end_max, int64_t n_total,
+    const int64_t* __restrict__ note_ptr, int F, const int32_t* __restrict__ win_clip,
+    const int64_t* __restrict__ win_start, int64_t win_len, int64_t out_stride, const int16_t* __restrict__ waves,
+    const int32_t* __restrict__ env, const uint32_t* __restrict__ inc, int16_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  int16_t* s_waves = reinterpret_cast<int16_t*>(s_raw);
+  int4* s_voice = reinterpret_cast<int4*>(s_raw + kGmWaveBytes);
+  int* s_env = reinterpret_cast<int*>(s_raw + kGmWaveBytes + (size_t)kTile * sizeof(int4));
+  int* s_count = s_env + 2 * kFam;
+  const int tid = threadIdx.x, w = blockIdx.y;
+  const int clip = min(max(win_clip[w], 0), F - 1);
+  const int64_t r0 = min(max(note_ptr[clip], (int64_t)0), n_total);
+  const int64_t r1 = min(max(note_ptr[clip + 1], r0), n_total);
+  const int64_t c0 = (int64_t)blockIdx.x * kChunk;                   // first output sample of this workgroup
+  const int64_t lo = min(max(win_start[w], -kTimeMax), kTimeMax) + c0, hi = lo + kChunk - 1;
+  int64_t a = r0, b = r1;                                            // end: the first row with s_on > hi
+  while (a < b) {
+    const int64_t m = a + ((b - a) >> 1);
+    if (notes[5 * m] > hi) b = m; else a = m + 1;
+  }
+  const int64_t end = a;
+  a = r0, b = end;                                                   // begin: the first row with end_max > lo
+  while (a < b) {
+    const int64_t m = a + ((b - a) >> 1);
+    if (end_max[m] > lo) b = m; else a = m + 1;
+  }
+  const int64_t begin = a;
+  if (tid == 0) *s_count = 0;
+  if (tid < 2 * kFam) s_env[tid] = min(max(env[tid], 1), kEnvMax);
+  if (begin < end) {                                                 // uniform: a silent chunk reads no table
+    const int4* src = reinterpret_cast<const int4*>(waves);
+    int4* dst = reinterpret_cast<int4*>(s_waves);
+    for (int i = tid; i < (int)(kGmWaveBytes / sizeof(int4)); i += kThreads) dst[i] = src[i];
+  }
+  int t[kPer], acc[kPer];
+#pragma unroll
+  for (int e = 0; e < kPer; ++e) {
+    t[e] = tid * kPer + e;
+    acc[e] = 0;
+  }
+  __syncthreads();
+  for (int64_t base = begin; base < end; base += kTile) {            // uniform over the workgroup
+    const int64_t stop = min(base + kTile, end);
+    for (int64_t k = base + tid; k < stop; k += kThreads) {
+      const int64_t s_on = notes[5 * k + 0], s_off = notes[5 * k + 1];
+      const int family = (int)((notes[5 * k + 4] & 127) >> 3);
+      if (s_on > hi || s_off <= lo - s_env[2 * family + 1]) continue;
+      s_voice[atomicAdd(s_count, 1)] = voice_entry_gm(s_on, s_off, notes[5 * k + 2], notes[5 * k + 3], family, lo, inc);
+    }
+    __syncthreads();
+    add_voices_gm(s_voice, *s_count, s_waves, s_env, t, acc);        // <= kTile entries: the list cannot overflow
+    __syncthreads();
+    if (tid == 0) *s_count = 0;                                      // ordered before the next tile's adds by its barrier
+    __syncthreads();
+  }
+  const int64_t i0 = c0 + tid * kPer;
+  int16_t* o = out + (int64_t)w * out_stride;
+  if (i0 + kPer <= win_len) {
+    short8 v;
+#pragma unroll
+    for (int e = 0; e < kPer; ++e) v[e] = (short)clamp16(acc[e]);
+    *reinterpret_cast<short8*>(o + i0) = v;
+  } else {
+#pragma unroll
+    for (int e = 0; e < kPer; ++e)
+      if (i0 + e < win_len) o[i0 + e] = (int16_t)clamp16(acc[e]);
+  }
+}
+
+}  // namespace
+
+extern "C" int gdm_synth_windows_gm(const int64_t* notes, const int64_t* end_max, int64_t n_total,
+                                    const int64_t* note_ptr, int F, const int32_t* win_clip, const int64_t* win_start,
+                                    int W, int64_t win_len, int64_t out_stride, const int16_t* waves, const int32_t* env,
+                                    const uint32_t* inc, int16_t* out, void* stream) {
+  GDM_REQUIRE(n_total >= 0, "gdm_synth_windows_gm: n_total = %lld", (long long)n_total);
+  GDM_REQUIRE((notes && end_max) || n_total == 0, "gdm_synth_windows_gm: null pointer (notes / end_max of %lld rows)",
+              (long long)n_total);
+  GDM_REQUIRE(note_ptr && win_clip && win_start && waves && env && inc && out, "gdm_synth_windows_gm: null pointer");
+  GDM_REQUIRE(((uintptr_t)notes & 7) == 0 && ((uintptr_t)end_max & 7) == 0 && ((uintptr_t)note_ptr & 7) == 0 &&
+                  ((uintptr_t)win_start & 7) == 0 && ((uintptr_t)win_clip & 3) == 0 && ((uintptr_t)env & 3) == 0 &&
+                  ((uintptr_t)inc & 3) == 0,
+              "gdm_synth_windows_gm: notes / end_max / note_ptr / win_clip / win_start / env / inc must be aligned to "
+              "their elements");
+  GDM_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)waves & 15) == 0,
+              "gdm_synth_windows_gm: out and waves must be 16-byte aligned (16-byte stores and loads)");
+  GDM_REQUIRE(F >= 1, "gdm_synth_windows_gm: F = %d clips (at least 1)", F);
+  GDM_REQUIRE(W >= 1 && W <= 65535, "gdm_synth_windows_gm: W = %d windows (1 .. 65535)", W);
+  GDM_REQUIRE(win_len >= 1 && win_len <= ((int64_t)1 << 30), "gdm_synth_windows_gm: win_len = %lld (1 .. 2^30 samples)",
+              (long long)win_len);
+  GDM_REQUIRE(out_stride >= win_len && out_stride % 8 == 0,
+              "gdm_synth_windows_gm: out_stride = %lld (at least win_len = %lld and a multiple of 8: 16-byte stores)",
+              (long long)out_stride, (long long)win_len);
+  allow_lds(synth_windows_gm_kernel, kGmLdsBytes);
+  hipLaunchKernelGGL(synth_windows_gm_kernel, dim3((unsigned)((win_len + kChunk - 1) / kChunk), W), dim3(kThreads),
+                     kGmLdsBytes, (hipStream_t)stream, notes, end_max, n_total, note_ptr, F, win_clip, win_start, win_len,
+                     out_stride, waves, env, inc, out);
+  GDM_LAUNCH_OK("gdm_synth_windows_gm");
   return GDM_OK;
 }

@@ -627,7 +627,7 @@ MAX_CLIP_NOTES = 1 << 18            # the kernel's int32 voice sum is proven bel
 _WAV_CHUNK = 1 << 22                # samples midi_to_wav renders per launch (8 MB of PCM)
 
 
-def midi_notes(midi_input, *, pedal=True):
+def midi_notes(midi_input, *, pedal=True, programs=False):
     """A Standard MIDI File (path, bytes or MidiData) -> (notes (n, 4) int64, clip_len): rows (s_on, s_off, pitch,
     velocity) IN SAMPLES at 44 100 Hz, sorted by s_on (stable), as ``ops.synth_windows`` takes them.  The rules are
     defined here and in include/gdm.h, as the synth is:
@@ -645,7 +645,9 @@ def midi_notes(midi_input, *, pedal=True):
     pitch), and the file's last message.  ``pedal=False`` ignores controller 64.
     All channels sound the same voice, program changes are ignored, pitch and velocity are kept as stored (0..127).
     clip_len = max(s_off) + the synth's release (8192), or 5 * 44100 for a file without notes (the bridge's blank clip).
-    ValueError for a clip beyond 2^40 samples and for 2^18 notes or more."""
+    ValueError for a clip beyond 2^40 samples and for 2^18 notes or more.
+    ``programs=True`` adds a fifth column: the program in force on the note's channel at its note_on (0 before the
+    channel's first program_change) -- the rows ``ops.synth_windows_gm`` takes; everything else is unchanged."""
     md = midi_input if isinstance(midi_input, MidiData) else read_midi(midi_input)
     if md.format == 2:
         raise TypeError("can't merge tracks in type 2 (asynchronous) file")
@@ -661,6 +663,7 @@ def midi_notes(midi_input, *, pedal=True):
     open_rows = collections.defaultdict(collections.deque)      # (channel, pitch) -> rows waiting for their close
     held = collections.defaultdict(list)                 # channel -> rows whose close the pedal defers
     down = [False] * 16
+    program = [0] * 16
     u = prev = s = 0
     tempo = DEFAULT_TEMPO
     for tk, k, a, b, st in zip(ticks, kinds, av, bv, sv):
@@ -678,7 +681,7 @@ def midi_notes(midi_input, *, pedal=True):
                     if r[2] == a:
                         r[1] = s
                 held[ch] = [r for r in held[ch] if r[2] != a]
-            rows.append([s, None, a, b])
+            rows.append([s, None, a, b, program[ch]] if programs else [s, None, a, b])
             open_rows[ch, a].append(rows[-1])
         elif k in (_K_ON, _K_OFF):
             ch = st & 15
@@ -688,6 +691,8 @@ def midi_notes(midi_input, *, pedal=True):
                     held[ch].append(r)
                 else:
                     r[1] = s
+        elif programs and st >> 4 == 0xC:
+            program[st & 15] = a
         elif pedal and st >> 4 == 0xB and a == 64:
             ch = st & 15
             down[ch] = b >= 64
@@ -701,7 +706,7 @@ def midi_notes(midi_input, *, pedal=True):
     if len(rows) >= MAX_CLIP_NOTES:
         raise ValueError(f"{len(rows)} notes in one file (fewer than 2^18 keep the synth's int32 voice sum exact)")
     if not rows:
-        return np.zeros((0, 4), dtype=np.int64), 5 * ops.SYNTH_RATE
+        return np.zeros((0, 5 if programs else 4), dtype=np.int64), 5 * ops.SYNTH_RATE
     clip_len = max(r[1] for r in rows) + ops.SYNTH_RELEASE
     if clip_len > MAX_CLIP_SAMPLES:
         raise ValueError(f"a clip of {clip_len} samples (2^40 at most)")

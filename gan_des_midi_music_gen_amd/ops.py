@@ -1238,8 +1238,10 @@ def des_log_to_roll(value, event_id, node, kind, rec_ptr, tails, instruments, no
 # ---- model 1's DES bridge: log -> notes -> integer synth (GAN_DES/sim_log_process_music.py:65-133,159-185;
 # GAN_DES/matrix_sim_process.py:112-129) ------------------------------------------------------------------------------
 DES_NOTES_MAX = 5000            # GDM_DES_NOTES_MAX
-DES_NOTES_ERRORS = {1: "a note for a node without note level", 2: "note outside 0..127"}       # the reference raises
+DES_NOTES_ERRORS = {1: "a note for a node without note level", 2: "note outside 0..127",
+                    4: "program outside 0..127"}                                                # the reference raises
 DES_NOTES_ELONG = 3             # the clip would pass 2^40 samples: left blank, nothing is raised
+DES_NOTES_EPROGRAM = 4          # des_log_to_notes_pc only
 SYNTH_ATTACK, SYNTH_RELEASE, SYNTH_SHIFT, SYNTH_WAVE, SYNTH_FRAMES, SYNTH_NFFT = 256, 8192, 30, 2048, 216, 2048
 SYNTH_RATE = 44100
 _synth_tables = {}
@@ -1371,6 +1373,157 @@ def synth_windows(notes, off_max, note_ptr, win_clip, win_start, win_len, *, tab
             raise GdmError(f"synth_windows: out must be a contiguous ({w}, out_stride) int16 tensor")
     _call("gdm_synth_windows", _p(notes), _p(off_max), n, _p(note_ptr), note_ptr.numel() - 1, _p(win_clip),
           _p(win_start), w, win_len, out.shape[1], _p(wave), _p(inc), _p(out), _stream())
+    return out
+
+
+# ---- the stand-alone demo (SIMULATOR/simulation_to_wav.py): prologue, log -> notes with programs, synth with timbres ----
+S2W_MIN_SIZE, S2W_MAX_SIZE = 6, 256          # GDM_S2W_MIN_SIZE, GDM_S2W_MAX_SIZE
+S2W_NO_INSTRUMENT = -2 ** 31
+_S2W_FIELDS = (("src", torch.uint8, "d"), ("instruments", torch.int32, "d"), ("note_levels", torch.int32, "d"),
+               ("loc", torch.float64, "d"), ("scale", torch.float64, "d"), ("queue_cap", torch.int32, "d"),
+               ("adj", torch.float64, "dd"), ("status", torch.int32, ""))
+
+
+def s2w_prologue(m, instrument_override=None, out=None):
+    """``gdm_s2w_prologue`` (include/gdm.h): m (B, S, S) float64 device tensor, read only; instrument_override (B) i32
+    or None (S2W_NO_INSTRUMENT = the matrix's own).  Returns a dict of device tensors: src (B,dim) u8, instruments,
+    note_levels (B,dim) i32, loc, scale (B,dim) f64, queue_cap (B,dim) i32, adj (B,dim,dim) f64, status (B) i32 (1: a
+    row sum is zero or not finite; the sample then has scale -1).  ``out``: such a dict to write into."""
+    _need_gpu(m, instrument_override)
+    if m.dtype != torch.float64 or m.dim() != 3 or m.shape[1] != m.shape[2] or not m.is_contiguous() or m.shape[0] < 1:
+        raise GdmError("s2w_prologue: m must be a contiguous (B, S, S) float64 tensor with B >= 1")
+    b, size = m.shape[0], m.shape[1]
+    if not S2W_MIN_SIZE <= size <= S2W_MAX_SIZE:
+        raise GdmError(f"s2w_prologue: size {size} ({S2W_MIN_SIZE} .. {S2W_MAX_SIZE})")
+    dim = size - 5
+    if instrument_override is not None and (instrument_override.dtype != torch.int32 or
+                                            instrument_override.shape != (b,) or
+                                            not instrument_override.is_contiguous()):
+        raise GdmError("s2w_prologue: instrument_override must be a contiguous (B,) int32 tensor")
+    shapes = {"d": (b, dim), "dd": (b, dim, dim), "": (b,)}
+    if out is None:
+        out = {name: torch.empty(shapes[kind], dtype=dt, device=m.device) for name, dt, kind in _S2W_FIELDS}
+    for name, dt, kind in _S2W_FIELDS:
+        t = out[name]
+        _need_gpu(t)
+        if tuple(t.shape) != shapes[kind] or t.dtype != dt or not t.is_contiguous():
+            raise GdmError(f"s2w_prologue: out[{name!r}] must be a contiguous {dt} tensor of shape {shapes[kind]}")
+    _call("gdm_s2w_prologue", _p(m), b, size, _p(instrument_override),
+          *(_p(out[name]) for name, _dt, _k in _S2W_FIELDS), _stream())
+    return out
+
+
+def tick_rule(tempo=500000, ticks_per_beat=480):
+    """(mul, div) of sample(tick) = tick * mul // div at 44 100 Hz: the rule ``datasets.midi_notes`` applies to a file
+    with one tempo, ``tick * tempo * 441 // (ticks_per_beat * 10000)``, in lowest terms."""
+    import math
+    num, den = int(tempo) * 441, int(ticks_per_beat) * 10000
+    g = math.gcd(num, den)
+    return num // g, den // g
+
+
+SYNTH_GM_FAMILIES = 16          # GDM_SYNTH_GM_FAMILIES
+SYNTH_GM_ENV_MAX = 1 << 21      # GDM_SYNTH_GM_ENV_MAX
+# General MIDI family f = program >> 3: (name, harmonic weights w1..w4 in sixteenths, a_f); A_f = 2^a_f, R_f = 2^(21 - a_f)
+SYNTH_GM_FAMILY_TABLE = (
+    ("piano", (16, 8, 4, 2), 8), ("chromatic percussion", (16, 0, 6, 0), 6), ("organ", (16, 12, 8, 4), 10),
+    ("guitar", (16, 10, 6, 3), 7), ("bass", (16, 5, 0, 0), 8), ("strings", (16, 8, 5, 4), 12),
+    ("ensemble", (16, 6, 4, 2), 12), ("brass", (16, 12, 10, 6), 10), ("reed", (16, 2, 10, 1), 9),
+    ("pipe", (16, 2, 0, 0), 10), ("synth lead", (16, 8, 6, 4), 6), ("synth pad", (16, 4, 0, 2), 13),
+    ("synth effects", (16, 0, 0, 8), 11), ("ethnic", (16, 9, 2, 6), 7), ("percussive", (16, 3, 9, 1), 5),
+    ("sound effects", (8, 16, 4, 12), 9))
+_synth_gm_tables = {}
+
+
+def synth_gm_tables(device):
+    """(waves int16 (16, 2048), env int32 (16, 2) = (A_f, R_f), inc int32[128]) of ``synth_windows_gm``: built once in
+    float64 (include/gdm.h: wave_f = rint(32767 s_f / max |s_f|), s_f(i) = sum_k w_fk sin(2 pi k i / 2048)), cached per
+    device."""
+    key = str(device)
+    if key not in _synth_gm_tables:
+        import numpy as np
+        i = np.arange(SYNTH_WAVE, dtype=np.float64)
+        waves, env = [], []
+        for _name, weights, a in SYNTH_GM_FAMILY_TABLE:
+            s = np.zeros(SYNTH_WAVE, dtype=np.float64)
+            for k, w in enumerate(weights, start=1):
+                s = s + float(w) * np.sin(2.0 * np.pi * k * i / SYNTH_WAVE)
+            waves.append(np.rint(32767.0 * s / np.abs(s).max()).astype(np.int16))
+            env.append((1 << a, 1 << (21 - a)))
+        _synth_gm_tables[key] = (torch.from_numpy(np.stack(waves)).contiguous().to(device),
+                                 torch.tensor(env, dtype=torch.int32).to(device), synth_tables(device)[1])
+    return _synth_gm_tables[key]
+
+
+def des_log_to_notes_pc(value, event_id, node, kind, rec_ptr, instruments, note_levels, *, tick_mul_div=None, tail=None,
+                        check_rec_ptr=True):
+    """``des_log_to_notes`` for the demo's MidiGenerator, whose program_change lines are live (gdm_des_log_to_notes_pc,
+    include/gdm.h): -> (notes (B,5000,5) i64 of (on_tick, off_tick, pitch, velocity, program), n_notes (B) i32, clip_len
+    (B) i64, status (B) i32).  tick_mul_div: (mul, div) of sample(tick) (default ``tick_rule()``: tempo 500 000, 480
+    ticks per beat); tail: samples a clip lasts beyond its last note_off (default: the longest release of
+    ``synth_gm_tables``)."""
+    _need_gpu(value, event_id, node, kind, rec_ptr, instruments, note_levels)
+    n = value.numel()
+    b = rec_ptr.numel() - 1
+    for t, dt in ((value, torch.float64), (event_id, torch.int64), (node, torch.int32), (kind, torch.int32)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise GdmError("des_log_to_notes_pc: records must be contiguous f64 / i64 / i32 / i32 arrays of one length")
+    if rec_ptr.dtype != torch.int64 or b < 1 or not rec_ptr.is_contiguous():
+        raise GdmError("des_log_to_notes_pc: rec_ptr must be a contiguous int64 tensor of B + 1 offsets")
+    for t, what in ((note_levels, "note_levels"), (instruments, "instruments")):
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != b or not t.is_contiguous() or \
+                t.shape != note_levels.shape:
+            raise GdmError(f"des_log_to_notes_pc: {what} must be contiguous (B, dim) int32")
+    if check_rec_ptr and bool(((rec_ptr[1:] < rec_ptr[:-1]).any() | (rec_ptr[0] < 0) | (rec_ptr[-1] > n)).item()):
+        raise GdmError(f"des_log_to_notes_pc: rec_ptr must ascend within [0, {n}] (the number of records)")
+    mul, div = tick_rule() if tick_mul_div is None else (int(tick_mul_div[0]), int(tick_mul_div[1]))
+    if tail is None:
+        tail = max(1 << (21 - a) for _n, _w, a in SYNTH_GM_FAMILY_TABLE)
+    dev = value.device
+    notes = torch.zeros((b, DES_NOTES_MAX, 5), dtype=torch.int64, device=dev)
+    n_notes = torch.empty(b, dtype=torch.int32, device=dev)
+    clip_len = torch.empty(b, dtype=torch.int64, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    _call("gdm_des_log_to_notes_pc", _p(value), _p(event_id), _p(node), _p(kind), _p(rec_ptr), n, _p(instruments),
+          _p(note_levels), note_levels.shape[1], b, mul, div, int(tail), _p(notes), DES_NOTES_MAX, _p(n_notes),
+          _p(clip_len), _p(status), _stream())
+    return notes, n_notes, clip_len, status
+
+
+def synth_windows_gm(notes, end_max, note_ptr, win_clip, win_start, win_len, *, tables=None, out=None):
+    """``synth_windows`` with a timbre per General MIDI family (gdm_synth_windows_gm, include/gdm.h): notes (n, 5) int64
+    rows (s_on, s_off, pitch, velocity, program) in SAMPLES, ascending in s_on within a clip; end_max (n,) int64 the
+    running maximum of s_off + R_family within each clip; the rest as ``synth_windows``.  tables: (waves int16
+    (16, 2048), env int32 (16, 2), inc int32[128]); default ``synth_gm_tables``."""
+    _need_gpu(notes, end_max, note_ptr, win_clip, win_start)
+    n = notes.shape[0] if notes.dim() == 2 else -1
+    if notes.dtype != torch.int64 or notes.dim() != 2 or notes.shape[1] != 5 or not notes.is_contiguous():
+        raise GdmError("synth_windows_gm: notes must be a contiguous (n, 5) int64 tensor")
+    if end_max.dtype != torch.int64 or end_max.shape != (n,) or not end_max.is_contiguous():
+        raise GdmError("synth_windows_gm: end_max must be a contiguous (n,) int64 tensor")
+    if note_ptr.dtype != torch.int64 or note_ptr.dim() != 1 or note_ptr.numel() < 2 or not note_ptr.is_contiguous():
+        raise GdmError("synth_windows_gm: note_ptr must be a contiguous int64 tensor of F + 1 offsets")
+    w = win_clip.numel()
+    if win_clip.dtype != torch.int32 or win_clip.dim() != 1 or not win_clip.is_contiguous() or \
+            win_start.dtype != torch.int64 or win_start.shape != (w,) or not win_start.is_contiguous():
+        raise GdmError("synth_windows_gm: win_clip (W,) int32 and win_start (W,) int64 must be contiguous and of one "
+                       "length")
+    waves, env, inc = synth_gm_tables(notes.device) if tables is None else tables
+    _need_gpu(waves, env, inc)
+    if waves.dtype != torch.int16 or waves.shape != (SYNTH_GM_FAMILIES, SYNTH_WAVE) or env.dtype != torch.int32 or \
+            env.shape != (SYNTH_GM_FAMILIES, 2) or inc.dtype != torch.int32 or inc.shape != (128,) or \
+            not (waves.is_contiguous() and env.is_contiguous() and inc.is_contiguous()):
+        raise GdmError(f"synth_windows_gm: tables must be (waves int16 (16, {SYNTH_WAVE}), env int32 (16, 2), inc "
+                       "int32[128] holding uint32 bits)")
+    win_len = int(win_len)
+    if out is None:
+        out = torch.empty((w, (max(win_len, 0) + 7) // 8 * 8), dtype=torch.int16, device=notes.device)
+    else:
+        _need_gpu(out)
+        if out.dtype != torch.int16 or out.dim() != 2 or out.shape[0] != w or not out.is_contiguous():
+            raise GdmError(f"synth_windows_gm: out must be a contiguous ({w}, out_stride) int16 tensor")
+    _call("gdm_synth_windows_gm", _p(notes), _p(end_max), n, _p(note_ptr), note_ptr.numel() - 1, _p(win_clip),
+          _p(win_start), w, win_len, out.shape[1], _p(waves), _p(env), _p(inc), _p(out), _stream())
     return out
 
 

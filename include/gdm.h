@@ -423,7 +423,7 @@ int gdm_des_run(const double* adj, int dim, const double* loc, const double* sca
  * (n_records_cap entries each) and rec_ptr (B + 1); n_records (B) i64, stop_reason (B) i32 = GDM_DES_STOP_*.  A sample
  * that errors (reason 3: bad spec, no destination, a customer routed to a source, a capacity overrun) has an empty log
  * and leaves its neighbours alone.
- * gdm_des_run_batch_host: host arrays; math 0 = libm's log / sqrt (numpy's bits, as gdm_des_run), 1 = the portable
+ * gdm_des_run_batch_host: host arrays, dim <= GDM_DES_BATCH_HOST_MAX_DIM; math 0 = libm's log / sqrt (numpy's bits, as gdm_des_run), 1 = the portable
  *   log / sqrt of des_sim.h.  GDM_EWORKSPACE when n_records_cap is too small (rec_ptr[B] then holds the count needed).
  * gdm_des_run_batch: device arrays, always portable math: bit-identical to the host entry with math = 1.  One wave per
  *   sample + a one-workgroup pack step.  max_records >= 1 is required and n_records_cap >= B * max_records (the bound
@@ -441,6 +441,7 @@ int gdm_des_run(const double* adj, int dim, const double* loc, const double* sca
 #define GDM_DES_STOP_RECORDS 4
 #define GDM_DES_STOP_BUDGET 5
 #define GDM_DES_BATCH_MAX_DIM 128
+#define GDM_DES_BATCH_HOST_MAX_DIM 4096 /* gdm_des_run_batch_host only (gdm_des_run's bound): its tables are on the heap */
 #define GDM_DES_BATCH_MAX_QUEUE_CAP 65536
 #define GDM_DES_BATCH_MAX_EVENTS ((int64_t)1 << 40)
 int gdm_des_run_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale,
@@ -710,6 +711,7 @@ int gdm_pcm_stft_frames(const void* pcm, int fmt, int channels, int mix, int64_t
 #define GDM_DES_NOTES_ENODE 1  /* a note for a node without note level (KeyError upstream) */
 #define GDM_DES_NOTES_EPITCH 2 /* note outside 0..127 (mido refuses the message) */
 #define GDM_DES_NOTES_ELONG 3  /* the clip would pass 2^40 samples: left blank, nothing is raised */
+#define GDM_DES_NOTES_EPROGRAM 4 /* gdm_des_log_to_notes_pc: program outside 0..127 (mido refuses the message) */
 #define GDM_SYNTH_ATTACK 256
 #define GDM_SYNTH_RELEASE 8192
 #define GDM_SYNTH_SHIFT 30
@@ -728,6 +730,62 @@ int gdm_synth_pcm(const int64_t* notes, int notes_cap, const int32_t* n_notes, c
 int gdm_synth_windows(const int64_t* notes, const int64_t* off_max, int64_t n_total, const int64_t* note_ptr, int F,
                       const int32_t* win_clip, const int64_t* win_start, int W, int64_t win_len, int64_t out_stride,
                       const int16_t* wave, const uint32_t* inc, int16_t* out, void* stream);
+
+/* ---- the stand-alone demo: random (or given) matrix -> DES -> MIDI -> WAV (SIMULATOR/simulation_to_wav.py) ------------
+ * gdm_s2w_prologue (:25-71): m (B, S, S) float64 device matrices, read and not modified; dim = S - 5 nodes, rows dim ..
+ *   dim + 4 are the parameter rows.  One launch, one workgroup per sample.  Outputs, bit for bit what the reference's
+ *   numpy float64 code computes: src (B,dim) u8 = m[dim][i] > 0.75 (false for a NaN); instruments, note_levels (B,dim)
+ *   i32 = (int)(m[dim+1][i] * 127), (int)(m[dim+2][i] * 127) (truncation; no abs and no 126 as in gdm_des_scan);
+ *   instrument_override (B) i32 or NULL puts one program on every node of a sample, INT32_MIN = none, as in
+ *   gdm_des_draws; loc, scale (B,dim) f64 = 10 r3, 5 r4 for a source and 3 r3, 2 r4 for a server (r3, r4 = rows dim+3,
+ *   dim+4); queue_cap (B,dim) i32 = 127; adj (B,dim,dim) f64: EVERY column c < S with m[dim][c] > 0.75 is zeroed (a
+ *   given matrix may mark parameter columns), the diagonal is zeroed, each row i < dim is divided (IEEE) by Python's
+ *   sum() of it -- the strictly sequential left-to-right float64 sum over all S entries, parameter columns included --,
+ *   then the diagonal is +1 for a source and -1 for a server and the first dim columns are kept.  Nothing is drawn and
+ *   no NaN is repaired: status (B) i32 = 1 when a row sum is zero or not finite (0 otherwise); such a sample has scale
+ *   -1 on every node -- gdm_des_run_batch ends it with GDM_DES_STOP_ERROR and no records -- and an adj of zeros around
+ *   its diagonal; its neighbours are untouched.  Checked before the launch: null pointers, GDM_S2W_MIN_SIZE <= S <=
+ *   GDM_S2W_MAX_SIZE, B >= 1, every array aligned to its elements.  No value read from device memory forms an address.
+ *
+ * gdm_des_log_to_notes_pc (:162-214, the demo's own MidiGenerator): gdm_des_log_to_notes -- same records, same reader,
+ *   same replay, one source -- for the copy whose program_change lines are live: the track receives program_change(on),
+ *   note_on(on), program_change(off), note_off(off), so on_tick = ticks + 2 on and off_tick = on_tick + 2 off, and a
+ *   note row has FIVE columns (on_tick, off_tick, pitch, velocity, program) with program = instruments[node]
+ *   (instruments (B,dim) i32).  A program outside 0..127 is GDM_DES_NOTES_EPROGRAM (tested before the pitch: the
+ *   program_change is built first).  The demo never calls generate_midi, so its file has no set_tempo; the tick ->
+ *   sample rule is therefore not fixed here but passed: sample(tick) = tick * tick_mul / tick_div (integers, rounded
+ *   down; 735 / 16 for the default tempo 500 000 at 480 ticks per beat -- the rule datasets.midi_notes applies to the
+ *   written file), clip_len = sample(last off_tick) + tail (0: no notes).  GDM_DES_NOTES_ELONG when sample + tail would
+ *   pass 2^40, tested against the doubled steps before they are added.  1 <= tick_mul, tick_div <= 2^20, 0 <= tail <=
+ *   2^30, every array aligned to its elements.
+ *
+ * gdm_synth_windows_gm: gdm_synth_windows with a timbre per General MIDI family.  Same windows, tiles, searches and
+ *   checks; note rows are (n_total, 5) i64 (s_on, s_off, pitch, velocity, program) and the family is f = (program & 127)
+ *   >> 3.  Tables from the caller: waves (16, 2048) i16, env (16, 2) i32 = (A_f, R_f), clamped on the device to 1 ..
+ *   2^21 each.  With the tables ops.synth_gm_tables builds, A_f * R_f = 2^21 = GDM_SYNTH_ATTACK * GDM_SYNTH_RELEASE
+ *   for every family, so the voice bound and the int32-sum argument above carry over.  A voice contributes at s in
+ *   [s_on, s_off + R_f):
+ *     phase = (uint32)(inc[p] * (s - s_on))            e_att = min(s - s_on + 1, A_f)
+ *     e_rel = s < s_off ? R_f : R_f - (s - s_off)      voice = ((int64)waves[f][phase >> 21] * v * e_att * e_rel) >> 30
+ *   end_max[k] = the running maximum of s_off + R_f(row) over the clip's rows up to k (the release varies per row; it
+ *   stands where off_max stands).  The 64 KB of wave tables and the 16 envelopes are staged in LDS by every workgroup:
+ *   the inner loop reads one table entry per voice and sample at a data-dependent index, which LDS serves per lane and
+ *   a global load would serve per cache line.  waves and out 16-byte aligned.                                         */
+#define GDM_S2W_MIN_SIZE 6
+#define GDM_S2W_MAX_SIZE 256
+#define GDM_SYNTH_GM_FAMILIES 16
+#define GDM_SYNTH_GM_ENV_MAX (1 << 21)
+int gdm_s2w_prologue(const double* m, int B, int S, const int32_t* instrument_override_or_null, uint8_t* src,
+                     int32_t* instruments, int32_t* note_levels, double* loc, double* scale, int32_t* queue_cap,
+                     double* adj, int32_t* status, void* stream);
+int gdm_des_log_to_notes_pc(const double* value, const int64_t* event_id, const int32_t* node, const int32_t* kind,
+                            const int64_t* rec_ptr, int64_t n_records, const int32_t* instruments,
+                            const int32_t* note_levels, int dim, int B, int64_t tick_mul, int64_t tick_div, int64_t tail,
+                            int64_t* notes, int notes_cap, int32_t* n_notes, int64_t* clip_len, int32_t* status,
+                            void* stream);
+int gdm_synth_windows_gm(const int64_t* notes, const int64_t* end_max, int64_t n_total, const int64_t* note_ptr, int F,
+                         const int32_t* win_clip, const int64_t* win_start, int W, int64_t win_len, int64_t out_stride,
+                         const int16_t* waves, const int32_t* env, const uint32_t* inc, int16_t* out, void* stream);
 
 #ifdef __cplusplus
 }
