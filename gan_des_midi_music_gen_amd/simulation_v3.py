@@ -18,7 +18,17 @@ Differences, on purpose:
     accepted and ignored);
   * only what the bridges construct is supported: 'normal' distributions, ``logging_mode='Music'``, probability routing
     (no 'queue' / 'branch' nodes, no animation, no metric history) -- anything else raises NotImplementedError;
-  * the log records are also kept as arrays (``sim.music_log``), so a caller need not go through the log file.
+  * the log records are also kept as arrays (``sim.music_log``), so a caller need not go through the log file;
+  * where the reference's run ends in an exception, ``Sim.run`` raises ValueError with the core's message, and a sample
+    of ``run_batch`` / ``run_batch_host`` ends with stop reason 3 ("error") and an empty log, its neighbours untouched
+    (tests/golden/des_corpus.npz records the reference's exception, tests/test_des_corpus.py pins this table):
+
+        case                                            reference                                   here
+        a customer is routed to a source node           KeyError (``self.servers[id]``, Sim.run)    ValueError / stop 3
+        a source has no child with a positive flow      KeyError (``self.servers[None]``, Sim.run)  ValueError / stop 3
+
+    In both cases the reference fails when it takes the event off the list, before the arrival is logged; the records
+    written up to that point stay in its log file, while ``Sim.run`` here returns nothing.
 
 ``run_batch`` / ``run_batch_host`` simulate B specs of one size at once, every sample FROM ITS OWN snapshot of numpy's
 global stream (``gdm_des_run_batch`` on a HIP device: one wave per sample, csrc/des_batch.hip; ``gdm_des_run_batch_host``

@@ -27,11 +27,14 @@ What is stored (inputs AND expected outputs, all small):
                       `Sim` replaced by a recorder (constructor arguments captured, nothing simulated) under
                       np.random.seed(...); see des_prologue() below
   des_core.npz        the reference's Sim itself ('Music' log records) on bridge-shaped arguments; see des_core()
-  des_prologue_rng.npz  the same with a recorder whose run() DRAWS from numpy's global stream like Sim does: pins the
-                      per-sample interleaving of prologue draws and simulation draws; see des_prologue_rng()
+  des_corpus.npz      the reference's Sim on 45 small nets, one per branch of the event logic (ties, queue capacities,
+                      routing branches, sinks, redraws, stops, dims 1..128, the two error cases), with the whole final
+                      generator state and witnesses that the branch was reached; see des_corpus()
+  des_prologue_rng.npz  des_prologue.npz's runs with a recorder whose run() DRAWS from numpy's global stream like Sim does:
+                      pins the per-sample interleaving of prologue draws and simulation draws; see des_prologue_rng()
 
 `python tests/golden/make_golden.py` regenerates everything; `python tests/golden/make_golden.py NAME...` only the
-named sections (base, input_grads, simnn_net, des_prologue, des_prologue_rng, des_core).
+named sections (base, input_grads, simnn_net, des_prologue, des_prologue_rng, des_core, des_corpus).
 """
 import hashlib
 import importlib
@@ -643,8 +646,370 @@ def main():
     print("golden fixtures written to", HERE)
 
 
+# ---- des_corpus: the reference's Sim on a corpus of small nets, one per branch of the event logic -----------------------
+def _corpus_net(dim, sources, flows, params, qcap, default=(1.0, 0.25), server_diag=-1.0):
+    """One case's constructor arguments.  sources: node ids with a positive diagonal; flows {(i, j): flow}; params
+    {node: (loc, scale)} (float32, like the bridges'; `default` for the rest); qcap: an int or {node: cap} (the largest
+    of them for the rest, so that a ring as wide as the largest capacity is exactly as wide as the busiest queue)."""
+    adj = np.zeros((dim, dim))
+    for i in range(dim):
+        adj[i, i] = 1.0 if i in sources else (server_diag if i % 2 else 0.0)     # servers: diagonal <= 0, both kinds
+    for (i, j), f in flows.items():
+        adj[i, j] = f
+    dist = [["normal", np.float32(params.get(i, default)[0]), np.float32(params.get(i, default)[1])] for i in range(dim)]
+    caps = [int(qcap.get(i, max(qcap.values()))) if isinstance(qcap, dict) else int(qcap) for i in range(dim)]
+    return {"sim_matrix": adj, "distributions": dist, "queue_list": caps}
+
+
+def _corpus_flows(n, uniform, seed):
+    """n positive flows whose normalised values (FlowBranchOperator's own arithmetic) sum to exactly 1 (uniform=False:
+    the p= branch) or not (uniform=True: np.random.choice(children))."""
+    rs = np.random.RandomState(seed)
+    for _ in range(100000):
+        p = [float(x) for x in rs.uniform(0.1, 1.0, n)]
+        q = [p[i] / sum(p) for i in range(n)]
+        if (sum(q) != 1) == uniform:
+            return p
+    raise AssertionError("no such row found")
+
+
+def _corpus_random_net(dim, seed, sources=None, n_children=(1, 3), qcap=(1, 6)):
+    """A seeded random net: sources at low and high indices, servers ranked by a random permutation and routing only to
+    later-ranked servers (every path ends in a childless server), random float32 parameters and capacities."""
+    rs = np.random.RandomState(seed)
+    if sources is None:
+        k = max(1, dim // 5)
+        sources = sorted(set(rs.choice(dim, size=k, replace=False).tolist())) if dim > 1 else []
+    servers = [i for i in range(dim) if i not in sources]
+    order = [servers[i] for i in rs.permutation(len(servers))]
+    flows = {}
+    for r, i in enumerate(order):
+        later = order[r + 1:]
+        if not later:
+            continue
+        k = min(len(later), int(rs.randint(n_children[0], n_children[1] + 1)))
+        picks = rs.choice(len(later), size=k, replace=False)
+        for c in picks:
+            flows[(i, later[c])] = float(np.float32(rs.uniform(0.1, 1.0))) if rs.random_sample() < 0.6 else 0.5
+    for s in sources:
+        k = min(len(order), int(rs.randint(1, 3)))
+        for c in rs.choice(min(len(order), max(k, len(order) // 2)), size=k, replace=False):
+            flows[(s, order[c])] = 0.5
+    params = {}
+    for i in range(dim):
+        if i in sources:
+            params[i] = (rs.uniform(0.6, 1.4) * max(1, len(sources)) * 0.5, rs.uniform(0.05, 0.4))
+        else:
+            params[i] = (rs.uniform(0.2, 0.9), 0.0 if rs.random_sample() < 0.15 else rs.uniform(0.05, 0.5))
+    caps = {i: int(rs.randint(qcap[0], qcap[1] + 1)) for i in range(dim)}
+    return _corpus_net(dim, sources, flows, params, caps), sources
+
+
+def _corpus_cases():
+    """name -> (spec, seeds, customers, np_seed, pre_normal, what the case exists for).  The catalogue."""
+    C = {}
+
+    def add(name, spec, customers, np_seed, seeds=(4242,), pre_normal=0, want=()):
+        assert name not in C
+        C[name] = (spec, np.array(seeds), customers, np_seed, pre_normal, tuple(want))
+
+    Z = 0.0                                                # scale 0: deterministic
+    # ---- ties ----
+    # (a) three sources with one deterministic period feed one deterministic server (capacity 2: reneging under ties)
+    add("tie_a", _corpus_net(5, [0, 1, 2], {(0, 4): 1.0, (1, 4): 1.0, (2, 4): 1.0, (4, 3): 1.0},
+                             {0: (0.5, Z), 1: (0.5, Z), 2: (0.5, Z), 4: (0.25, Z), 3: (0.5, Z)}, {4: 2, 3: 1}),
+        100, 11, want=("ties", "deterministic", "reneges", "childless"))
+    # (b) commensurate dyadic periods and service times: arrivals and departures coincide
+    tb = {(0, 3): 1.0, (1, 3): 0.5, (1, 4): 0.5, (2, 4): 1.0, (3, 5): 0.25, (3, 4): 0.75, (4, 5): 1.0}
+    pb = {0: (0.25, Z), 1: (0.5, Z), 2: (0.75, Z), 3: (0.25, Z), 4: (0.5, Z), 5: (0.75, Z)}
+    add("tie_b", _corpus_net(6, [0, 1, 2], tb, pb, {3: 2, 4: 1, 5: 0}), 120, 12, want=("ties", "deterministic"))
+    # (c) the same with random nodes mixed in
+    pc = dict(pb)
+    pc[1], pc[4] = (0.5, 0.2), (0.5, 0.3)
+    add("tie_c", _corpus_net(6, [0, 1, 2], tb, pc, {3: 2, 4: 1, 5: 0}), 120, 13, want=("ties",))
+    # (d) twelve / thirteen sources with one period: a dozen simultaneous events, sift paths several levels deep
+    fd = {(s, 12 + s % 2): 1.0 for s in range(12)}
+    fd.update({(12, 14): 1.0, (13, 15): 0.5, (13, 14): 0.5})
+    pd = {s: (0.5, Z) for s in range(12)}
+    pd.update({12: (0.125, Z), 13: (0.25, Z), 14: (0.125, Z), 15: (0.5, Z)})
+    add("tie_d16", _corpus_net(16, list(range(12)), fd, pd, {12: 3, 13: 2, 14: 1, 15: 0}), 150, 14,
+        want=("ties", "deterministic", "group12"))
+    src65 = list(range(2, 26, 2)) + [64]                   # 13 sources, one of them in the second lane pass
+    fd = {(s, 1 + 2 * (k % 3)): 1.0 for k, s in enumerate(src65)}
+    fd.update({(1, 63): 1.0, (3, 63): 0.5, (3, 61): 0.5, (5, 61): 1.0})
+    pd = {s: (0.5, Z) for s in src65}
+    pd.update({1: (0.125, Z), 3: (0.25, Z), 5: (0.125, Z), 61: (0.25, Z), 63: (0.125, Z)})
+    add("tie_d65", _corpus_net(65, src65, fd, pd, {1: 3, 3: 2, 5: 1, 61: 2, 63: 0}, default=(1.0, Z)), 150, 15,
+        want=("ties", "deterministic", "group12"))
+    # (e) non-dyadic equal periods: the sums round, identically, and still tie
+    add("tie_e", _corpus_net(5, [0, 1, 2], {(0, 4): 1.0, (1, 4): 1.0, (2, 3): 1.0, (4, 3): 1.0},
+                             {0: (0.3, Z), 1: (0.3, Z), 2: (0.3, Z), 4: (0.3, Z), 3: (0.3, Z)}, {4: 2, 3: 3}),
+        100, 16, want=("ties", "deterministic"))
+    # ---- queues: two quick sources, one slow server, a sink behind it ----
+    fq = {(0, 3): 1.0, (1, 3): 1.0, (3, 4): 1.0}
+    pq = {0: (0.5, 0.2), 1: (0.6, 0.3), 3: (0.45, 0.2), 4: (0.2, 0.1)}
+    for name, caps, seed in (("q_cap0", {3: 0, 4: 0}, 21), ("q_cap1", {3: 1, 4: 1}, 22), ("q_cap2", {3: 2, 4: 2}, 23),
+                             ("q_mix", {3: 2, 4: 0, 2: 1}, 24)):
+        add(name, _corpus_net(5, [0, 1], fq, pq, caps), 100, seed, want=("reneges",))
+    add("q_wrap3", _corpus_net(5, [0, 1], fq, pq, {3: 3, 4: 3}), 150, 25, want=("reneges", "wrap3"))
+    # ---- routing ----
+    u2, u5, u6, u7 = (_corpus_flows(n, True, 30 + n) for n in (2, 5, 6, 7))
+    add("route_u2", _corpus_net(6, [0], {(0, 1): 1.0, (1, 2): u2[0], (1, 3): u2[1], (2, 4): 1.0, (3, 4): 1.0},
+                                {0: (0.5, 0.2), 1: (0.3, 0.1), 2: (0.4, 0.2), 3: (0.4, 0.2), 4: (0.2, 0.1)}, 4),
+        80, 31, want=("uniform",))
+    add("route_p", _corpus_net(6, [0], {(0, 1): 1.0, (1, 2): 0.5, (1, 3): 0.5, (2, 4): 0.25, (2, 5): 0.75, (3, 4): 1.0},
+                               {0: (0.5, 0.2), 1: (0.3, 0.1), 2: (0.3, 0.2), 3: (0.4, 0.2), 4: (0.2, 0.1), 5: (0.2, 0.1)}, 4),
+        80, 32, want=("pbranch",))
+    # a single child: its probability is p / p == 1, so the p= branch (one double drawn per routing); the uniform branch
+    # with one child (nothing drawn) cannot be reached through the reference's constructor
+    add("route_single", _corpus_net(5, [4], {(4, 3): 0.7, (3, 2): 0.3, (2, 1): 2.0},
+                                    {4: (0.6, 0.2), 3: (0.3, 0.1), 2: (0.3, 0.1), 1: (0.3, 0.1)}, 4),
+        80, 33, want=("single",))
+    for name, dim, fl, uniform, seed in (("route_u5", 15, u5, True, 34), ("route_u6", 16, u6, True, 35),
+                                         ("route_u7", 17, u7, True, 36),
+                                         ("route_p7", 15, [0.125] * 6 + [0.25], False, 37)):
+        n = len(fl)
+        hub, kids = dim - 2, list(range(2, 2 + n))
+        flows = {(dim - 1, hub): 1.0, (0, hub): 1.0}
+        flows.update({(hub, k): f for k, f in zip(kids, fl)})
+        flows.update({(k, 1): 1.0 for k in kids[::2]})     # every other child hands on to node 1, a childless server
+        pr = {dim - 1: (0.5, 0.2), 0: (0.7, 0.3), hub: (0.2, 0.1), 1: (0.1, 0.05)}
+        add(name, _corpus_net(dim, [0, dim - 1], flows, pr, 6, default=(0.4, 0.2)), 100, seed,
+            want=("uniform" if uniform else "pbranch", f"children{n}"))
+    add("route_neg", _corpus_net(6, [0], {(0, 1): 1.0, (0, 2): -0.5, (1, 2): 0.5, (1, 3): 0.5, (1, 4): -1.0, (1, 5): 0.0,
+                                          (2, 4): 1.0, (3, 4): -0.25, (4, 1): -2.0, (2, 0): -1.0},
+                                 {0: (0.5, 0.2), 1: (0.3, 0.1), 2: (0.3, 0.2), 3: (0.4, 0.2), 4: (0.2, 0.1)}, 4),
+        80, 38, want=("negative",))
+    add("route_interleave", _corpus_net(17, [0, 2, 5, 16], {(0, 1): 1.0, (2, 3): 0.5, (2, 1): 0.5, (5, 4): 1.0, (16, 15): 1.0,
+                                                             (1, 3): 0.5, (1, 4): 0.5, (3, 6): 1.0, (4, 6): 0.5, (4, 15): 0.5,
+                                                             (15, 6): 1.0},
+                                        {0: (1.0, 0.3), 2: (1.2, 0.4), 5: (0.9, 0.2), 16: (1.1, 0.3)}, 3,
+                                        default=(0.3, 0.15)),
+        100, 39, want=("interleave",))
+    # ---- sinks ----
+    add("sink_node0_server", _corpus_net(5, [4], {(4, 2): 1.0, (2, 1): 0.5, (2, 3): 0.5, (1, 0): 1.0, (3, 0): 0.5, (3, 1): 0.5},
+                                         {4: (0.5, 0.2), 0: (0.3, 0.1)}, 4, default=(0.3, 0.15)),
+        80, 41, want=("sink0",))
+    add("sink_node0_source", _corpus_net(5, [3], {(3, 0): 1.0, (0, 1): 0.5, (0, 2): 0.5, (1, 2): 1.0},
+                                         {3: (0.5, 0.2)}, 4, default=(0.3, 0.15)),
+        80, 42, want=("source0",))
+    # ---- draws ----
+    add("draw_redraw", _corpus_net(5, [0], {(0, 1): 1.0, (1, 2): 1.0}, {0: (1.5, 0.3), 1: (0.1, 1.0), 2: (0.1, 1.0)}, 6),
+        100, 51, want=("redraw",))
+    add("draw_backwards", _corpus_net(5, [0, 2], {(0, 1): 1.0, (2, 3): 1.0, (1, 4): 1.0, (3, 4): 1.0},
+                                      {0: (0.3, 0.6), 2: (0.3, 0.6)}, 6, default=(0.2, 0.1)),
+        100, 52, want=("backwards",))
+    add("draw_scale0", _corpus_net(5, [0, 2], {(0, 1): 1.0, (2, 3): 1.0, (1, 4): 0.5, (1, 3): 0.5, (3, 4): 1.0},
+                                   {0: (0.5, Z), 2: (0.7, 0.3), 1: (0.375, Z), 3: (0.25, 0.1), 4: (0.125, Z)}, 3),
+        100, 53, want=("scale0",))
+    add("draw_cached_gauss", _corpus_net(6, [0], {(0, 1): 1.0, (1, 2): 0.5, (1, 3): 0.5, (2, 4): 0.25, (2, 5): 0.75,
+                                                  (3, 4): 1.0}, {0: (0.5, 0.2)}, 4, default=(0.3, 0.15)),
+        80, 54, pre_normal=1, want=("cached_gauss",))
+    # ---- stops: two sources ----
+    fs = {(0, 2): 1.0, (1, 2): 1.0, (2, 3): 0.5, (2, 4): 0.5}
+    ps = {0: (0.5, 0.2), 1: (0.7, 0.3)}
+    for n in (0, 1, 2, 3, 4):
+        add(f"stop_n{n}", _corpus_net(5, [0, 1], fs, ps, 4, default=(0.3, 0.15)), n, 60 + n, want=(f"stop{n}",))
+    add("stop_nosrc", _corpus_net(3, [], {(0, 1): 1.0, (1, 2): 1.0}, {}, 4), 60, 66, want=("nosrc",))
+    add("stop_two_seeds", _corpus_net(5, [0, 1], fs, ps, 4, default=(0.3, 0.15)), 60, 67, seeds=(4242, 977),
+        want=("two_seeds",))
+    # ---- sizes ----
+    add("size_1", _corpus_net(1, [], {}, {}, 4), 60, 71, want=("nosrc",))
+    add("size_2", _corpus_net(2, [1], {(1, 0): 1.0}, {1: (0.5, 0.2), 0: (0.4, 0.2)}, 2), 120, 72, want=())
+    add("size_3", _corpus_net(3, [1], {(1, 2): 1.0, (2, 0): 1.0}, {1: (0.5, 0.2), 2: (0.4, 0.2), 0: (0.3, 0.2)}, 2),
+        60, 73, want=())
+    add("size_3b", _corpus_net(3, [0], {(0, 1): 0.5, (0, 2): 0.5, (1, 2): 1.0}, {0: (0.5, 0.25), 1: (0.6, 0.2), 2: (0.2, 0.1)}, 1),
+        40, 74, want=())
+    for dim, seed, customers in ((15, 81, 90), (16, 82, 90), (17, 83, 90), (64, 84, 100), (65, 85, 70), (128, 86, 80)):
+        sources = None
+        if dim == 65:
+            sources = [1, 7, 20, 33, 47, 64]               # a source in the second lane pass; servers there: at 128
+        if dim == 128:
+            sources = [0, 3, 9, 30, 62, 63, 64, 65, 90, 111, 126, 127]
+        spec, sources = _corpus_random_net(dim, seed, sources)
+        add(f"size_{dim}", spec, customers, seed + 100, want=("second_pass",) if dim > 64 else ())
+    # ---- errors ----
+    add("err_to_source", _corpus_net(5, [0, 1], {(0, 2): 1.0, (1, 2): 1.0, (2, 3): 0.5, (2, 1): 0.5}, ps, 4,
+                                     default=(0.3, 0.15)), 60, 91, want=("error",))
+    add("err_source_childless", _corpus_net(5, [0, 1], {(0, 2): 1.0, (2, 3): 1.0}, ps, 4, default=(0.3, 0.15)),
+        60, 92, want=("error",))
+    return C
+
+
+def _write_npz_reproducibly(path, arrays):
+    """np.savez_compressed with fixed member dates: the same arrays give the same bytes."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for k in sorted(arrays):
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(arrays[k]), allow_pickle=False)
+
+
+def des_corpus():
+    """des_corpus.npz: the reference's own ``Sim`` ('Music' mode) on a catalogue of small nets, each built for one
+    branch of the event logic (_corpus_cases): constructor arguments, number_of_customers, numpy seed (and the whole
+    state handed in where that is not a plain seed), every log record, the WHOLE final global generator state, and the
+    case's witnesses -- computed from the reference's objects and its log, never from the project's code -- that the
+    branch was reached.  The generator asserts the witness every case was built for, and that no two distinct event
+    times of a recording are nearly simultaneous (portable math may move a value by a few ulps, not change the order)."""
+    import logging
+    import math
+    import re
+    import tempfile
+    S = load_reference("MMGAN_MIDI_DES", "simulation_v3")
+    line_re = re.compile(r"INFO:root:(\S+) - (\S+) - (\S+) - (arrival|departure|processing)$")
+    skip_re = re.compile(r"INFO:root:\d+ branch method set as shortest queue$")     # simulation_v3.py:51: childless nodes
+    kinds = {"arrival": 0, "departure": 1, "processing": 2}
+    out, names, total = {}, [], 0
+
+    for name, (spec, seeds, customers, np_seed, pre_normal, want) in _corpus_cases().items():
+        dim = len(spec["queue_list"])
+        np.random.seed(np_seed)
+        if pre_normal:
+            np.random.standard_normal(pre_normal)
+        state0 = np.random.get_state()
+        cwd = os.getcwd()
+        error, rows, sim = "", [], None
+        with tempfile.TemporaryDirectory() as tmp:
+            os.chdir(tmp)
+            os.makedirs("logs")
+            try:
+                for h in list(logging.root.handlers):
+                    logging.root.removeHandler(h)
+                sim = S.Sim(spec["sim_matrix"].copy(), spec["distributions"], list(spec["queue_list"]), seeds=seeds,
+                            log_path="logs/", generate_log=True, animation=False, record_history=False,
+                            logging_mode='Music', max_sim_time=1e9)
+                try:
+                    sim.run(number_of_customers=customers)
+                except Exception as e:                     # the class name is what is recorded
+                    error = type(e).__name__
+                    logging.shutdown()
+                for ln in open("logs/simulation.log"):
+                    if skip_re.match(ln.strip()):
+                        continue
+                    m = line_re.match(ln.strip())
+                    assert m, ln
+                    rows.append((float(m.group(1)), int(m.group(2)), int(m.group(3)), kinds[m.group(4)]))
+            finally:
+                os.chdir(cwd)
+        final = np.random.get_state()
+        pre = name
+        names.append(name)
+        out[f"{pre}/sim_matrix"] = np.asarray(spec["sim_matrix"], dtype=np.float64)
+        out[f"{pre}/dist"] = np.array([[float(d[1]), float(d[2])] for d in spec["distributions"]], dtype=np.float64)
+        out[f"{pre}/queue_list"] = np.array(spec["queue_list"], dtype=np.int32)
+        out[f"{pre}/seeds"] = np.asarray(seeds, dtype=np.int64)
+        out[f"{pre}/customers"] = np.int64(customers)
+        out[f"{pre}/np_seed"] = np.int64(np_seed)
+        if pre_normal:
+            out[f"{pre}/state0_key"] = np.asarray(state0[1], dtype=np.uint32)
+            out[f"{pre}/state0_rest"] = np.array([state0[2], state0[3]], dtype=np.int64)
+            out[f"{pre}/state0_gauss"] = np.float64(state0[4])
+            assert state0[3] == 1 and state0[4] != 0.0
+        out[f"{pre}/error"] = np.array(error)
+        if error:
+            continue
+        value = np.array([r[0] for r in rows], dtype=np.float64)
+        eid = np.array([r[1] for r in rows], dtype=np.int64)
+        node = np.array([r[2] for r in rows], dtype=np.int32)
+        kind = np.array([r[3] for r in rows], dtype=np.int32)
+        out[f"{pre}/value"], out[f"{pre}/event_id"], out[f"{pre}/node"], out[f"{pre}/kind"] = value, eid, node, kind
+        out[f"{pre}/final_key"] = np.asarray(final[1], dtype=np.uint32)
+        out[f"{pre}/final_rest"] = np.array([final[2], final[3]], dtype=np.int64)
+        out[f"{pre}/final_gauss"] = np.float64(final[4])
+        total += len(rows)
+        assert len(rows) <= 1250, (name, len(rows))
+
+        # ---- witnesses, from the reference's objects and its log ----
+        ev = kind < 2                                      # arrival / departure records carry the event times
+        t, ids = value[ev], eid[ev]
+        same = t[1:] == t[:-1]
+        ties = int((same & (ids[1:] != ids[:-1])).sum())
+        group, i = 0, 0
+        while i < len(t):
+            j = i
+            while j + 1 < len(t) and t[j + 1] == t[i]:
+                j += 1
+            group = max(group, len(set(ids[i:j + 1].tolist())))
+            i = j + 1
+        u = np.unique(t)
+        gaps = np.diff(u) / np.maximum(1.0, np.abs(u[1:])) if len(u) > 1 else np.array([np.inf])
+        assert gaps.min() > 1e-9, (name, "nearly simultaneous events: choose another seed", gaps.min())
+        reneges = np.array([sim.servers[i].reneges if i in sim.servers else -1 for i in range(dim)], dtype=np.int64)
+        is_sink = np.array([int(sim.servers[i].destination.is_sink()) if i in sim.servers else -1 for i in range(dim)],
+                           dtype=np.int8)
+        nodes_of = {**sim.servers, **sim.sources}
+        n_children = np.array([len(nodes_of[i].destination.children) for i in range(dim)], dtype=np.int32)
+        routed = np.array([int(((kind == 1) & (node == i)).sum()) if i in sim.servers and not is_sink[i] else 0
+                           for i in range(dim)], dtype=np.int64)
+        uniform = np.array([(int(sum(nodes_of[i].destination.probabilities) != 1) if routed[i] >= 20 else -1)
+                            for i in range(dim)], dtype=np.int8)
+        backwards = bool((np.diff(t) < 0).any()) if len(seeds) == 1 else False
+        # services taken from the queue: a processing record that follows the node's own departure record
+        from_queue = np.zeros(dim, dtype=np.int64)
+        for r in range(1, len(kind)):
+            if kind[r] == 2 and kind[r - 1] == 1 and node[r - 1] == node[r]:
+                from_queue[node[r]] += 1
+        p_neg = np.array([0.5 * math.erfc(float(d[1]) / float(d[2]) / math.sqrt(2.0)) if float(d[2]) > 0 else 0.0
+                          for d in spec["distributions"]])
+        services = int((kind == 2).sum())
+        redraw_services = int(sum(int(((kind == 2) & (node == i)).sum()) for i in range(dim) if p_neg[i] >= 0.3))
+        w = {"ties": np.int64(ties), "group": np.int64(group), "reneges": reneges, "is_sink": is_sink,
+             "n_children": n_children, "routed": routed, "uniform": uniform, "backwards": np.bool_(backwards),
+             "from_queue": from_queue, "redraw_services": np.int64(redraw_services),
+             "redraw_share": np.float64(redraw_services / services if services else 0.0),
+             "min_gap": np.float64(gaps.min()), "is_source": np.array([int(i in sim.sources) for i in range(dim)], dtype=np.int8)}
+        for k, v in w.items():
+            out[f"{pre}/w_{k}"] = v
+        caps = np.array(spec["queue_list"])
+        scale = out[f"{pre}/dist"][:, 1]
+        served = np.array([int(((kind == 2) & (node == i)).sum()) for i in range(dim)])
+        for tag in want:                                   # the witness this case was built for
+            ok = {"ties": ties >= 20, "deterministic": bool((scale == 0).all()), "group12": group >= 12,
+                  "reneges": bool((reneges > 0).any()),
+                  "wrap3": bool(((caps == 3) & (from_queue >= 20)).any()),
+                  "uniform": bool((uniform == 1).any()), "pbranch": bool(((uniform == 0) & (n_children >= 2)).any()),
+                  "single": bool(((uniform == 0) & (n_children == 1)).any()),
+                  "negative": bool((spec["sim_matrix"][~np.eye(dim, dtype=bool)] < 0).any()) and len(rows) > 50,
+                  "interleave": bool(w["is_source"][0] == 1 and w["is_source"][-1] == 1 and (w["is_source"][1:-1] == 1).any()
+                                     and (w["is_source"][1:-1] == 0).any()),
+                  "sink0": bool(any(is_sink[i] == 1 and n_children[i] == 1 and served[i] >= 10 for i in range(dim))),
+                  "source0": bool(any(w["is_source"][i] == 1 and n_children[i] == 1 and spec["sim_matrix"][i, 0] > 0
+                                      for i in range(dim)) and is_sink[0] == 0 and served[0] >= 10),
+                  "redraw": redraw_services >= 50 and redraw_services / max(1, services) >= 0.5,
+                  "backwards": backwards,
+                  "scale0": bool(any(scale[i] == 0 and w["is_source"][i] == 1 for i in range(dim))
+                                 and any(scale[i] == 0 and served[i] >= 10 for i in range(dim))),
+                  "cached_gauss": bool(final[3] == 1 and final[4] == state0[4]),
+                  "nosrc": len(rows) == 0 and not sim.sources, "two_seeds": len(seeds) == 2 and int((eid == 0).sum()) >= 4,
+                  "second_pass": bool(w["is_source"][64:].any() and (dim == 65 or (served[64:] > 0).any())),
+                  "error": False}
+            for n in range(5):                             # two sources: nothing is processed up to n = 2
+                ok[f"stop{n}"] = customers == n and (len(rows) == 0) == (n <= 2)
+            ok["childless"] = bool(any(is_sink[i] == 1 and n_children[i] == 0 and served[i] >= 10 for i in range(dim)))
+            for n in (5, 6, 7):
+                ok[f"children{n}"] = bool(((n_children == n) & (routed >= 20)).any())
+            assert ok[tag], (name, tag, {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in w.items()})
+        print(f"{name:22s} dim {dim:3d} records {len(rows):5d} ties {ties:4d} group {group:2d} reneges {int(reneges.clip(0).sum()):3d}"
+              f" min gap {gaps.min():.2e}")
+    for name, (spec, seeds, customers, np_seed, pre_normal, want) in _corpus_cases().items():
+        if "error" in want:
+            assert str(out[f"{name}/error"]) != "", name
+        else:
+            assert str(out[f"{name}/error"]) == "", (name, out[f"{name}/error"])
+    out["names"] = np.array(names)
+    assert 40 <= len(names) <= 60 and total < 40000, (len(names), total)
+    path = os.path.join(HERE, "des_corpus.npz")
+    _write_npz_reproducibly(path, out)
+    assert os.path.getsize(path) <= 700 * 1024, os.path.getsize(path)
+    print(len(names), "cases,", total, "records,", os.path.getsize(path), "bytes")
+
+
 SECTIONS = {"base": main, "input_grads": input_grads, "simnn_net": simnn_net, "des_prologue": des_prologue,
-            "des_prologue_rng": des_prologue_rng, "des_core": des_core}
+            "des_prologue_rng": des_prologue_rng, "des_core": des_core, "des_corpus": des_corpus}
 
 if __name__ == "__main__":
     torch.set_num_threads(4)
