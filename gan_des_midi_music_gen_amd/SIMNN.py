@@ -26,6 +26,7 @@ from torch import nn
 import torch.nn.init as init
 
 from . import functional as Fn
+from . import matrix_sim_process as msp
 from . import synthetic
 
 
@@ -175,15 +176,10 @@ def generate_song(model_folder, device=None, bridge=None, compute_dtype=None, *,
     with torch.no_grad():
         generated = gen(get_noise(1, 100, device=device)).detach()
     if isinstance(bridge, str):
-        if bridge not in ("des", "des_batch", "des_device"):
-            raise ValueError(f"unknown bridge {bridge!r} (the built-in ones are \"des\", \"des_batch\" and "
-                             "\"des_device\")")
-        return _des_song(generated.reshape(1, 20, 20), midi_path, wav_path, max_seconds, batched=bridge)
+        msp.check_back_end(bridge, "unknown bridge", ValueError)
+        return _des_song(generated.reshape(1, 20, 20), midi_path, wav_path, max_seconds, bridge)
     adj = generated.squeeze().cpu().numpy()
     return bridge(adj) if bridge is not None else adj
-
-
-_WAV_CHUNK = 1 << 22          # samples rendered per gdm_synth_pcm launch (8 MB of PCM)
 
 
 def _write_clip(notes, n_notes, i, count, total, midi_path, wav_path, max_seconds):
@@ -195,40 +191,13 @@ def _write_clip(notes, n_notes, i, count, total, midi_path, wav_path, max_second
     if midi_path is not None:
         sim_log_to_midi.write_midi(slpm.notes_to_track(notes[i, :count].cpu().numpy()), midi_path)
     if wav_path is not None:
-        blank = total == 0
-        if blank:
-            total = 5 * ops.SYNTH_RATE                                   # matrix_sim_process.py:103: np.zeros(5 * 44100)
-        if max_seconds is not None:
-            total = max(1, min(total, int(max_seconds * ops.SYNTH_RATE)))
-        d = os.path.dirname(wav_path)
-        if d:
-            os.makedirs(d, exist_ok=True)
-        with open(wav_path, "wb") as f:
-            f.write(util.wav_header(total, ops.SYNTH_RATE))
-            for first in range(0, total, _WAV_CHUNK):
-                chunk = min(_WAV_CHUNK, total - first)
-                pcm = torch.zeros(chunk, dtype=torch.int16) if blank else \
-                    ops.synth_pcm(notes[i:i + 1], n_notes[i:i + 1], first, chunk).cpu()
-                f.write(pcm.numpy().astype("<i2").tobytes())
+        util.write_wav_chunks(wav_path, total, lambda first, n: ops.synth_pcm(notes[i:i + 1], n_notes[i:i + 1], first, n),
+                              blank=total == 0, max_seconds=max_seconds)
 
 
-def _des_mel(matrices, batched):
-    """matrix_to_wav(simulate="des" / "des_batch" / "des_device") on (B, 20, 20) matrices (batched: True for
-    "des_batch", or a back end's name), keeping the note lists:
-    -> (mel (B, 128, 216), (notes, n_notes, clip_len))."""
-    from . import matrix_sim_process as msp
-    if batched == "des_device":
-        return msp._batch_to_mel(msp.device_prologue_wav(matrices, 20, None), 200000)
-    if batched and batched != "des":
-        return msp._batch_to_mel(msp.batched_prologue_wav(matrices, 20, None), 200000)
-    h = msp._wav_scan(matrices, 20)
-    specs = msp._interleaved_specs(h, msp._wav_draws, lambda h_, i, r, src, sd: msp._wav_spec(h_, i, r, src, sd, None))
-    return msp._specs_to_mel(specs, matrices.device, 200000)
-
-
-def _des_song(matrix, midi_path, wav_path, max_seconds, batched=False):
-    """matrix_to_wav(simulate="des" / "des_batch") for one matrix, keeping the note list for the two files."""
-    mel, (notes, n_notes, clip_len) = _des_mel(matrix, batched)
+def _des_song(matrix, midi_path, wav_path, max_seconds, bridge):
+    """matrix_to_wav with the built-in back end ``bridge`` for one matrix, keeping the note list for the two files."""
+    mel, (notes, n_notes, clip_len) = msp.matrices_to_mel(matrix, simulate=bridge)
     _write_clip(notes, n_notes, 0, int(n_notes[0]), int(clip_len[0]), midi_path, wav_path, max_seconds)
     return mel[0]
 
@@ -249,17 +218,15 @@ def generate_songs(model, n_samples=None, *, noise=None, bridge="des_batch", out
 
     model: a ``Generator`` or the path of a ``gen_*.pt`` checkpoint.  ``sample_matrices`` draws the n matrices (one
     launch), then bridge "des_batch" simulates all of them in one device launch
-    (matrix_sim_process._batch_to_mel(batched_prologue_wav(...))) and "des" keeps the reference's interleaved order
+    (matrix_sim_process.matrices_to_mel) and "des" keeps the reference's interleaved order
     (see matrix_sim_process for what differs); "des_device" also makes the draws on the device, one stream per clip.
     With ``out_dir`` clip i is written to ``out_dir/song_{i:04d}.mid`` (midi)
     and ``.wav`` (wav) exactly as ``generate_song`` writes its one clip; with out_dir=None nothing is written and the
     path lists hold None.  -> SongBatch."""
-    if bridge not in ("des", "des_batch", "des_device"):
-        raise ValueError(f"unknown bridge {bridge!r} (the built-in ones are \"des\", \"des_batch\" and "
-                         "\"des_device\")")
+    msp.check_back_end(bridge, "unknown bridge", ValueError)
     matrices = sample_matrices(model, n_samples, noise=noise, compute_dtype=compute_dtype, device=device)
     n = matrices.shape[0]
-    mel, (notes, n_notes, clip_len) = _des_mel(matrices.reshape(n, 20, 20), bridge)
+    mel, (notes, n_notes, clip_len) = msp.matrices_to_mel(matrices.reshape(n, 20, 20), simulate=bridge)
     midi_paths, wav_paths = [None] * n, [None] * n
     if out_dir is not None:
         counts, lengths = n_notes.cpu(), clip_len.cpu()                  # one read-back for all clips
@@ -276,7 +243,6 @@ def des_fake_provider(start=0, end=216, max_events=200000, batched=False):
     generated (B,1,20,20) device tensor -> (B,128,end-start) dB tensor on the same device (SIMNN.py:301).
     batched: simulate on the device (matrix_to_wav(simulate="des_batch")); a back end's name ("des_batch",
     "des_device") selects that one."""
-    from . import matrix_sim_process as msp
     simulate = batched if isinstance(batched, str) else ("des_batch" if batched else "des")
 
     def provider(generated):
@@ -373,9 +339,7 @@ def train(dataloader=None, *, n_epochs=1, batch_size=30, lr=0.00002, betas=(0.5,
     elif input_hw is None:
         input_hw = (128, 216)
     if isinstance(fake_provider, str):
-        if fake_provider not in ("des", "des_batch", "des_device"):
-            raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in ones are \"des\", "
-                             "\"des_batch\" and \"des_device\")")
+        msp.check_back_end(fake_provider, "unknown fake_provider", ValueError)
         if input_hw[0] != 128 or not 0 < input_hw[1] <= 216:
             raise ValueError(f"fake_provider=\"{fake_provider}\" makes (128, end - start <= 216) windows, input_hw is "
                              f"{tuple(input_hw)}")
@@ -437,7 +401,7 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=30)
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--no-save", action="store_true", help="write no generator checkpoints")
-    ap.add_argument("--fake-provider", choices=["des", "des_batch", "des_device"], default=None,
+    ap.add_argument("--fake-provider", choices=msp.BACK_ENDS, default=None,
                     help="des: fakes from the built-in DES bridge; des_batch: the same with the simulation batched on "
                          "the device; des_device: the draws on the device too (default: seeded synthetic windows)")
     ap.add_argument("--generate", type=int, default=None, metavar="N",
@@ -446,7 +410,7 @@ def main(argv=None):
     ap.add_argument("--out-dir", default="adj_sim_outputs/songs", help="where --generate writes song_NNNN.mid / .wav")
     ap.add_argument("--max-seconds", type=float, default=None, help="cut the clips of --generate")
     ap.add_argument("--seed", type=int, default=None, help="seed of --generate (torch and numpy)")
-    ap.add_argument("--bridge", choices=["des", "des_batch", "des_device"], default="des_batch",
+    ap.add_argument("--bridge", choices=msp.BACK_ENDS, default="des_batch",
                     help="DES bridge of --generate")
     a = ap.parse_args(argv)
     if a.generate is not None:

@@ -624,7 +624,6 @@ class InputSong(torch.utils.data.Dataset):
 # ---- model 1's MAESTRO route: MIDI file -> notes in samples -> windows of the integer synth -> mel dB ------------------
 MAX_CLIP_SAMPLES = 1 << 40          # the synth's sample range (gdm_synth_pcm, GDM_DES_NOTES_ELONG)
 MAX_CLIP_NOTES = 1 << 18            # the kernel's int32 voice sum is proven below that: 2^18 * 8128 < 2^31
-_WAV_CHUNK = 1 << 22                # samples midi_to_wav renders per launch (8 MB of PCM)
 
 
 def midi_notes(midi_input, *, pedal=True, programs=False):
@@ -734,22 +733,13 @@ def midi_to_wav(midi_input, wav_path, *, pedal=True, max_seconds=None, device="c
     ``midi_notes`` as a mono 16-bit 44 100 Hz WAV file, rendered by the integer synth in bounded chunks (one
     ``ops.synth_windows`` window of 2^22 samples per launch); ``max_seconds`` cuts it.  Returns the samples written."""
     notes, clip_len = midi_notes(midi_input, pedal=pedal)
-    total = clip_len
-    if max_seconds is not None:
-        total = max(1, min(total, int(max_seconds * ops.SYNTH_RATE)))
     rows, off_max, note_ptr = _upload_clips([notes], device)
     win_clip = torch.zeros(1, dtype=torch.int32, device=rows.device)
-    d = os.path.dirname(wav_path)
-    if d:
-        os.makedirs(d, exist_ok=True)
-    with open(wav_path, "wb") as f:
-        f.write(util.wav_header(total, ops.SYNTH_RATE))
-        for first in range(0, total, _WAV_CHUNK):
-            count = min(_WAV_CHUNK, total - first)
-            start = torch.full((1,), first, dtype=torch.int64, device=rows.device)
-            pcm = ops.synth_windows(rows, off_max, note_ptr, win_clip, start, count)
-            f.write(pcm[0, :count].cpu().numpy().astype("<i2").tobytes())
-    return total
+
+    def render(first, count):
+        start = torch.full((1,), first, dtype=torch.int64, device=rows.device)
+        return ops.synth_windows(rows, off_max, note_ptr, win_clip, start, count)[0, :count]
+    return util.write_wav_chunks(wav_path, clip_len, render, max_seconds=max_seconds)
 
 
 def choose_windows(n, k):

@@ -6,6 +6,17 @@
                                                         the generate=True route for a batch: every sample's track
     matrix_to_wav(matrices, size=20, use_same_instrument=None, start=0, end=174, device='cpu')
                                                         GAN_DES/matrix_sim_process.py:17-137
+    matrices_to_mel(matrices, size=20, use_same_instrument=None, *, simulate)
+                                                        matrix_to_wav's built-in back ends, keeping the note lists
+
+How the module is laid out: what differs between the two bridges is one ``Route`` record each (``MIDI``, ``WAV``: the
+scan's arguments, the host draws ``_midi_draws`` / ``_wav_draws``, the spec builders ``_midi_spec`` / ``_wav_spec``, the
+``ops.des_draws`` route), and the stages are written once over it: ``Route.scan`` (validation + the scan launch, its
+products downloaded or left on the device), ``Route.specs`` (the reference's interleaved order), ``Route.batched`` ->
+``BatchedPrologue`` and ``Route.device`` -> ``DevicePrologue``.  The two prologues show their consumers one surface
+(the per-node fields, ``simulate_on``, ``readback_words``, ``check``, ``check_rec_ptr``); ``BACK_ENDS`` /
+``check_back_end`` name the built-in back ends for every module that takes one, and the back-end name picks the
+prologue in ``Route.prologue``.  ``midi_prologue`` ... ``device_prologue_wav`` are the public wrappers.
 
 Both reference functions do, per generated sample, (1) a block of numpy arithmetic that turns the generator's matrix
 into the constructor arguments of the discrete-event simulator and (2) the simulation / MIDI / audio rendering.  Part
@@ -80,6 +91,7 @@ global stream, sample i+1 continuing from sample i's reseed -- so this is a back
 At most 64 nodes (a row's candidate set is one 64-bit word), which covers both models (61 and 15).
 """
 from dataclasses import dataclass, field
+from functools import cached_property
 
 import numpy as np
 import torch
@@ -126,21 +138,6 @@ def _check_finite(flags):
         raise ValueError("generated matrix holds non-finite values: the DES prologue is defined for finite inputs only")
 
 
-def _midi_scan(gen1_output, gen2_output, adj_size):
-    size = adj_size[0]
-    dim = size - 3
-    g1 = gen1_output.detach()
-    if not g1.is_cuda:
-        raise ops.GdmError("matrix_sim_process runs the prologue on a HIP device; move the generator outputs there")
-    g1 = g1.float()
-    scan = ops.des_scan(g1, size, dim, note_mod=True)
-    h = {"g1": g1, "size": size, "dim": dim, "b": g1.shape[0],
-         "g2": gen2_output.detach().float().cpu().numpy(), "inst": scan["instruments"].cpu().numpy(),
-         "notes": scan["note_levels"].cpu().numpy(), "zmask": scan["zero_mask"].cpu().numpy()}
-    _check_finite(scan["flags"].cpu().numpy())
-    return h
-
-
 def _midi_draws(h, i):
     """Sample i's draws from numpy's global stream, in the reference's order (lines 43, 101-102, 119-120)."""
     dim = h["dim"]
@@ -164,24 +161,141 @@ def _midi_spec(h, i, routing, src, seeds, instrument):
                    instruments, h["notes"][i].astype(np.float64), np.flatnonzero(src))
 
 
-def _routing(h, lo, hi, src, cols):
-    """des_routing for samples [lo, hi) of the scanned batch: src (n,dim) bool, cols (n,dim) int32 -> (n,dim,dim) f64."""
+def _wav_draws(h, i):
+    dim, size = h["dim"], h["size"]
+    hit = np.flatnonzero(h["thr"][i])
+    if len(hit) == 0:
+        sources = np.random.choice(dim, size=size // 8, replace=False)     # line 27
+    elif len(hit) == 1:
+        sources = hit
+    else:
+        raise ValueError("The truth value of an array with more than one element is ambiguous (matrix_to_wav keeps "
+                         "np.where's tuple: more than one thresholded source cannot be processed, line 30)")
+    if sources.max() >= dim:
+        raise IndexError(f"index {int(sources.max())} is out of bounds for axis 1 with size {dim}")   # line 67
+    src = np.zeros(dim, dtype=bool)
+    src[sources] = True
+    cols = _draw_residue_columns(h["zmask"][i], src, dim)
+    return src, cols, _reseed()
+
+
+def _wav_spec(h, i, routing, src, seeds, use_same_instrument):
+    dim = h["dim"]
+    r3, r4 = h["aux"][i, 0], h["aux"][i, 1]
+    dist = [["normal", 30 * r3[k], 15 * r4[k]] if src[k] else ["normal", 5 * r3[k], 3 * r4[k]] for k in range(dim)]
+    instruments = h["inst"][i].astype(np.float64) if use_same_instrument is None else \
+        np.array([use_same_instrument] * dim)
+    return DesSpec(routing, dist, [2 * 127] * dim, seeds, 1000, 0.5, instruments, h["notes"][i].astype(np.float64),
+                   np.flatnonzero(src))
+
+
+BACK_ENDS = ("des", "des_batch", "des_device")
+
+
+def check_back_end(name, who, exc=ops.GdmError):
+    """Raise ``exc`` unless ``name`` is a built-in back end; ``who`` opens the message ("f: unknown back end")."""
+    if name not in BACK_ENDS:
+        names = ", ".join(f'"{n}"' for n in BACK_ENDS[:-1])
+        raise exc(f"{who} {name!r} (the built-in ones are {names} and \"{BACK_ENDS[-1]}\")")
+
+
+@dataclass(frozen=True)
+class Route:
+    """What differs between the two bridges; everything below is written once over it (``MIDI``, ``WAV``)."""
+    inputs: str               # what the error for a host tensor calls the input
+    aux_rows: int             # dim = size - aux_rows
+    scan_args: dict           # keyword arguments of ops.des_scan
+    host_fields: tuple        # (key in h, key of the scan) of what the host draws and specs read
+    draws: object             # (h, i) -> (src, cols, seeds): sample i's draws from numpy's global stream
+    spec: object              # (h, i, routing, src, seeds, instrument) -> DesSpec
+    draws_id: int             # ops.DES_DRAWS_*
+    params: str               # key in a device scan of the ``params`` argument of ops.des_draws
+
+    def scan(self, g, size, g2=None, *, download=True, tail=False):
+        """Validate the inputs and launch the RNG-free scan -> the dict ``h`` every later stage reads: ``g1``, ``size``,
+        ``dim``, ``b``; with ``download`` the host copies the numpy draws and specs need (``g2``, ``inst``, ``notes``,
+        ``zmask``, ``thr``, ``aux``: whichever the route has) after a finite check; without, nothing is read back and
+        ``h`` holds the device tensors (``g2``, ``scan``, ``aux``, ``flags``).  ``tail``: gen2_output[10:16] will be
+        read (the built-in MIDI back ends)."""
+        g = g.detach() if isinstance(g, torch.Tensor) else torch.as_tensor(np.asarray(g))
+        if not g.is_cuda:
+            raise ops.GdmError(f"matrix_sim_process runs the prologue on a HIP device; move the {self.inputs} there")
+        if tail and g2.shape[1] < 16:
+            raise ops.GdmError("matrix_to_midi: gen2_output needs at least 16 columns (gen2_output[10:16] drive the "
+                               "MIDI)")
+        g = g.float()
+        h = {"g1": g, "size": size, "dim": size - self.aux_rows, "b": g.shape[0]}
+        if g2 is not None and not download:
+            h["g2"] = g2.detach().to(device=g.device, dtype=torch.float32).contiguous()
+            if h["g2"].dim() != 2 or h["g2"].shape[0] != h["b"] or h["g2"].shape[1] < 7:
+                raise ops.GdmError("des_device: gen2_output must be (B, n) with n >= 7 (columns 1..6 drive the "
+                                   "simulator)")
+        scan = ops.des_scan(g, size, h["dim"], **self.scan_args)
+        if not download:
+            h.update(scan=scan, aux=scan["aux"], flags=scan["flags"])
+            return h
+        if g2 is not None:
+            h["g2"] = g2.detach().float().cpu().numpy()
+        h.update((key, scan[name].cpu().numpy()) for key, name in self.host_fields)
+        _check_finite(scan["flags"].cpu().numpy())
+        return h
+
+    def specs(self, h, instrument=None):
+        """The reference's order: a sample's spec is complete (and handed to the caller, who simulates) before the
+        next sample draws anything.  One one-sample routing launch each."""
+        for i in range(h["b"]):
+            src, cols, sd = self.draws(h, i)
+            routing = _routing(h, slice(i, i + 1), src[None], cols[None]).cpu().numpy()[0]
+            yield self.spec(h, i, routing, src, sd, instrument)
+
+    def batched(self, h, instrument=None):
+        """A downloaded scan -> BatchedPrologue: ALL host draws in the reference's order with a snapshot of numpy's
+        stream after each sample's reseed, then one routing launch whose output stays on the device."""
+        b, dim = h["b"], h["dim"]
+        src_all = np.zeros((b, dim), dtype=bool)
+        cols_all = np.empty((b, dim), dtype=np.int32)
+        seeds, states = [], []
+        for i in range(b):                                               # global-RNG order of the reference, per sample
+            src_all[i], cols_all[i], sd = self.draws(h, i)
+            seeds.append(sd)
+            states.append(np.random.get_state())                         # where simulation i starts
+        return BatchedPrologue(self, h, _routing(h, slice(None), src_all, cols_all), src_all, seeds, states, instrument)
+
+    def device(self, h, instrument=None, base=None):
+        """A scan left on the device -> DevicePrologue: ``ops.des_draws`` (sample i on ``RandomState(base[i])``;
+        base=None: ``draw_base_seeds``, the one call on numpy's global stream), routing.  Nothing is read back."""
+        b, dim, dev = h["b"], h["dim"], h["g1"].device
+        if dim > ops.DES_DRAWS_MAX_DIM:
+            raise ops.GdmError(f"des_device: at most {ops.DES_DRAWS_MAX_DIM} nodes (a row's candidates are one 64-bit "
+                               "word)")
+        override = _instrument_override(instrument, b)
+        base = draw_base_seeds(b) if base is None else np.ascontiguousarray(base, dtype=np.uint32).reshape(b)
+        draws = ops.des_draws(self.draws_id, h["size"], dim, torch.from_numpy(base.view(np.int32)).to(dev), h["scan"],
+                              h[self.params], None if override is None else torch.from_numpy(override).to(dev))
+        return DevicePrologue(h, base, draws, ops.des_routing(h["g1"], h["size"], dim, draws["src"], draws["cols"]))
+
+    def prologue(self, back_end, g, size, g2=None, instrument=None, *, tail=False):
+        """Scan and prologue of "des_batch" or "des_device" -> BatchedPrologue or DevicePrologue."""
+        download, make = _PROLOGUES[back_end]
+        return make(self, self.scan(g, size, g2, download=download, tail=tail), instrument)
+
+
+_PROLOGUES = {"des_batch": (True, Route.batched), "des_device": (False, Route.device)}
+MIDI = Route("generator outputs", 3, {"note_mod": True},
+             (("inst", "instruments"), ("notes", "note_levels"), ("zmask", "zero_mask")),
+             _midi_draws, _midi_spec, ops.DES_DRAWS_MIDI, "g2")
+WAV = Route("generated matrices", 5, {"threshold": 0.75, "norm_aux": True},
+            (("thr", "thr_mask"), ("inst", "instruments"), ("notes", "note_levels"), ("zmask", "zero_mask"),
+             ("aux", "aux")), _wav_draws, _wav_spec, ops.DES_DRAWS_WAV, "aux")
+
+
+def _routing(h, rows, src, cols):
+    """des_routing for the samples ``rows`` (a slice) of the scanned batch: src (n,dim) bool, cols (n,dim) int32 host
+    arrays -> (n,dim,dim) f64 on the device."""
     dev = h["g1"].device
-    return ops.des_routing(h["g1"][lo:hi], h["size"], h["dim"],
+    return ops.des_routing(h["g1"][rows], h["size"], h["dim"],
                            torch.from_numpy(np.ascontiguousarray(src, dtype=np.uint8)).to(dev),
-                           torch.from_numpy(np.ascontiguousarray(cols, dtype=np.int32)).to(dev)).cpu().numpy()
-
-
-def _batched_specs(h, draws, spec_of):
-    b, dim = h["b"], h["dim"]
-    src_all = np.zeros((b, dim), dtype=bool)
-    cols_all = np.empty((b, dim), dtype=np.int32)
-    seeds = []
-    for i in range(b):                                                   # global-RNG order of the reference, per sample
-        src_all[i], cols_all[i], sd = draws(h, i)
-        seeds.append(sd)
-    routing = _routing(h, 0, b, src_all, cols_all)
-    return [spec_of(h, i, routing[i], src_all[i], seeds[i]) for i in range(b)]
+                           torch.from_numpy(np.ascontiguousarray(cols, dtype=np.int32)).to(dev))
 
 
 # "des_batch" simulates on the device from this batch size on and with the host mirror below it.  The two give the same
@@ -191,80 +305,60 @@ def _batched_specs(h, draws, spec_of):
 DES_BATCH_DEVICE_MIN_B = 48
 
 
+def _per_sample(build, dtype):
+    """A BatchedPrologue array, built from the samples' DesSpecs when it is first read (``specs()`` needs none)."""
+    return cached_property(lambda self: np.ascontiguousarray([build(sp) for sp in self._heads], dtype=dtype))
+
+
 class BatchedPrologue:
     """What the batched prologue leaves, each product where its consumer needs it: ``routing`` (B,dim,dim) fp64 on the
     device; ``loc``, ``scale`` (B,dim) f64, ``queue_cap`` (B,dim) i32, ``seed``, ``customers`` (B) i64, ``instruments``,
     ``note_levels`` (B,dim) i32 on the host (built with the float32 arithmetic of ``_midi_spec`` / ``_wav_spec``);
-    ``states``: the B snapshots of ``np.random.get_state()`` taken right after each sample's reseed; ``h``: the scan."""
+    ``states``: the B snapshots of ``np.random.get_state()`` taken right after each sample's reseed; ``h``: the scan.
+    The consumers' surface is DevicePrologue's: ``simulate_on``, ``readback_words``, ``check``, ``check_rec_ptr``."""
+    check_rec_ptr = True                  # the log may come from the host mirror: the consumer checks its row pointers
 
-    def __init__(self, h, routing, src, seeds, states, spec_of):
-        self.h, self.routing, self.states = h, routing, states
-        self._src, self._seeds, self._spec_of = src, seeds, spec_of
-        heads = [spec_of(h, i, None, src[i], seeds[i]) for i in range(h["b"])]       # the per-node parameters
-        self.loc = np.ascontiguousarray([[float(d[1]) for d in sp.distributions] for sp in heads], dtype=np.float64)
-        self.scale = np.ascontiguousarray([[float(d[2]) for d in sp.distributions] for sp in heads], dtype=np.float64)
-        self.queue_cap = np.ascontiguousarray([sp.queue_list for sp in heads], dtype=np.int32)
-        self.seed = np.ascontiguousarray([int(np.asarray(sp.seeds).reshape(-1)[0]) for sp in heads], dtype=np.int64)
-        self.customers = np.ascontiguousarray([sp.num_customers for sp in heads], dtype=np.int64)
-        self.instruments = np.ascontiguousarray([[int(x) for x in sp.instruments] for sp in heads], dtype=np.int32)
-        self.note_levels = np.ascontiguousarray([[int(x) for x in sp.note_levels] for sp in heads], dtype=np.int32)
+    def __init__(self, route, h, routing, src, seeds, states, instrument=None):
+        self.route, self.h, self.routing, self.states = route, h, routing, states
+        self._src, self._seeds, self._instrument = src, seeds, instrument
+
+    def _spec(self, i, routing):
+        return self.route.spec(self.h, i, routing, self._src[i], self._seeds[i], self._instrument)
+
+    _heads = cached_property(lambda self: [self._spec(i, None) for i in range(self.h["b"])])   # the per-node parameters
+    loc = _per_sample(lambda sp: [float(d[1]) for d in sp.distributions], np.float64)
+    scale = _per_sample(lambda sp: [float(d[2]) for d in sp.distributions], np.float64)
+    queue_cap = _per_sample(lambda sp: sp.queue_list, np.int32)
+    seed = _per_sample(lambda sp: int(np.asarray(sp.seeds).reshape(-1)[0]), np.int64)
+    customers = _per_sample(lambda sp: sp.num_customers, np.int64)
+    instruments = _per_sample(lambda sp: [int(x) for x in sp.instruments], np.int32)
+    note_levels = _per_sample(lambda sp: [int(x) for x in sp.note_levels], np.int32)
 
     def specs(self):
         """The DesSpecs ``midi_prologue`` / ``wav_prologue`` return (downloads the routing matrices)."""
         routing = self.routing.cpu().numpy()
-        return [self._spec_of(self.h, i, routing[i], self._src[i], self._seeds[i]) for i in range(self.h["b"])]
+        return [self._spec(i, routing[i]) for i in range(self.h["b"])]
 
-    def simulate(self, device, max_events=200000, max_records=5001):
+    def simulate(self, device, max_events=200000, max_records=5001, min_device_b=0):
         """``gdm_des_run_batch`` (device: a HIP device) or the host mirror with portable math (device=None), every
         sample from its snapshot -> simulation_v3.BatchLog."""
         from . import simulation_v3
-        if device is None:
-            return simulation_v3.run_batch_host(self.routing.cpu().numpy(), self.loc, self.scale, self.queue_cap,
-                                                self.seed, self.customers, self.states, math=1, max_events=max_events,
-                                                max_records=max_records)
-        return simulation_v3.run_batch_device(self.routing, self.loc, self.scale, self.queue_cap, self.seed,
-                                              self.customers, self.states, device=device, max_events=max_events,
-                                              max_records=max_records, max_queue_cap=max(1, int(self.queue_cap.max())))
-
+        return simulation_v3.run_batch_auto(
+            self.routing, self.loc, self.scale, self.queue_cap, self.seed, self.customers, self.states, device=device,
+            min_device_b=min_device_b, max_events=max_events, max_records=max_records,
+            max_queue_cap=max(1, int(self.queue_cap.max())))
 
     def simulate_on(self, device, max_events=200000, max_records=5001):
         """``simulate`` for the bridges: a BatchLog of tensors on ``device`` either way -- from the kernel when the batch
         holds at least DES_BATCH_DEVICE_MIN_B samples, else from the host mirror (same bits), uploaded once."""
-        from . import simulation_v3
-        if self.h["b"] >= DES_BATCH_DEVICE_MIN_B:
-            return self.simulate(device, max_events=max_events, max_records=max_records)
-        host = self.simulate(None, max_events=max_events, max_records=max_records)
-        dev = torch.device(device)
-        fields = [torch.from_numpy(np.ascontiguousarray(a.view(np.int32) if a.dtype == np.uint32 else a)).to(dev)
-                  for a in host]
-        return simulation_v3.BatchLog(*fields)
+        return self.simulate(device, max_events, max_records, min_device_b=DES_BATCH_DEVICE_MIN_B)
 
+    def readback_words(self):
+        """Nothing of the prologue is left to read back: the host draws raised what there was to raise."""
+        return {}
 
-def _batched_prologue(h, draws, spec_of):
-    b, dim = h["b"], h["dim"]
-    src_all = np.zeros((b, dim), dtype=bool)
-    cols_all = np.empty((b, dim), dtype=np.int32)
-    seeds, states = [], []
-    for i in range(b):                                                   # global-RNG order of the reference, per sample
-        src_all[i], cols_all[i], sd = draws(h, i)
-        seeds.append(sd)
-        states.append(np.random.get_state())                             # where simulation i starts
-    dev = h["g1"].device
-    routing = ops.des_routing(h["g1"], h["size"], dim, torch.from_numpy(src_all.astype(np.uint8)).to(dev),
-                              torch.from_numpy(cols_all).to(dev))
-    return BatchedPrologue(h, routing, src_all, seeds, states, spec_of)
-
-
-def batched_prologue_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None):
-    """``midi_prologue`` with its products left where "des_batch" needs them -> BatchedPrologue."""
-    h = _midi_scan(gen1_output, gen2_output, adj_size)
-    return _batched_prologue(h, _midi_draws, lambda h_, i, r, src, sd: _midi_spec(h_, i, r, src, sd, instrument))
-
-
-def batched_prologue_wav(matrices, size=20, use_same_instrument=None):
-    """``wav_prologue`` with its products left where "des_batch" needs them -> BatchedPrologue."""
-    h = _wav_scan(matrices, size)
-    return _batched_prologue(h, _wav_draws, lambda h_, i, r, src, sd: _wav_spec(h_, i, r, src, sd, use_same_instrument))
+    def check(self, words, raise_draws=True):
+        return ()
 
 
 # ---- "des_device": the draws and parameters on the device, one stream per sample --------------------------------------
@@ -325,7 +419,8 @@ class DevicePrologue:
     ``instruments``, ``note_levels`` (B,dim) i32, ``states`` = (mt_key (B,624) i32, mt_pos, has_gauss (B) i32, gauss (B)
     f64): every sample's stream after its last draw; plus ``src`` (B,dim) u8, ``cols`` (B,dim) i32, ``status`` (B) i32
     (``ops.DES_DRAWS_ERRORS``), ``flags`` (B) i32 of the scan and ``base`` (B,) uint32 on the host.  Nothing was read
-    back: ``status`` and ``flags`` travel with the consumer's one read-back (``readback_words`` / ``raise_for``)."""
+    back: ``status`` and ``flags`` travel with the consumer's one read-back (``readback_words`` / ``check``)."""
+    check_rec_ptr = False                 # the log comes from the kernel, and checking would need a read-back
 
     def __init__(self, h, base, draws, routing):
         self.h, self.base, self.routing = h, base, routing
@@ -342,81 +437,58 @@ class DevicePrologue:
                                               self.customers, self.states, device=device, max_events=max_events,
                                               max_records=max_records, max_queue_cap=DES_DEVICE_QUEUE_CAP)
 
-    simulate = simulate_on
-
     def readback_words(self):
-        """int32 device tensors to append to the consumer's read-back: draw status, scan flags."""
-        return [self.status, self.flags]
+        """int32 device tensors to add to the consumer's read-back, by name: draw status, scan flags."""
+        return {"draw_status": self.status, "flags": self.flags}
 
-    @staticmethod
-    def check_flags(flags):
-        _check_finite(np.asarray(flags))
-
-    @staticmethod
-    def raise_for(status):
-        """Raise what the reference raises for the first sample with a draw status."""
-        for i in np.flatnonzero(np.asarray(status)):
-            raise draws_error(status[i])
+    def check(self, words, raise_draws=True):
+        """After the read-back: ValueError for a non-finite generated matrix, then (``raise_draws``) what the
+        reference raises for the first sample with a draw status.  -> the draw status words (B,)."""
+        _check_finite(words["flags"])
+        for i in np.flatnonzero(words["draw_status"]) if raise_draws else ():
+            raise draws_error(words["draw_status"][i])
+        return words["draw_status"]
 
 
-def _device_prologue(route, h, scan, params, override, base):
-    b, dim, dev = h["b"], h["dim"], h["g1"].device
-    if dim > ops.DES_DRAWS_MAX_DIM:
-        raise ops.GdmError(f"des_device: at most {ops.DES_DRAWS_MAX_DIM} nodes (a row's candidates are one 64-bit word)")
-    base = draw_base_seeds(b) if base is None else np.ascontiguousarray(base, dtype=np.uint32).reshape(b)
-    base_dev = torch.from_numpy(base.view(np.int32)).to(dev)
-    over = None if override is None else torch.from_numpy(override).to(dev)
-    draws = ops.des_draws(route, h["size"], dim, base_dev, scan, params, over)
-    routing = ops.des_routing(h["g1"], h["size"], dim, draws["src"], draws["cols"])
-    h["flags"] = scan["flags"]
-    return DevicePrologue(h, base, draws, routing)
+def _read_back(tensors):
+    """name -> integer device tensor, in order -> name -> int32 numpy view of the same shape: ONE transfer for all."""
+    host = torch.cat([t.reshape(-1).to(torch.int32) for t in tensors.values()]).cpu().numpy()
+    ends = np.cumsum([t.numel() for t in tensors.values()])
+    return {name: host[end - t.numel():end].reshape(tuple(t.shape)) for (name, t), end in zip(tensors.items(), ends)}
+
+
+def batched_prologue_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None):
+    """``midi_prologue`` with its products left where "des_batch" needs them -> BatchedPrologue."""
+    return MIDI.prologue("des_batch", gen1_output, adj_size[0], gen2_output, instrument)
+
+
+def batched_prologue_wav(matrices, size=20, use_same_instrument=None):
+    """``wav_prologue`` with its products left where "des_batch" needs them -> BatchedPrologue."""
+    return WAV.prologue("des_batch", matrices, size, None, use_same_instrument)
 
 
 def device_prologue_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None, *, base=None):
     """The MIDI route's prologue entirely on the device: scan, ``ops.des_draws`` (sample i on the stream
     ``RandomState(base[i])``; base=None: ``draw_base_seeds``, the one call on numpy's global stream), routing.  No host
     synchronisation, nothing read back -> DevicePrologue."""
-    size = adj_size[0]
-    dim = size - 3
-    g1 = gen1_output.detach()
-    if not g1.is_cuda:
-        raise ops.GdmError("matrix_sim_process runs the prologue on a HIP device; move the generator outputs there")
-    g1 = g1.float()
-    g2 = gen2_output.detach().to(device=g1.device, dtype=torch.float32).contiguous()
-    if g2.dim() != 2 or g2.shape[0] != g1.shape[0] or g2.shape[1] < 7:
-        raise ops.GdmError("des_device: gen2_output must be (B, n) with n >= 7 (columns 1..6 drive the simulator)")
-    scan = ops.des_scan(g1, size, dim, note_mod=True)
-    h = {"g1": g1, "size": size, "dim": dim, "b": g1.shape[0], "g2": g2}
-    return _device_prologue(ops.DES_DRAWS_MIDI, h, scan, g2, _instrument_override(instrument, g1.shape[0]), base)
+    return MIDI.device(MIDI.scan(gen1_output, adj_size[0], gen2_output, download=False), instrument, base)
 
 
 def device_prologue_wav(matrices, size=20, use_same_instrument=None, *, base=None):
     """The wav route's prologue entirely on the device (see ``device_prologue_midi``) -> DevicePrologue."""
-    dim = size - 5
-    m = matrices.detach() if isinstance(matrices, torch.Tensor) else torch.as_tensor(np.asarray(matrices))
-    if not m.is_cuda:
-        raise ops.GdmError("matrix_sim_process runs the prologue on a HIP device; move the generated matrices there")
-    m = m.float()
-    scan = ops.des_scan(m, size, dim, threshold=0.75, norm_aux=True)
-    h = {"g1": m, "size": size, "dim": dim, "b": m.shape[0]}
-    return _device_prologue(ops.DES_DRAWS_WAV, h, scan, scan["aux"],
-                            _instrument_override(use_same_instrument, m.shape[0]), base)
-
-
-def _interleaved_specs(h, draws, spec_of):
-    """The reference's order: a sample's spec is complete (and handed to the caller, who simulates) before the next
-    sample draws anything."""
-    for i in range(h["b"]):
-        src, cols, sd = draws(h, i)
-        routing = _routing(h, i, i + 1, src[None], cols[None])[0]
-        yield spec_of(h, i, routing, src, sd)
+    return WAV.device(WAV.scan(matrices, size, download=False), use_same_instrument, base)
 
 
 def midi_prologue(gen1_output, gen2_output, adj_size=(32, 32), instrument=None):
     """Device-batched head of matrix_to_midi: gen1_output (B,1,S,S), gen2_output (B,n2) device tensors -> [DesSpec].
     All draws are made before the first spec is returned (see the module docstring)."""
-    h = _midi_scan(gen1_output, gen2_output, adj_size)
-    return _batched_specs(h, _midi_draws, lambda h_, i, r, src, sd: _midi_spec(h_, i, r, src, sd, instrument))
+    return batched_prologue_midi(gen1_output, gen2_output, adj_size, instrument).specs()
+
+
+def wav_prologue(matrices, size=20, use_same_instrument=None):
+    """Device-batched head of matrix_to_wav: matrices (B,size,size) device tensor -> [DesSpec].  All draws are made
+    before the first spec is returned (see the module docstring)."""
+    return batched_prologue_wav(matrices, size, use_same_instrument).specs()
 
 
 def matrix_to_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None, start=0, end=150, count=0,
@@ -451,21 +523,18 @@ def matrix_to_midi(gen1_output, gen2_output, adj_size=(32, 32), instrument=None,
                            "simulate=callable (it receives the DesSpec the reference would construct Sim from)")
     start, end = int(start), int(end)
     if isinstance(simulate, str):
-        if simulate not in ("des", "des_batch", "des_device"):
-            raise ops.GdmError(f"matrix_to_midi: unknown back end {simulate!r} (the built-in ones are \"des\", "
-                               "\"des_batch\" and \"des_device\")")
+        check_back_end(simulate, "matrix_to_midi: unknown back end")
         if simulate == "des":
             return _matrix_to_midi_des(gen1_output, gen2_output, adj_size, instrument, start, end, generate,
                                        return_tensor, midi_path, max_events)
-        return _matrix_to_midi_des_batch(gen1_output, gen2_output, adj_size, instrument, start, end, generate,
-                                         return_tensor, midi_path, max_events, device_draws=simulate == "des_device")
+        return _matrix_to_midi_des_batch(simulate, gen1_output, gen2_output, adj_size, instrument, start, end, generate,
+                                         return_tensor, midi_path, max_events)
     if return_tensor:
         raise ops.GdmError("matrix_to_midi: return_tensor needs the built-in back end (simulate=\"des\")")
-    h = _midi_scan(gen1_output, gen2_output, adj_size)
+    h = MIDI.scan(gen1_output, adj_size[0], gen2_output)
     g2 = h["g2"]
     midi_rolls, failed = [], 0
-    specs = _interleaved_specs(h, _midi_draws, lambda h_, i, r, src, sd: _midi_spec(h_, i, r, src, sd, instrument))
-    for index, spec in enumerate(specs):
+    for index, spec in enumerate(MIDI.specs(h, instrument)):
         this_count = count if index == 0 else 1
         output = np.zeros((2, 128, end - start))
         res = simulate(spec, count=this_count, start=start, end=end, generate=generate, gen2_tail=g2[index][10:])
@@ -482,12 +551,9 @@ def _des_run(gen1_output, gen2_output, adj_size, instrument, start, end, generat
     (B,), reasons (None or why the simulation failed), ok, save)."""
     from . import sim_log_to_midi, simulation_v3
     _check_midi_window(start, end)
-    h = _midi_scan(gen1_output, gen2_output, adj_size)
-    if h["g2"].shape[1] < 16:
-        raise ops.GdmError("matrix_to_midi: gen2_output needs at least 16 columns (gen2_output[10:16] drive the MIDI)")
-    specs = _interleaved_specs(h, _midi_draws, lambda h_, i, r, src, sd: _midi_spec(h_, i, r, src, sd, instrument))
+    h = MIDI.scan(gen1_output, adj_size[0], gen2_output, tail=True)
     logs, ok, insts, notes, reasons = [], [], [], [], []
-    for spec in specs:
+    for spec in MIDI.specs(h, instrument):
         try:
             log, _reason = simulation_v3.run_spec(spec, max_events=max_events)
             ok.append(True)
@@ -536,50 +602,35 @@ def _on(a, dev):
     return a.contiguous() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
-def _des_batch_run(gen1_output, gen2_output, adj_size, instrument, start, end, generate, max_events,
-                   device_draws=False):
-    """The body "des_batch" and "des_device" share between ``matrix_to_midi`` and ``matrix_to_midis``: batched (or
-    device) prologue, simulator, one ``des_log_to_roll`` launch, ONE read-back -> (planes (B,2,128,W) on the device;
-    status, track_len, good, save, stop (B,) and tracks (B, cap, 4) int32 host arrays; draw status (B,) or None)."""
+def _des_batch_run(simulate, gen1_output, gen2_output, adj_size, instrument, start, end, generate, max_events,
+                   raise_draws=True):
+    """The body "des_batch" and "des_device" share between ``matrix_to_midi`` and ``matrix_to_midis``: batched or
+    device prologue, simulator, one ``des_log_to_roll`` launch, ONE read-back -> (planes (B,2,128,W) on the device;
+    the words read back, int32 host arrays by name: status, track_len, good, save, stop (B,) and tracks (B, cap, 4);
+    the draw status words ``pro.check`` returns)."""
     from . import sim_log_to_midi
     _check_midi_window(start, end)
-    if device_draws and gen2_output.shape[1] < 16:
-        raise ops.GdmError("matrix_to_midi: gen2_output needs at least 16 columns (gen2_output[10:16] drive the MIDI)")
-    pro = (device_prologue_midi if device_draws else batched_prologue_midi)(gen1_output, gen2_output, adj_size,
-                                                                              instrument)
-    h = pro.h
-    if h["g2"].shape[1] < 16:
-        raise ops.GdmError("matrix_to_midi: gen2_output needs at least 16 columns (gen2_output[10:16] drive the MIDI)")
-    dev = h["g1"].device
+    pro = MIDI.prologue(simulate, gen1_output, adj_size[0], gen2_output, instrument, tail=True)
+    dev = pro.h["g1"].device
     log = pro.simulate_on(dev, max_events=max_events, max_records=sim_log_to_midi.MAX_LINES + 1)
     good = (log.stop_reason != ops.DES_STOP_ERROR) & (log.stop_reason != ops.DES_STOP_BUDGET)
     lines = torch.clamp(log.n_records, max=sim_log_to_midi.MAX_LINES + 1)             # lines_read, on the device
     save = (good & ((lines % 100 == 0) | bool(generate))).to(torch.int32)
-    tails = _on(h["g2"][:, 10:], dev)
     planes, track, track_len, status = ops.des_log_to_roll(
-        log.value, log.event_id, log.node, log.kind, log.rec_ptr, tails, _on(pro.instruments, dev),
-        _on(pro.note_levels, dev), save, start, end, check_rec_ptr=not device_draws)
+        log.value, log.event_id, log.node, log.kind, log.rec_ptr, _on(pro.h["g2"][:, 10:], dev),
+        _on(pro.instruments, dev), _on(pro.note_levels, dev), save, start, end, check_rec_ptr=pro.check_rec_ptr)
     # the one read-back: stop reasons (and the device prologue's status words) with the tracks
-    extra = pro.readback_words() if device_draws else []
-    words = torch.cat([status, track_len, good.to(torch.int32), save, log.stop_reason.to(torch.int32), *extra,
-                       track.reshape(-1)]).cpu().numpy()
-    b = h["b"]
-    status, track_len, good, save, stop = (words[k * b:(k + 1) * b] for k in range(5))
-    draw_status = None
-    if device_draws:
-        draw_status = words[5 * b:6 * b]
-        pro.check_flags(words[6 * b:7 * b])
-    tracks = words[(5 + len(extra)) * b:].reshape(b, ops.DES_MIDI_TRACK_CAP, 4)
-    return planes, status, track_len, good, save, stop, tracks, draw_status
+    words = _read_back({"status": status, "track_len": track_len, "good": good, "save": save, "stop": log.stop_reason,
+                        **pro.readback_words(), "tracks": track})
+    return planes, words, pro.check(words, raise_draws)
 
 
-def _matrix_to_midi_des_batch(gen1_output, gen2_output, adj_size, instrument, start, end, generate, return_tensor,
-                              midi_path, max_events, device_draws=False):
+def _matrix_to_midi_des_batch(simulate, gen1_output, gen2_output, adj_size, instrument, start, end, generate,
+                              return_tensor, midi_path, max_events):
     from . import sim_log_to_midi
-    planes, status, track_len, good, save, _stop, tracks, draw_status = _des_batch_run(
-        gen1_output, gen2_output, adj_size, instrument, start, end, generate, max_events, device_draws)
-    if draw_status is not None:
-        DevicePrologue.raise_for(draw_status)
+    planes, words, _draw_status = _des_batch_run(simulate, gen1_output, gen2_output, adj_size, instrument, start, end,
+                                                 generate, max_events)
+    status, track_len, good, save, tracks = (words[k] for k in ("status", "track_len", "good", "save", "tracks"))
     b = len(status)
     for i in range(b):
         if status[i] >> 8:
@@ -620,18 +671,17 @@ def matrix_to_midis(gen1_output, gen2_output, adj_size, instrument, start, end, 
     zero roll, no track, no file, its reason in ``reasons`` -- and nothing is raised for it.  -> MidiBatch."""
     from . import sim_log_to_midi, simulation_v3
     start, end = int(start), int(end)
-    if simulate not in ("des", "des_batch", "des_device"):
-        raise ops.GdmError(f"matrix_to_midis: unknown back end {simulate!r} (the built-in ones are \"des\", "
-                           "\"des_batch\" and \"des_device\")")
+    check_back_end(simulate, "matrix_to_midis: unknown back end")
     b = gen1_output.shape[0]
     if midi_paths is not None and len(midi_paths) != b:
         raise ops.GdmError(f"matrix_to_midis: {len(midi_paths)} midi_paths for {b} samples")
-    if simulate in ("des_batch", "des_device"):
-        planes, status, track_len, good, _save, stop, track, draw_status = _des_batch_run(
-            gen1_output, gen2_output, adj_size, instrument, start, end, True, max_events, simulate == "des_device")
-        tracks = [track[i, :track_len[i]].copy() for i in range(b)]
-        reasons = [None if good[i] else simulation_v3.STOP_REASONS[int(stop[i])] for i in range(b)]
-        for i in np.flatnonzero(draw_status if draw_status is not None else []):
+    if simulate != "des":
+        planes, words, draw_status = _des_batch_run(simulate, gen1_output, gen2_output, adj_size, instrument, start, end,
+                                                    True, max_events, raise_draws=False)
+        status = words["status"]
+        tracks = [words["tracks"][i, :words["track_len"][i]].copy() for i in range(b)]
+        reasons = [None if words["good"][i] else simulation_v3.STOP_REASONS[int(words["stop"][i])] for i in range(b)]
+        for i in np.flatnonzero(draw_status):
             reasons[i] = f"error ({draws_error(draw_status[i])})"
     else:
         planes, tracks, status, reasons = _des_run(gen1_output, gen2_output, adj_size, instrument, start, end, True,
@@ -649,80 +699,21 @@ def matrix_to_midis(gen1_output, gen2_output, adj_size, instrument, start, end, 
 
 
 def _batch_to_mel(pro, max_events):
-    """The built-in batched back end behind matrix_to_wav: BatchedPrologue -> ((B, 128, 216) dB device tensor, (notes,
+    """The built-in batched back ends behind matrix_to_wav: Batched- or DevicePrologue -> ((B, 128, 216) dB device tensor, (notes,
     n_notes, clip_len) device tensors).  Simulator, log -> notes, synth and mel are enqueued without a read-back in
     between; the status words and stop reasons come back once, and a sample the reference would raise for raises."""
-    from . import sim_log_process_music, util
+    from . import sim_log_process_music, simulation_v3, util
     dev = pro.h["g1"].device
     log = pro.simulate_on(dev, max_events=max_events, max_records=sim_log_process_music.MAX_LINES + 1)
     notes, n_notes, clip_len, status = ops.des_log_to_notes(log.value, log.event_id, log.node, log.kind, log.rec_ptr,
-                                                            _on(pro.note_levels, dev),
-                                                            check_rec_ptr=not isinstance(pro, DevicePrologue))
+                                                            _on(pro.note_levels, dev), check_rec_ptr=pro.check_rec_ptr)
     frames = ops.synth_frames(notes, n_notes, clip_len)
     mel = util._db_from_frames(frames, pro.h["b"], ops.SYNTH_FRAMES, ops.SYNTH_RATE, ops.SYNTH_NFFT, 128, 20, 8300, 80)
-    extra = pro.readback_words() if isinstance(pro, DevicePrologue) else []
-    words = torch.stack([status, log.stop_reason, *extra]).cpu()
-    if extra:                                    # the device prologue's own errors come first, as in the reference
-        pro.check_flags(words[3].numpy())
-        pro.raise_for(words[2].numpy())
-    for i, reason in enumerate(words[1].tolist()):
-        if reason in (ops.DES_STOP_ERROR, ops.DES_STOP_BUDGET):
-            from . import simulation_v3
-            raise ValueError(f"matrix_to_wav: the simulation of sample {i} stopped with "
-                             f"{simulation_v3.STOP_REASONS[reason]!r} (a node without destination, a customer routed "
-                             "to a source, or a service distribution that never turns positive; the reference raises "
-                             "or never returns)")
-    sim_log_process_music.raise_for_status(words[0])
+    words = _read_back({"status": status, "stop": log.stop_reason, **pro.readback_words()})
+    pro.check(words)                             # the device prologue's own errors come first, as in the reference
+    simulation_v3.raise_for_stop(words["stop"], "matrix_to_wav", "sample")
+    sim_log_process_music.raise_for_status(torch.from_numpy(words["status"]))
     return mel, (notes, n_notes, clip_len)
-
-
-def _wav_scan(matrices, size):
-    dim = size - 5
-    m = matrices.detach() if isinstance(matrices, torch.Tensor) else torch.as_tensor(np.asarray(matrices))
-    if not m.is_cuda:
-        raise ops.GdmError("matrix_sim_process runs the prologue on a HIP device; move the generated matrices there")
-    m = m.float()
-    scan = ops.des_scan(m, size, dim, threshold=0.75, norm_aux=True)
-    h = {"g1": m, "size": size, "dim": dim, "b": m.shape[0], "thr": scan["thr_mask"].cpu().numpy().astype(bool),
-         "inst": scan["instruments"].cpu().numpy(), "notes": scan["note_levels"].cpu().numpy(),
-         "zmask": scan["zero_mask"].cpu().numpy(), "aux": scan["aux"].cpu().numpy()}
-    _check_finite(scan["flags"].cpu().numpy())
-    return h
-
-
-def _wav_draws(h, i):
-    dim, size = h["dim"], h["size"]
-    hit = np.flatnonzero(h["thr"][i])
-    if len(hit) == 0:
-        sources = np.random.choice(dim, size=size // 8, replace=False)     # line 27
-    elif len(hit) == 1:
-        sources = hit
-    else:
-        raise ValueError("The truth value of an array with more than one element is ambiguous (matrix_to_wav keeps "
-                         "np.where's tuple: more than one thresholded source cannot be processed, line 30)")
-    if sources.max() >= dim:
-        raise IndexError(f"index {int(sources.max())} is out of bounds for axis 1 with size {dim}")   # line 67
-    src = np.zeros(dim, dtype=bool)
-    src[sources] = True
-    cols = _draw_residue_columns(h["zmask"][i], src, dim)
-    return src, cols, _reseed()
-
-
-def _wav_spec(h, i, routing, src, seeds, use_same_instrument):
-    dim = h["dim"]
-    r3, r4 = h["aux"][i, 0], h["aux"][i, 1]
-    dist = [["normal", 30 * r3[k], 15 * r4[k]] if src[k] else ["normal", 5 * r3[k], 3 * r4[k]] for k in range(dim)]
-    instruments = h["inst"][i].astype(np.float64) if use_same_instrument is None else \
-        np.array([use_same_instrument] * dim)
-    return DesSpec(routing, dist, [2 * 127] * dim, seeds, 1000, 0.5, instruments, h["notes"][i].astype(np.float64),
-                   np.flatnonzero(src))
-
-
-def wav_prologue(matrices, size=20, use_same_instrument=None):
-    """Device-batched head of matrix_to_wav: matrices (B,size,size) device tensor -> [DesSpec].  All draws are made
-    before the first spec is returned (see the module docstring)."""
-    h = _wav_scan(matrices, size)
-    return _batched_specs(h, _wav_draws, lambda h_, i, r, src, sd: _wav_spec(h_, i, r, src, sd, use_same_instrument))
 
 
 def matrix_to_wav(matrices, size=20, use_same_instrument=None, start=0, end=174, device="cpu", simulate=None, *,
@@ -747,20 +738,23 @@ def matrix_to_wav(matrices, size=20, use_same_instrument=None, start=0, end=174,
     if simulate is None:
         raise ops.GdmError("matrix_to_wav: pass simulate=\"des\" for the built-in DES / synth back end or "
                            "simulate=callable (it receives the DesSpec the reference would construct Sim from)")
-    if isinstance(simulate, str) and simulate in ("des_batch", "des_device"):
-        prologue = batched_prologue_wav if simulate == "des_batch" else device_prologue_wav
-        mel, _notes = _batch_to_mel(prologue(matrices, size, use_same_instrument), max_events)
-        return mel[:, :, start:end].to(device)
-    h = _wav_scan(matrices, size)
-    specs = _interleaved_specs(h, _wav_draws, lambda h_, i, r, src, sd: _wav_spec(h_, i, r, src, sd, use_same_instrument))
     if isinstance(simulate, str):
-        if simulate != "des":
-            raise ops.GdmError(f"matrix_to_wav: unknown back end {simulate!r} (the built-in ones are \"des\", "
-                               "\"des_batch\" and \"des_device\")")
-        mel, _notes = _specs_to_mel(specs, h["g1"].device, max_events)
+        mel, _notes = matrices_to_mel(matrices, size, use_same_instrument, simulate=simulate, max_events=max_events)
         return mel[:, :, start:end].to(device)
+    specs = WAV.specs(WAV.scan(matrices, size), use_same_instrument)
     spectrograms = [torch.as_tensor(simulate(spec, index=i)) for i, spec in enumerate(specs)]
     return torch.stack([s[:, start:end] for s in spectrograms]).to(device)
+
+
+def matrices_to_mel(matrices, size=20, use_same_instrument=None, *, simulate, max_events=200000):
+    """``matrix_to_wav`` with a built-in back end, before its ``[start:end]`` cut and keeping the note lists (what the
+    MIDI and WAV files of a clip are written from): -> (mel (B, 128, 216) dB on the matrices' device, (notes, n_notes,
+    clip_len) device tensors)."""
+    check_back_end(simulate, "matrix_to_wav: unknown back end")
+    if simulate != "des":
+        return _batch_to_mel(WAV.prologue(simulate, matrices, size, None, use_same_instrument), max_events)
+    h = WAV.scan(matrices, size)
+    return _specs_to_mel(WAV.specs(h, use_same_instrument), h["g1"].device, max_events)
 
 
 def _specs_to_mel(specs, dev, max_events):

@@ -33,6 +33,7 @@ from torch import nn
 
 from . import functional as Fn
 from . import synthetic
+from .matrix_sim_process import BACK_ENDS, check_back_end, matrix_to_midi, matrix_to_midis
 
 
 def get_noise(n_samples, noise_dim, device="cpu"):
@@ -201,7 +202,6 @@ def des_fake_provider(adj_size, instrument, start, end, generate=False, midi_pat
     the DES core and the batched log -> MIDI -> piano-roll kernel behind it; the rolls stay on the device.
     batched: simulate all samples in one device launch (matrix_to_midi(simulate="des_batch")); a back end's name
     ("des_batch", "des_device") selects that one."""
-    from .matrix_sim_process import matrix_to_midi
     simulate = batched if isinstance(batched, str) else ("des_batch" if batched else "des")
 
     def provider(gen_output1, gen_output2, count):
@@ -228,9 +228,7 @@ class MultiModalGAN(nn.Module):
         self.midi_path = midi_path          # where generate_midi's built-in bridge writes (default: upstream's path)
         self.generate_provider = None
         if isinstance(fake_provider, str):
-            if fake_provider not in ("des", "des_batch", "des_device"):
-                raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridges are \"des\", "
-                                 "\"des_batch\" and \"des_device\")")
+            check_back_end(fake_provider, "unknown fake_provider", ValueError)
             batched = fake_provider
             fake_provider = des_fake_provider(adj_size, instrument, start, end, batched=batched)
             self.generate_provider = des_fake_provider(adj_size, instrument, start, end, generate=True,
@@ -318,7 +316,6 @@ class MultiModalGAN(nn.Module):
         ``fake_provider`` the module was built with: bridge names the built-in one, "des", "des_batch" or
         "des_device".
         Returns the MidiBatch (rolls, tracks, ok, reasons) with ``paths``: None where ``ok`` is false."""
-        from .matrix_sim_process import matrix_to_midis
         out1, out2 = self.sample(n_samples, noise1=noise1, noise2=noise2, input_tensor=input_tensor,
                                  compute_dtype=compute_dtype)
         paths = [os.path.join(out_dir, name.format(i)) for i in range(out1.shape[0])]
@@ -371,9 +368,7 @@ def training_loop(batch_size=16, *, num_epochs=100, train_loader=None, steps_per
     roll_size = (2, 128, sequence_length)
     start = 100
     if isinstance(fake_provider, str):
-        if fake_provider not in ("des", "des_batch", "des_device"):
-            raise ValueError(f"unknown fake_provider {fake_provider!r} (the built-in bridges are \"des\", "
-                             "\"des_batch\" and \"des_device\")")
+        check_back_end(fake_provider, "unknown fake_provider", ValueError)
         fake_provider = des_fake_provider(adj_size, 0, start, start + sequence_length, batched=fake_provider)
     mmgan = MultiModalGAN(z_dim=noise_dim, adj_size=adj_size, roll_size=roll_size, input_dim=max_beat_length,
                           output_dim=gen2_output_dim, instrument=0, start=start, end=start + sequence_length,
@@ -481,7 +476,7 @@ def generate_main(argv):
     ap.add_argument("--start", type=int, default=100)
     ap.add_argument("--end", type=int, default=150)
     ap.add_argument("--seed", type=int, default=None)
-    ap.add_argument("--bridge", choices=("des", "des_batch", "des_device"), default="des_batch")
+    ap.add_argument("--bridge", choices=BACK_ENDS, default="des_batch")
     a = ap.parse_args(argv)
     if a.generate < 1:
         ap.error("--generate needs N >= 1")
@@ -518,7 +513,7 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--sequence-length", type=int, default=50)
     ap.add_argument("--sample-size", type=int, default=300)
-    ap.add_argument("--fake-provider", choices=("des", "des_batch", "des_device"), default=None,
+    ap.add_argument("--fake-provider", choices=BACK_ENDS, default=None,
                     help="des: the built-in DES bridge; des_batch: the same with the simulation batched on the "
                          "device; des_device: the draws on the device too; default: synthetic fake rolls")
     ap.add_argument("--save-dir", default=None)

@@ -55,13 +55,12 @@ import os
 import numpy as np
 import torch
 
-from . import ops, sim_log_process_music, sim_log_to_midi, simulation_v3, util
+from . import matrix_sim_process as msp, ops, sim_log_process_music, sim_log_to_midi, simulation_v3, util
+from .matrix_sim_process import BACK_ENDS, check_back_end
 
 NUM_AUG = 5
 QUEUE_CAPACITY = 127
 NUMBER_OF_CUSTOMERS = 1000
-BACK_ENDS = ("des", "des_batch", "des_device")
-_WAV_CHUNK = 1 << 22          # samples rendered per gdm_synth_windows_gm launch (8 MB of PCM)
 
 
 class SimWavBatch:
@@ -155,45 +154,23 @@ def batch_draws(matrices, size, base):
 
 def _simulate_batch(matrices, size, use_same_instrument, max_events, dev):
     """"des_batch" -> (simulation_v3.BatchLog of device tensors, instruments, note_levels (B, dim) i32 device)."""
-    from . import matrix_sim_process as msp
-    b, dim = len(matrices), size - NUM_AUG
+    b = len(matrices)
     base = np.random.randint(0, 2 ** 32, size=b)
     ms, seed, states = batch_draws(matrices, size, base)
     pro = ops.s2w_prologue(torch.from_numpy(ms).to(dev), _override(use_same_instrument, b, dev))
     _refuse(pro["status"].cpu())
     customers = np.full(b, NUMBER_OF_CUSTOMERS, dtype=np.int64)
-    max_records = sim_log_to_midi.MAX_LINES + 1
-    if dim <= ops.DES_BATCH_MAX_DIM and b >= msp.DES_BATCH_DEVICE_MIN_B:
-        log = simulation_v3.run_batch_device(pro["adj"], pro["loc"], pro["scale"], pro["queue_cap"], seed, customers,
-                                             states, device=dev, max_events=max_events, max_records=max_records,
-                                             max_queue_cap=QUEUE_CAPACITY)
-    else:
-        host = simulation_v3.run_batch_host(pro["adj"].cpu().numpy(), pro["loc"].cpu().numpy(),
-                                            pro["scale"].cpu().numpy(), pro["queue_cap"].cpu().numpy(), seed, customers,
-                                            states, math=1, max_events=max_events, max_records=max_records)
-        log = simulation_v3.BatchLog(*(torch.from_numpy(np.ascontiguousarray(
-            a.view(np.int32) if a.dtype == np.uint32 else a)).to(dev) for a in host))
-    stop = log.stop_reason.cpu().tolist()
-    for i, reason in enumerate(stop):
-        if reason in (ops.DES_STOP_ERROR, ops.DES_STOP_BUDGET):
-            raise ValueError(f"sim_to_wav: the simulation of matrix {i} stopped with "
-                             f"{simulation_v3.STOP_REASONS[reason]!r}")
+    log = simulation_v3.run_batch_auto(pro["adj"], pro["loc"], pro["scale"], pro["queue_cap"], seed, customers, states,
+                                       device=dev, min_device_b=msp.DES_BATCH_DEVICE_MIN_B, max_events=max_events,
+                                       max_records=sim_log_to_midi.MAX_LINES + 1, max_queue_cap=QUEUE_CAPACITY)
+    simulation_v3.raise_for_stop(log.stop_reason.cpu(), "sim_to_wav", "matrix")
     return log, pro["instruments"], pro["note_levels"]
 
 
 def _render(rows, count, total, wav_path, max_seconds, dev):
-    """Clip ``rows`` ((count, 5) device rows in ticks) as a mono 16-bit 44 100 Hz WAV file of ``total`` samples."""
-    blank = count == 0
-    if blank:
-        total = 5 * ops.SYNTH_RATE                                   # datasets.midi_notes: a file without notes
-    if max_seconds is not None:
-        total = max(1, min(total, int(max_seconds * ops.SYNTH_RATE)))
-    os.makedirs(os.path.dirname(wav_path) or ".", exist_ok=True)
-    with open(wav_path, "wb") as f:
-        f.write(util.wav_header(total, ops.SYNTH_RATE))
-        if blank:
-            f.write(bytes(2 * total))
-            return total
+    """Clip ``rows`` ((count, 5) device rows in ticks) as a mono 16-bit 44 100 Hz WAV file of ``total`` samples; a clip
+    without notes is the blank one ``datasets.midi_notes`` defines for such a file."""
+    if count:
         mul, div = ops.tick_rule()
         notes = rows.clone()
         notes[:, :2] = torch.div(notes[:, :2] * mul, div, rounding_mode="floor")        # ticks -> samples, exact
@@ -201,20 +178,17 @@ def _render(rows, count, total, wav_path, max_seconds, dev):
         end_max = torch.cummax(notes[:, 1] + release[(notes[:, 4] & 127) >> 3], dim=0).values.contiguous()
         note_ptr = torch.tensor([0, count], dtype=torch.int64, device=dev)
         win_clip = torch.zeros(1, dtype=torch.int32, device=dev)
-        for first in range(0, total, _WAV_CHUNK):
-            chunk = min(_WAV_CHUNK, total - first)
-            start = torch.full((1,), first, dtype=torch.int64, device=dev)
-            pcm = ops.synth_windows_gm(notes, end_max, note_ptr, win_clip, start, chunk)
-            f.write(pcm[0, :chunk].cpu().numpy().astype("<i2").tobytes())
-    return total
+
+    def render(first, chunk):
+        start = torch.full((1,), first, dtype=torch.int64, device=dev)
+        return ops.synth_windows_gm(notes, end_max, note_ptr, win_clip, start, chunk)[0, :chunk]
+    return util.write_wav_chunks(wav_path, total, render, blank=count == 0, max_seconds=max_seconds)
 
 
 def sim_to_wav(matrices=[None], size=32, use_same_instrument=None, sound_font='FluidR3_GM.sf2', *, simulate="des",
                out_dir="adj_sim_outputs", max_events=200000, max_seconds=None, device="cuda", return_batch=False):
     """See the module docstring.  matrices: ``(size, size)`` array-likes or None (a random matrix is drawn)."""
-    if simulate not in BACK_ENDS:
-        raise ValueError(f"sim_to_wav: unknown back end {simulate!r} (the built-in ones are \"des\", \"des_batch\" and "
-                         "\"des_device\")")
+    check_back_end(simulate, "sim_to_wav: unknown back end", ValueError)
     size = int(size)
     if not ops.S2W_MIN_SIZE <= size <= ops.S2W_MAX_SIZE:
         raise ValueError(f"sim_to_wav: size {size} (valid sizes are {ops.S2W_MIN_SIZE} .. {ops.S2W_MAX_SIZE}: 1 .. "

@@ -276,6 +276,40 @@ def run_batch_device(adj, loc, scale, queue_cap, seed, customers, states=None, *
     return BatchLog(*out, k, p, h, g)
 
 
+def batch_log_to(log, device):
+    """A host BatchLog -> BatchLog of tensors on ``device`` (uint32 travels as int32 bit patterns, as the kernel's)."""
+    import torch
+    dev = torch.device(device)
+    return BatchLog(*(torch.from_numpy(np.ascontiguousarray(a.view(np.int32) if a.dtype == np.uint32 else a)).to(dev)
+                      for a in log))
+
+
+def run_batch_auto(adj, loc, scale, queue_cap, seed, customers, states, *, device, min_device_b, max_events=200000,
+                   max_records=5001, max_queue_cap=None):
+    """The simulator choice of "des_batch" (arrays: numpy, or device tensors as ``run_batch_device`` takes them): the
+    kernel from ``min_device_b`` samples on if it holds ``dim`` nodes, else the host mirror with portable math (the
+    same bits; the launch costs 8-10 ms however small the batch is), its log uploaded once -> BatchLog of tensors on
+    ``device``.  device=None: the host mirror's BatchLog of numpy arrays."""
+    from . import ops
+    if device is not None and adj.shape[0] >= min_device_b and adj.shape[1] <= ops.DES_BATCH_MAX_DIM:
+        return run_batch_device(adj, loc, scale, queue_cap, seed, customers, states, device=device,
+                                max_events=max_events, max_records=max_records, max_queue_cap=max_queue_cap)
+    adj, loc, scale, queue_cap = (a if isinstance(a, np.ndarray) else a.cpu().numpy() for a in (adj, loc, scale, queue_cap))
+    host = run_batch_host(adj, loc, scale, queue_cap, seed, customers, states, math=1, max_events=max_events,
+                          max_records=max_records)
+    return host if device is None else batch_log_to(host, device)
+
+
+def raise_for_stop(stop_reasons, who, noun):
+    """ValueError for the first simulation of a batch that stopped with DES_STOP_ERROR or DES_STOP_BUDGET."""
+    from . import ops
+    for i, reason in enumerate(np.asarray(stop_reasons).tolist()):
+        if reason in (ops.DES_STOP_ERROR, ops.DES_STOP_BUDGET):
+            raise ValueError(f"{who}: the simulation of {noun} {i} stopped with {STOP_REASONS[reason]!r} (a node without "
+                             "destination, a customer routed to a source, or a service distribution that never turns "
+                             "positive; the reference raises or never returns)")
+
+
 def run_batch(specs, *, device=None, max_events=200000, max_records=5001, states=None):
     """B ``matrix_sim_process.DesSpec`` of one size, each simulated from its own generator state (``states``: B
     ``np.random.get_state()`` tuples, or one for all; None: numpy's current global state -- which is left untouched).

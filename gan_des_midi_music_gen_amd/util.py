@@ -21,6 +21,7 @@ own three files; the other sample formats follow torchaudio's documented formula
 """
 import math
 import operator
+import os
 import struct
 import warnings
 
@@ -238,6 +239,29 @@ def wav_header(n_samples, sample_rate=44100):
     return (b"RIFF" + struct.pack("<I", 36 + 2 * n_samples) + b"WAVEfmt " +
             struct.pack("<IHHIIHH", 16, 1, 1, sample_rate, 2 * sample_rate, 2, 16) +
             b"data" + struct.pack("<I", 2 * n_samples))
+
+
+_WAV_CHUNK = 1 << 22          # samples rendered per synth launch (8 MB of PCM)
+
+
+def write_wav_chunks(path, total, render, *, blank=False, max_seconds=None, rate=ops.SYNTH_RATE, chunk=None):
+    """A clip of ``total`` samples as a mono 16-bit WAV file, rendered on the device in bounded chunks:
+    ``render(first, count)`` -> int16 tensor of samples [first, first + count).  A ``blank`` clip is five seconds of
+    silence (the reference's ``np.zeros(5 * 44100)``, GAN_DES/matrix_sim_process.py:103) and ``render`` is not called;
+    ``max_seconds`` cuts the clip.  Directories are created.  chunk: samples per ``render`` call (default: _WAV_CHUNK).
+    Returns the samples written."""
+    chunk = chunk or _WAV_CHUNK
+    if blank:
+        total = 5 * rate
+    if max_seconds is not None:
+        total = max(1, min(total, int(max_seconds * rate)))
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(wav_header(total, rate))
+        for first in range(0, total, chunk):
+            count = min(chunk, total - first)
+            f.write(bytes(2 * count) if blank else render(first, count).cpu().numpy().astype("<i2").tobytes())
+    return total
 
 
 def upload_pcm(wav, device="cuda"):

@@ -214,9 +214,9 @@ def test_batched_prologue_makes_the_prologues_specs_and_snapshots():
     same(pro, specs, after)
     # the reference order, replayed by hand: the state right after each sample's reseed
     np.random.seed(int(g[f"{pre}/np_seed"]))
-    h = msp._midi_scan(g1, g2, (64, 64))
+    h = msp.MIDI.scan(g1, 64, g2)
     for i in range(h["b"]):
-        msp._midi_draws(h, i)
+        msp.MIDI.draws(h, i)
         want = np.random.get_state()
         got = pro.states[i]
         assert np.array_equal(got[1], want[1]) and got[2:] == want[2:]
@@ -228,8 +228,8 @@ def test_batched_prologue_makes_the_prologues_specs_and_snapshots():
     pro = msp.batched_prologue_wav(m, size=20)
     same(pro, specs, after)
     np.random.seed(int(g["wav/np_seed"]))
-    h = msp._wav_scan(m, 20)
+    h = msp.WAV.scan(m, 20)
     for i in range(h["b"]):
-        msp._wav_draws(h, i)
+        msp.WAV.draws(h, i)
         want = np.random.get_state()
         assert np.array_equal(pro.states[i][1], want[1]) and pro.states[i][2:] == want[2:]

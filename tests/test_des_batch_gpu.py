@@ -246,11 +246,13 @@ def route(request, monkeypatch):
 
 def test_route_by_batch_size(monkeypatch):
     seen = []
-    pro = msp.BatchedPrologue.__new__(msp.BatchedPrologue)
-    monkeypatch.setattr(msp.BatchedPrologue, "simulate",
-                        lambda self, device, **kw: seen.append(device) or sv.BatchLog(*[np.zeros(1, np.int32)] * 11))
+    log = sv.BatchLog(*[np.zeros(1, np.int32)] * 11)
+    monkeypatch.setattr(sv, "run_batch_device", lambda *a, device, **kw: seen.append(device) or log)
+    monkeypatch.setattr(sv, "run_batch_host", lambda *a, **kw: seen.append(None) or log)
     for b in (1, msp.DES_BATCH_DEVICE_MIN_B - 1, msp.DES_BATCH_DEVICE_MIN_B, 256):
-        pro.h = {"b": b}
+        pro = msp.BatchedPrologue(msp.WAV, {"b": b}, np.zeros((b, 15, 15)), None, None, None)
+        pro.loc = pro.scale = pro.queue_cap = np.ones((b, 15))      # the per-node arrays, which the stand-ins ignore
+        pro.seed = pro.customers = np.ones(b)
         pro.simulate_on(DEV)
     assert seen == [None, None, DEV, DEV] and 30 < msp.DES_BATCH_DEVICE_MIN_B <= 64
 

@@ -36,27 +36,27 @@ def _base_after_seed(seed, b):
     return base, np.random.get_state()
 
 
-def _numpy_prologue(h, draws, spec_of, base):
-    """``msp._batched_prologue`` with every sample on its own stream RandomState(base[i])."""
+def _numpy_prologue(route, h, instrument, base):
+    """``route.batched(h, instrument)`` with every sample on its own stream RandomState(base[i])."""
     b, dim = h["b"], h["dim"]
     src_all, cols_all = np.zeros((b, dim), dtype=bool), np.empty((b, dim), dtype=np.int32)
     seeds, states = [], []
     keep = np.random.get_state()
     for i in range(b):
         np.random.seed(int(base[i]))
-        src_all[i], cols_all[i], sd = draws(h, i)
+        src_all[i], cols_all[i], sd = route.draws(h, i)
         seeds.append(sd)
         states.append(np.random.get_state())
     np.random.set_state(keep)
     routing = ops.des_routing(h["g1"], h["size"], dim, torch.from_numpy(src_all.astype(np.uint8)).to(DEV),
                               torch.from_numpy(cols_all).to(DEV))
-    return msp.BatchedPrologue(h, routing, src_all, seeds, states, spec_of)
+    return msp.BatchedPrologue(route, h, routing, src_all, seeds, states, instrument)
 
 
 def _midi_want(g1, g2, adj, instrument, base, start, end, generate):
     from gan_des_midi_music_gen_amd import sim_log_to_midi as s2m
-    h = msp._midi_scan(g1, g2, adj)
-    pro = _numpy_prologue(h, msp._midi_draws, lambda h_, i, r, src, sd: msp._midi_spec(h_, i, r, src, sd, instrument), base)
+    pro = _numpy_prologue(msp.MIDI, msp.MIDI.scan(g1, adj[0], g2), instrument, base)
+    h = pro.h
     host = pro.simulate(None, max_records=s2m.MAX_LINES + 1)
     b = h["b"]
     logs = [sv.sample_log(host, i) for i in range(b)]
@@ -96,8 +96,7 @@ def test_device_prologue_equals_numpy_per_sample():
     np.random.seed(5)
     dev = msp.device_prologue_midi(g1, g2, (64, 64), 9)
     assert np.array_equal(np.random.get_state()[1], state_want[1]) and np.array_equal(dev.base, base)
-    h = msp._midi_scan(g1, g2, (64, 64))
-    want = _numpy_prologue(h, msp._midi_draws, lambda h_, i, r, src, sd: msp._midi_spec(h_, i, r, src, sd, 9), base)
+    want = _numpy_prologue(msp.MIDI, msp.MIDI.scan(g1, 64, g2), 9, base)
     assert torch.equal(dev.routing, want.routing) and not dev.status.any()
     for name in ("loc", "scale", "queue_cap", "seed", "customers", "instruments", "note_levels"):
         assert np.array_equal(getattr(dev, name).cpu().numpy(), getattr(want, name)), name
@@ -111,8 +110,7 @@ def test_matrix_to_wav_des_device_equals_the_numpy_route():
     from gan_des_midi_music_gen_amd import sim_log_process_music as slpm, util
     m = torch.from_numpy(_fixture()["wav/matrices"][:3]).to(DEV)
     base, state_want = _base_after_seed(33, 3)
-    h = msp._wav_scan(m, 20)
-    pro = _numpy_prologue(h, msp._wav_draws, lambda h_, i, r, src, sd: msp._wav_spec(h_, i, r, src, sd, None), base)
+    pro = _numpy_prologue(msp.WAV, msp.WAV.scan(m, 20), None, base)
     host = pro.simulate(None, max_records=slpm.MAX_LINES + 1)
     logs = [sv.sample_log(host, i) for i in range(3)]
     assert all(len(lg) > 100 for lg in logs)

@@ -229,6 +229,33 @@ def test_generate_songs_of_one_is_generate_song(gen_checkpoint, tmp_path):
     assert open(songs.wav_paths[0], "rb").read() == open(wav, "rb").read()
 
 
+def test_write_clip_whole_cut_blank_and_across_the_chunk_seam(tmp_path, monkeypatch):
+    """One 0.81 s clip through ``_write_clip``: the header is ``util.wav_header``, the body ``ops.synth_pcm``; cut at a
+    quarter second; a blank clip is five seconds of zeros (cut: a quarter); in 4096-sample chunks the same bytes."""
+    from gan_des_midi_music_gen_amd import simulation_v3 as sv3
+    log = np.zeros(2, dtype=sv3.EVENT_DTYPE)
+    log["value"], log["event_id"], log["node"], log["kind"] = [1.5, 3.25], [3, 3], [0, 0], [0, 1]
+    notes, n_notes, _clip_len = slpm.log_to_notes([log], [[0, 0]], [[60, 62]], device=DEV)
+    notes[0, 0, 1] = 300                                             # hold the one note for 300 ticks of 735 / 8 samples
+    total, rate = 300 * 735 // 8 + 8192, ops.SYNTH_RATE
+    pcm = ops.synth_pcm(notes, n_notes, 0, total).cpu().numpy().astype("<i2").tobytes()
+    assert rate // 4 < total <= rate and any(pcm[:2 * 4096]) and any(pcm[2 * 4096:])
+
+    def written(name, length, max_seconds=None):
+        path = str(tmp_path / "clips" / name)
+        SIMNN._write_clip(notes, n_notes, 0, 1, length, None, path, max_seconds)
+        return open(path, "rb").read()
+
+    whole = written("whole.wav", total)
+    assert whole == util.wav_header(total, rate) + pcm
+    assert written("cut.wav", total, 0.25) == util.wav_header(rate // 4, rate) + pcm[:2 * (rate // 4)]
+    assert written("blank.wav", 0) == util.wav_header(5 * rate, rate) + bytes(10 * rate)
+    assert written("blank_cut.wav", 0, 0.25) == util.wav_header(rate // 4, rate) + bytes(2 * (rate // 4))
+    monkeypatch.setattr(util, "_WAV_CHUNK", 4096)
+    assert written("seam.wav", total) == whole
+    assert written("seam_cut.wav", total, 0.25) == util.wav_header(rate // 4, rate) + pcm[:2 * (rate // 4)]
+
+
 @pytest.mark.parametrize("bridge", ["des_batch", "des"])
 def test_generate_songs_files(gen_checkpoint, bridge, tmp_path):
     gen = SIMNN._load_generator(gen_checkpoint, DEV)

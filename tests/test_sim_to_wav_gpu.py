@@ -312,6 +312,28 @@ def _messages(path):
     return np.asarray(rows, dtype=np.int64).reshape(-1, 4)
 
 
+def test_render_whole_cut_blank_and_across_the_chunk_seam(tmp_path, monkeypatch):
+    """One 0.82 s clip through ``_render``: the header is ``util.wav_header``, the body the reference render; cut at a
+    quarter second; a clip without notes is five seconds of zeros; in 4096-sample chunks the same bytes."""
+    from gan_des_midi_music_gen_amd import simulation_to_wav as S2W, util
+    rows, total, rate = np.asarray([[2, 600, 60, 80, 9]], dtype=np.int64), 36000, 44100
+    dev_rows = _up(rows, np.int64)
+
+    def written(name, count, max_seconds=None):
+        path = str(tmp_path / "clips" / name)
+        S2W._render(dev_rows[:count], count, total if count else 0, path, max_seconds, dev_rows.device)
+        return open(path, "rb").read()
+
+    body = R.render(rows, total).astype("<i2").tobytes()
+    assert any(body[:2 * 4096]) and any(body[2 * 4096:])
+    whole = written("whole.wav", 1)
+    assert whole == util.wav_header(total, rate) + body
+    assert written("cut.wav", 1, 0.25) == util.wav_header(rate // 4, rate) + body[:2 * (rate // 4)]
+    assert written("blank.wav", 0) == util.wav_header(5 * rate, rate) + bytes(10 * rate)
+    monkeypatch.setattr(util, "_WAV_CHUNK", 4096)
+    assert written("seam.wav", 1) == whole
+
+
 def test_sim_to_wav_des_equals_the_recording(golden, tmp_path):
     from gan_des_midi_music_gen_amd import simulation_to_wav as S2W
     out_dir = str(tmp_path / "out")

@@ -101,7 +101,7 @@ matrices = torch.from_numpy(np.tile(d["wav/matrices"], (6, 1, 1))[:B]).to(dev)
 res["model1_B30"] = measure(
     int(d["wav/np_seed"]),
     lambda mode: msp.matrix_to_wav(matrices, size=20, start=0, end=216, device=dev, simulate=mode),
-    lambda: msp.batched_prologue_wav(matrices, 20, None), lambda: msp._wav_scan(matrices, 20), msp._wav_draws)
+    lambda: msp.batched_prologue_wav(matrices, 20, None), lambda: msp.WAV.scan(matrices, 20), msp.WAV.draws)
 for B in (16, 256):
     reps = B // 4
     g1 = torch.from_numpy(np.tile(d["midi/g1"], (reps, 1, 1))).unsqueeze(1).to(dev)
@@ -109,8 +109,7 @@ for B in (16, 256):
     res[f"model2_B{B}"] = measure(
         3, lambda mode: msp.matrix_to_midi(g1, g2, adj_size=(64, 64), start=100, end=150, simulate=mode,
                                            return_tensor=True),
-        lambda: msp.batched_prologue_midi(g1, g2, (64, 64), None), lambda: msp._midi_scan(g1, g2, (64, 64)),
-        msp._midi_draws)
+        lambda: msp.batched_prologue_midi(g1, g2, (64, 64), None), lambda: msp.MIDI.scan(g1, 64, g2), msp.MIDI.draws)
 if len(sys.argv) > 1:
     os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
     with open(sys.argv[1], "w") as f:

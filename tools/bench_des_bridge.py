@@ -41,10 +41,8 @@ def one_pass():
     np.random.seed(int(d["wav/np_seed"]))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    h = msp._wav_scan(matrices, 20)
-    specs = msp._interleaved_specs(h, msp._wav_draws, lambda h_, i, r, src, sd: msp._wav_spec(h_, i, r, src, sd, None))
     logs, levels = [], []
-    for spec in specs:
+    for spec in msp.WAV.specs(msp.WAV.scan(matrices, 20)):
         logs.append(simulation_v3.run_spec(spec)[0])
         levels.append([int(x) for x in spec.note_levels])
     t["host_des_ms"] = (time.perf_counter() - t0) * 1e3

@@ -109,9 +109,9 @@ def midis_split(mm, n1, n2, beats, out_dir):
     t0 = time.perf_counter()
     o1, o2 = mm.sample(noise1=n1, noise2=n2, input_tensor=beats)
     t0 = lap("generators", t0)
-    h = msp._midi_scan(o1, o2, (64, 64))
+    h = msp.MIDI.scan(o1, 64, o2)
     t0 = lap("scan", t0)
-    pro = msp._batched_prologue(h, msp._midi_draws, lambda h_, i, r, src, sd: msp._midi_spec(h_, i, r, src, sd, 0))
+    pro = msp.MIDI.batched(h, 0)
     t0 = lap("host_draws_and_routing", t0)
     log = pro.simulate_on(DEV, max_records=sim_log_to_midi.MAX_LINES + 1)
     t0 = lap("simulator", t0)
