@@ -16,7 +16,7 @@
 // The np.random.randint fallbacks of MidiGenerator.__init__ (lines 24-31) are unreachable -- skip_k = max(2, .) is never
 // 0 -- and are not built.  The 'processing' branch of process_line is dead too: the reader's regex never matches such a
 // line.
-#include "gdm_common.h"
+#include "des_log.h"
 
 namespace {
 
@@ -26,13 +26,6 @@ constexpr int kThreads = 256;
 constexpr int kMaxDim = GDM_DES_MIDI_MAX_NODES;
 constexpr uint32_t kInactive = 0xFFFFFFFFu;
 constexpr uint32_t kNoNode = 0x3FFF;     // node >= dim: the reference's dict lookups raise KeyError for it
-
-// Python's % on integers (result takes the divisor's sign)
-__device__ __forceinline__ int64_t pymod(int64_t a, int64_t m) {
-  int64_t r = a % m;
-  if (r != 0 && ((r < 0) != (m < 0))) r += m;
-  return r;
-}
 
 struct Params {
   int skip1, skip2, skip3, base, tempo, var, key, err;
@@ -101,16 +94,13 @@ __global__ __launch_bounds__(kThreads) void des_log_to_roll_kernel(
   r0 = min(max(r0, (int64_t)0), n_records);
   r1 = min(max(r1, r0), n_records);
   const int n_look = (int)min(r1 - r0, (int64_t)kMaxLines);
-  constexpr uint64_t kBits1em4 = 0x3F1A36E2EB1C432DULL;     // 1e-4
   constexpr uint64_t kBits200 = 0x4069000000000000ULL;      // 200.0
-  // (values in [200, 1e16) match the regex but fail `midi_time < 200`: inactive either way)
   for (int r = tid; r < n_look; r += kThreads) {
     const uint64_t vb = (uint64_t)__double_as_longlong(value[r0 + r]);
     const int64_t e = event_id[r0 + r];
     const int nd = node[r0 + r], kd = kind[r0 + r];
-    // The regex matches iff kind is arrival / departure, the integers print without a sign and repr(value) is plain
-    // digits: +0.0 or 1e-4 <= value < 1e16.  Non-negative doubles order like their bit patterns.
-    const bool live = (kd == 0 || kd == 1) && e >= 0 && nd >= 0 && (vb == 0 || (vb >= kBits1em4 && vb < kBits200));
+    // values in [200, 1e16) match the regex but fail `midi_time < 200`: inactive either way
+    const bool live = des_line_matches(kd, e, nd, vb, kBits200);
     uint32_t w = kInactive;
     if (live && (e % p.skip1 == 0 || e % p.skip2 == 0 || e % p.skip3 == 0)) {
       const int mt = (int)__longlong_as_double((long long)vb);          // max(0, int(float(.))), < 200

@@ -19,7 +19,7 @@
 // (SIMULATOR/simulation_to_wav.py:162-214), where those program_change lines are NOT commented out: every note_on and
 // every note_off is preceded by a program_change carrying the same delta time, so each delta counts twice and each note
 // has its node's program (a fifth column).  One source, a template flag; the flag-off instance is the kernel above.
-#include "gdm_common.h"
+#include "des_log.h"
 #include "buffer_ops.h"
 
 namespace {
@@ -29,13 +29,6 @@ constexpr int kThreads = 256;
 constexpr int kMaxDim = GDM_DES_MIDI_MAX_NODES;
 constexpr int64_t kMaxTick = ((((int64_t)1 << 40) - GDM_SYNTH_RELEASE) << 3) / 735;   // sample(tick) + release <= 2^40
 constexpr size_t kLdsBytes = (size_t)kMaxLines * (8 + 8 + 4);
-
-// Python's % on integers (result takes the divisor's sign)
-__device__ __forceinline__ int64_t pymod(int64_t a, int64_t m) {
-  int64_t r = a % m;
-  if (r != 0 && ((r < 0) != (m < 0))) r += m;
-  return r;
-}
 
 // What only the program_change variant takes: the programs, the tick -> sample rule sample(tick) = tick * mul / div,
 // the samples a clip lasts beyond its last note_off, and the last tick whose sample + tail stays within 2^40.
@@ -78,17 +71,13 @@ __global__ __launch_bounds__(kThreads) void des_log_to_notes_kernel(
   r0 = min(max(r0, (int64_t)0), n_records);
   r1 = min(max(r1, r0), n_records);
   const int n_look = (int)min(r1 - r0, (int64_t)kMaxLines);
-  constexpr uint64_t kBits1em4 = 0x3F1A36E2EB1C432DULL;     // 1e-4
-  constexpr uint64_t kBits1e16 = 0x4341C37937E08000ULL;     // 1e16
   for (int r = tid; r < n_look; r += kThreads) {
     const uint64_t vb = (uint64_t)__double_as_longlong(value[r0 + r]);
     const int64_t e = event_id[r0 + r];
     const int nd = node[r0 + r], kd = kind[r0 + r];
-    // The regex matches iff kind is arrival / departure, the integers print without a sign and repr(value) is plain
-    // digits: +0.0 or 1e-4 <= value < 1e16.  Non-negative doubles order like their bit patterns.
-    const bool live = (kd == 0 || kd == 1) && e >= 0 && nd >= 0 && (vb == 0 || (vb >= kBits1em4 && vb < kBits1e16));
     int64_t t = -1;
-    if (live && (e % 3 == 0 || e % 5 == 0 || e % 7 == 0)) t = (int64_t)__longlong_as_double((long long)vb);
+    if (des_line_matches(kd, e, nd, vb, kDesBits1e16) && (e % 3 == 0 || e % 5 == 0 || e % 7 == 0))
+      t = (int64_t)__longlong_as_double((long long)vb);
     s_time[r] = t;
     s_eid[r] = e;
     s_meta[r] = (uint32_t)nd | ((uint32_t)(kd == 1) << 31);

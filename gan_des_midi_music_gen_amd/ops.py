@@ -1193,18 +1193,32 @@ def des_roll_width(start, end):
     return min(end, width) - col0
 
 
+def _records(what, value, event_id, node, kind, rec_ptr):
+    """The record arrays and their CSR offsets, as the three DES-log wrappers take them -> (n records, B samples)."""
+    n = value.numel()
+    b = rec_ptr.numel() - 1
+    for t, dt in ((value, torch.float64), (event_id, torch.int64), (node, torch.int32), (kind, torch.int32)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise GdmError(f"{what}: records must be contiguous f64 / i64 / i32 / i32 arrays of one length")
+    if rec_ptr.dtype != torch.int64 or b < 1 or not rec_ptr.is_contiguous():
+        raise GdmError(f"{what}: rec_ptr must be a contiguous int64 tensor of B + 1 offsets")
+    return n, b
+
+
+def _rec_ptr_ascends(what, rec_ptr, n):
+    """Argument validation (one small reduction + sync), not arithmetic of the path: offsets must ascend within [0, n].
+    A caller passes check_rec_ptr=False to vouch for offsets that never left the device (``des_run_batch``'s pack step
+    wrote them); the kernels clamp every offset to [0, n] either way."""
+    if bool(((rec_ptr[1:] < rec_ptr[:-1]).any() | (rec_ptr[0] < 0) | (rec_ptr[-1] > n)).item()):
+        raise GdmError(f"{what}: rec_ptr must ascend within [0, {n}] (the number of records)")
+
+
 def des_log_to_roll(value, event_id, node, kind, rec_ptr, tails, instruments, note_levels, save, start, end,
                     sequence_length=100, *, check_rec_ptr=True):
     """Event records of B samples (CSR: rec_ptr (B+1) i64) -> (planes (B,2,128,W) fp32, track (B,512,4) i32, track_len
     (B) i32, status (B) i32), all device tensors; one launch (gdm_des_log_to_roll, include/gdm.h)."""
     _need_gpu(value, event_id, node, kind, rec_ptr, tails, instruments, note_levels, save)
-    n = value.numel()
-    b = rec_ptr.numel() - 1
-    for t, dt in ((value, torch.float64), (event_id, torch.int64), (node, torch.int32), (kind, torch.int32)):
-        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
-            raise GdmError("des_log_to_roll: records must be contiguous f64 / i64 / i32 / i32 arrays of one length")
-    if rec_ptr.dtype != torch.int64 or b < 1 or not rec_ptr.is_contiguous():
-        raise GdmError("des_log_to_roll: rec_ptr must be a contiguous int64 tensor of B + 1 offsets")
+    n, b = _records("des_log_to_roll", value, event_id, node, kind, rec_ptr)
     if tails.dtype != torch.float32 or tails.dim() != 2 or tails.shape[0] != b or tails.shape[1] < 6 or \
             tails.stride(1) != 1:
         raise GdmError("des_log_to_roll: tails must be (B, >= 6) fp32")
@@ -1214,11 +1228,8 @@ def des_log_to_roll(value, event_id, node, kind, rec_ptr, tails, instruments, no
             raise GdmError("des_log_to_roll: instruments / note_levels must be contiguous (B, dim) int32")
     if save.dtype != torch.int32 or save.shape != (b,) or not save.is_contiguous():
         raise GdmError("des_log_to_roll: save must be a contiguous (B,) int32 tensor")
-    # argument validation (one small reduction + sync), not arithmetic of the path: offsets must ascend within [0, n].
-    # check_rec_ptr=False: the caller vouches for offsets that never left the device (``des_run_batch``'s pack step
-    # wrote them); the kernel clamps every offset to [0, n] either way
-    if check_rec_ptr and bool(((rec_ptr[1:] < rec_ptr[:-1]).any() | (rec_ptr[0] < 0) | (rec_ptr[-1] > n)).item()):
-        raise GdmError(f"des_log_to_roll: rec_ptr must ascend within [0, {n}] (the number of records)")
+    if check_rec_ptr:
+        _rec_ptr_ascends("des_log_to_roll", rec_ptr, n)
     start, end = int(start), int(end)
     w = des_roll_width(start, end)
     if end - start <= 0 or w <= 0:
@@ -1260,31 +1271,38 @@ def synth_tables(device):
     return _synth_tables[key]
 
 
+def _notes_out(b, cols, dev):
+    """(notes (B, 5000, cols) i64 zeroed, n_notes (B) i32, clip_len (B) i64, status (B) i32) of the log -> notes kernels."""
+    return (torch.zeros((b, DES_NOTES_MAX, cols), dtype=torch.int64, device=dev),
+            torch.empty(b, dtype=torch.int32, device=dev), torch.empty(b, dtype=torch.int64, device=dev),
+            torch.empty(b, dtype=torch.int32, device=dev))
+
+
 def des_log_to_notes(value, event_id, node, kind, rec_ptr, note_levels, *, check_rec_ptr=True):
     """Event records of B samples (CSR: rec_ptr (B+1) i64) -> (notes (B,5000,4) i64 of (on_tick, off_tick, pitch,
     velocity), n_notes (B) i32, clip_len (B) i64, status (B) i32), all device tensors; one launch
     (gdm_des_log_to_notes, include/gdm.h)."""
     _need_gpu(value, event_id, node, kind, rec_ptr, note_levels)
-    n = value.numel()
-    b = rec_ptr.numel() - 1
-    for t, dt in ((value, torch.float64), (event_id, torch.int64), (node, torch.int32), (kind, torch.int32)):
-        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
-            raise GdmError("des_log_to_notes: records must be contiguous f64 / i64 / i32 / i32 arrays of one length")
-    if rec_ptr.dtype != torch.int64 or b < 1 or not rec_ptr.is_contiguous():
-        raise GdmError("des_log_to_notes: rec_ptr must be a contiguous int64 tensor of B + 1 offsets")
+    n, b = _records("des_log_to_notes", value, event_id, node, kind, rec_ptr)
     if note_levels.dtype != torch.int32 or note_levels.dim() != 2 or note_levels.shape[0] != b or \
             not note_levels.is_contiguous():
         raise GdmError("des_log_to_notes: note_levels must be contiguous (B, dim) int32")
-    if check_rec_ptr and bool(((rec_ptr[1:] < rec_ptr[:-1]).any() | (rec_ptr[0] < 0) | (rec_ptr[-1] > n)).item()):
-        raise GdmError(f"des_log_to_notes: rec_ptr must ascend within [0, {n}] (the number of records)")
-    dev = value.device
-    notes = torch.zeros((b, DES_NOTES_MAX, 4), dtype=torch.int64, device=dev)
-    n_notes = torch.empty(b, dtype=torch.int32, device=dev)
-    clip_len = torch.empty(b, dtype=torch.int64, device=dev)
-    status = torch.empty(b, dtype=torch.int32, device=dev)
+    if check_rec_ptr:
+        _rec_ptr_ascends("des_log_to_notes", rec_ptr, n)
+    notes, n_notes, clip_len, status = _notes_out(b, 4, value.device)
     _call("gdm_des_log_to_notes", _p(value), _p(event_id), _p(node), _p(kind), _p(rec_ptr), n, _p(note_levels),
           note_levels.shape[1], b, _p(notes), DES_NOTES_MAX, _p(n_notes), _p(clip_len), _p(status), _stream())
     return notes, n_notes, clip_len, status
+
+
+def _plain_tables(what, tables, device):
+    """(wave, inc) of the plain timbre: ``tables``, or ``synth_tables(device)`` for None."""
+    wave, inc = synth_tables(device) if tables is None else tables
+    _need_gpu(wave, inc)
+    if wave.dtype != torch.int16 or wave.shape != (SYNTH_WAVE,) or inc.dtype != torch.int32 or inc.shape != (128,) or \
+            not wave.is_contiguous() or not inc.is_contiguous():
+        raise GdmError(f"{what}: tables must be (wave int16[{SYNTH_WAVE}], inc int32[128] holding uint32 bits)")
+    return wave, inc
 
 
 def _synth_args(notes, n_notes, what, tables):
@@ -1294,12 +1312,7 @@ def _synth_args(notes, n_notes, what, tables):
         raise GdmError(f"{what}: notes must be a contiguous (B, 1..{DES_NOTES_MAX}, 4) int64 tensor")
     if n_notes.dtype != torch.int32 or n_notes.shape != (notes.shape[0],) or not n_notes.is_contiguous():
         raise GdmError(f"{what}: n_notes must be a contiguous (B,) int32 tensor")
-    wave, inc = synth_tables(notes.device) if tables is None else tables
-    _need_gpu(wave, inc)
-    if wave.dtype != torch.int16 or wave.shape != (SYNTH_WAVE,) or inc.dtype != torch.int32 or inc.shape != (128,) or \
-            not wave.is_contiguous() or not inc.is_contiguous():
-        raise GdmError(f"{what}: tables must be (wave int16[{SYNTH_WAVE}], inc int32[128] holding uint32 bits)")
-    return wave, inc
+    return _plain_tables(what, tables, notes.device)
 
 
 def synth_frames(notes, n_notes, clip_len, *, tables=None, out=None):
@@ -1340,6 +1353,33 @@ def synth_pcm(notes, n_notes, first, count, *, tables=None, out=None):
     return out
 
 
+def _windows_args(what, notes, cols, bound, bound_name, note_ptr, win_clip, win_start):
+    """The note and window tables the two windows wrappers share -> (n rows, W windows)."""
+    _need_gpu(notes, bound, note_ptr, win_clip, win_start)
+    n = notes.shape[0] if notes.dim() == 2 else -1
+    if notes.dtype != torch.int64 or notes.dim() != 2 or notes.shape[1] != cols or not notes.is_contiguous():
+        raise GdmError(f"{what}: notes must be a contiguous (n, {cols}) int64 tensor")
+    if bound.dtype != torch.int64 or bound.shape != (n,) or not bound.is_contiguous():
+        raise GdmError(f"{what}: {bound_name} must be a contiguous (n,) int64 tensor")
+    if note_ptr.dtype != torch.int64 or note_ptr.dim() != 1 or note_ptr.numel() < 2 or not note_ptr.is_contiguous():
+        raise GdmError(f"{what}: note_ptr must be a contiguous int64 tensor of F + 1 offsets")
+    w = win_clip.numel()
+    if win_clip.dtype != torch.int32 or win_clip.dim() != 1 or not win_clip.is_contiguous() or \
+            win_start.dtype != torch.int64 or win_start.shape != (w,) or not win_start.is_contiguous():
+        raise GdmError(f"{what}: win_clip (W,) int32 and win_start (W,) int64 must be contiguous and of one length")
+    return n, w
+
+
+def _windows_out(what, w, win_len, out, device):
+    """``out`` validated, or the default (W, win_len rounded up to a multiple of 8) int16 buffer."""
+    if out is None:
+        return torch.empty((w, (max(win_len, 0) + 7) // 8 * 8), dtype=torch.int16, device=device)
+    _need_gpu(out)
+    if out.dtype != torch.int16 or out.dim() != 2 or out.shape[0] != w or not out.is_contiguous():
+        raise GdmError(f"{what}: out must be a contiguous ({w}, out_stride) int16 tensor")
+    return out
+
+
 def synth_windows(notes, off_max, note_ptr, win_clip, win_start, win_len, *, tables=None, out=None):
     """W windows of F clips as 16-bit PCM in one launch (gdm_synth_windows, include/gdm.h): notes (n, 4) int64 rows
     (s_on, s_off, pitch, velocity) in SAMPLES, the clips back to back and ascending in s_on within a clip; off_max (n,)
@@ -1347,30 +1387,10 @@ def synth_windows(notes, off_max, note_ptr, win_clip, win_start, win_len, *, tab
     int64; every window ``win_len`` samples long.  Returns the (W, out_stride) int16 device tensor, out_stride =
     win_len rounded up to a multiple of 8 (or the row length of ``out``, a contiguous (W, out_stride) int16 tensor
     with out_stride >= win_len and out_stride % 8 == 0); columns from win_len on are not written."""
-    _need_gpu(notes, off_max, note_ptr, win_clip, win_start)
-    n = notes.shape[0] if notes.dim() == 2 else -1
-    if notes.dtype != torch.int64 or notes.dim() != 2 or notes.shape[1] != 4 or not notes.is_contiguous():
-        raise GdmError("synth_windows: notes must be a contiguous (n, 4) int64 tensor")
-    if off_max.dtype != torch.int64 or off_max.shape != (n,) or not off_max.is_contiguous():
-        raise GdmError("synth_windows: off_max must be a contiguous (n,) int64 tensor")
-    if note_ptr.dtype != torch.int64 or note_ptr.dim() != 1 or note_ptr.numel() < 2 or not note_ptr.is_contiguous():
-        raise GdmError("synth_windows: note_ptr must be a contiguous int64 tensor of F + 1 offsets")
-    w = win_clip.numel()
-    if win_clip.dtype != torch.int32 or win_clip.dim() != 1 or not win_clip.is_contiguous() or \
-            win_start.dtype != torch.int64 or win_start.shape != (w,) or not win_start.is_contiguous():
-        raise GdmError("synth_windows: win_clip (W,) int32 and win_start (W,) int64 must be contiguous and of one length")
-    wave, inc = synth_tables(notes.device) if tables is None else tables
-    _need_gpu(wave, inc)
-    if wave.dtype != torch.int16 or wave.shape != (SYNTH_WAVE,) or inc.dtype != torch.int32 or inc.shape != (128,) or \
-            not wave.is_contiguous() or not inc.is_contiguous():
-        raise GdmError(f"synth_windows: tables must be (wave int16[{SYNTH_WAVE}], inc int32[128] holding uint32 bits)")
+    n, w = _windows_args("synth_windows", notes, 4, off_max, "off_max", note_ptr, win_clip, win_start)
+    wave, inc = _plain_tables("synth_windows", tables, notes.device)
     win_len = int(win_len)
-    if out is None:
-        out = torch.empty((w, (max(win_len, 0) + 7) // 8 * 8), dtype=torch.int16, device=notes.device)
-    else:
-        _need_gpu(out)
-        if out.dtype != torch.int16 or out.dim() != 2 or out.shape[0] != w or not out.is_contiguous():
-            raise GdmError(f"synth_windows: out must be a contiguous ({w}, out_stride) int16 tensor")
+    out = _windows_out("synth_windows", w, win_len, out, notes.device)
     _call("gdm_synth_windows", _p(notes), _p(off_max), n, _p(note_ptr), note_ptr.numel() - 1, _p(win_clip),
           _p(win_start), w, win_len, out.shape[1], _p(wave), _p(inc), _p(out), _stream())
     return out
@@ -1463,27 +1483,17 @@ def des_log_to_notes_pc(value, event_id, node, kind, rec_ptr, instruments, note_
     ticks per beat); tail: samples a clip lasts beyond its last note_off (default: the longest release of
     ``synth_gm_tables``)."""
     _need_gpu(value, event_id, node, kind, rec_ptr, instruments, note_levels)
-    n = value.numel()
-    b = rec_ptr.numel() - 1
-    for t, dt in ((value, torch.float64), (event_id, torch.int64), (node, torch.int32), (kind, torch.int32)):
-        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
-            raise GdmError("des_log_to_notes_pc: records must be contiguous f64 / i64 / i32 / i32 arrays of one length")
-    if rec_ptr.dtype != torch.int64 or b < 1 or not rec_ptr.is_contiguous():
-        raise GdmError("des_log_to_notes_pc: rec_ptr must be a contiguous int64 tensor of B + 1 offsets")
+    n, b = _records("des_log_to_notes_pc", value, event_id, node, kind, rec_ptr)
     for t, what in ((note_levels, "note_levels"), (instruments, "instruments")):
         if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != b or not t.is_contiguous() or \
                 t.shape != note_levels.shape:
             raise GdmError(f"des_log_to_notes_pc: {what} must be contiguous (B, dim) int32")
-    if check_rec_ptr and bool(((rec_ptr[1:] < rec_ptr[:-1]).any() | (rec_ptr[0] < 0) | (rec_ptr[-1] > n)).item()):
-        raise GdmError(f"des_log_to_notes_pc: rec_ptr must ascend within [0, {n}] (the number of records)")
+    if check_rec_ptr:
+        _rec_ptr_ascends("des_log_to_notes_pc", rec_ptr, n)
     mul, div = tick_rule() if tick_mul_div is None else (int(tick_mul_div[0]), int(tick_mul_div[1]))
     if tail is None:
         tail = max(1 << (21 - a) for _n, _w, a in SYNTH_GM_FAMILY_TABLE)
-    dev = value.device
-    notes = torch.zeros((b, DES_NOTES_MAX, 5), dtype=torch.int64, device=dev)
-    n_notes = torch.empty(b, dtype=torch.int32, device=dev)
-    clip_len = torch.empty(b, dtype=torch.int64, device=dev)
-    status = torch.empty(b, dtype=torch.int32, device=dev)
+    notes, n_notes, clip_len, status = _notes_out(b, 5, value.device)
     _call("gdm_des_log_to_notes_pc", _p(value), _p(event_id), _p(node), _p(kind), _p(rec_ptr), n, _p(instruments),
           _p(note_levels), note_levels.shape[1], b, mul, div, int(tail), _p(notes), DES_NOTES_MAX, _p(n_notes),
           _p(clip_len), _p(status), _stream())
@@ -1495,19 +1505,7 @@ def synth_windows_gm(notes, end_max, note_ptr, win_clip, win_start, win_len, *, 
     rows (s_on, s_off, pitch, velocity, program) in SAMPLES, ascending in s_on within a clip; end_max (n,) int64 the
     running maximum of s_off + R_family within each clip; the rest as ``synth_windows``.  tables: (waves int16
     (16, 2048), env int32 (16, 2), inc int32[128]); default ``synth_gm_tables``."""
-    _need_gpu(notes, end_max, note_ptr, win_clip, win_start)
-    n = notes.shape[0] if notes.dim() == 2 else -1
-    if notes.dtype != torch.int64 or notes.dim() != 2 or notes.shape[1] != 5 or not notes.is_contiguous():
-        raise GdmError("synth_windows_gm: notes must be a contiguous (n, 5) int64 tensor")
-    if end_max.dtype != torch.int64 or end_max.shape != (n,) or not end_max.is_contiguous():
-        raise GdmError("synth_windows_gm: end_max must be a contiguous (n,) int64 tensor")
-    if note_ptr.dtype != torch.int64 or note_ptr.dim() != 1 or note_ptr.numel() < 2 or not note_ptr.is_contiguous():
-        raise GdmError("synth_windows_gm: note_ptr must be a contiguous int64 tensor of F + 1 offsets")
-    w = win_clip.numel()
-    if win_clip.dtype != torch.int32 or win_clip.dim() != 1 or not win_clip.is_contiguous() or \
-            win_start.dtype != torch.int64 or win_start.shape != (w,) or not win_start.is_contiguous():
-        raise GdmError("synth_windows_gm: win_clip (W,) int32 and win_start (W,) int64 must be contiguous and of one "
-                       "length")
+    n, w = _windows_args("synth_windows_gm", notes, 5, end_max, "end_max", note_ptr, win_clip, win_start)
     waves, env, inc = synth_gm_tables(notes.device) if tables is None else tables
     _need_gpu(waves, env, inc)
     if waves.dtype != torch.int16 or waves.shape != (SYNTH_GM_FAMILIES, SYNTH_WAVE) or env.dtype != torch.int32 or \
@@ -1516,12 +1514,7 @@ def synth_windows_gm(notes, end_max, note_ptr, win_clip, win_start, win_len, *, 
         raise GdmError(f"synth_windows_gm: tables must be (waves int16 (16, {SYNTH_WAVE}), env int32 (16, 2), inc "
                        "int32[128] holding uint32 bits)")
     win_len = int(win_len)
-    if out is None:
-        out = torch.empty((w, (max(win_len, 0) + 7) // 8 * 8), dtype=torch.int16, device=notes.device)
-    else:
-        _need_gpu(out)
-        if out.dtype != torch.int16 or out.dim() != 2 or out.shape[0] != w or not out.is_contiguous():
-            raise GdmError(f"synth_windows_gm: out must be a contiguous ({w}, out_stride) int16 tensor")
+    out = _windows_out("synth_windows_gm", w, win_len, out, notes.device)
     _call("gdm_synth_windows_gm", _p(notes), _p(end_max), n, _p(note_ptr), note_ptr.numel() - 1, _p(win_clip),
           _p(win_start), w, win_len, out.shape[1], _p(waves), _p(env), _p(inc), _p(out), _stream())
     return out

@@ -61,6 +61,21 @@ def off_max(notes):
     return np.maximum.accumulate(np.asarray(notes, dtype=np.int64).reshape(-1, 4)[:, 1])
 
 
+def as_gm(notes, seed):
+    """The clip as gdm_synth_windows_gm takes it when every family has the plain voice (``plain_gm_tables``): a fifth
+    column of seeded programs 0..127, and end_max = off_max + RELEASE."""
+    notes = np.asarray(notes, dtype=np.int64).reshape(-1, 4)
+    programs = np.random.default_rng(seed).integers(0, 128, (len(notes), 1))
+    return np.concatenate([notes, programs], axis=1), off_max(notes) + RELEASE
+
+
+def plain_gm_tables():
+    """(waves (16, 2048), env (16, 2), inc) of gdm_synth_windows_gm under which it is gdm_synth_windows: the one wave
+    table and (ATTACK, RELEASE) for every family."""
+    wave, inc = _TABLES
+    return np.tile(wave, (16, 1)), np.tile(np.asarray([ATTACK, RELEASE], dtype=np.int64), (16, 1)), inc
+
+
 # ---- hand-assembled Standard MIDI Files ----------------------------------------------------------------------------------
 def _vlq(n):
     assert 0 <= n < 1 << 28

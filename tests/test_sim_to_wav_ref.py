@@ -279,6 +279,21 @@ def test_synth_windows_gm_refuses_bad_arguments(lib):
     del keep
 
 
+def test_gm_mirror_with_the_plain_tables_is_the_plain_mirror():
+    """The identity tests/test_synth_windows_gpu.py demands of the two kernel instances, on the two mirrors and the same
+    clips and windows: with the plain wave and (A, R) for every family the programs do not matter."""
+    import synth_windows_ref as SW
+    import test_synth_windows_gpu as G
+    tables = SW.plain_gm_tables()
+    assert np.array_equal(tables[2], R.gm_tables()[2]) and (tables[1][:, 0] * tables[1][:, 1] == 1 << 21).all()
+    for i, c in ((0, 1), (1, 2)):
+        rows, end_max = SW.as_gm(G.CLIPS[c], 31 + i)
+        assert np.array_equal(end_max, R.end_max(rows, tables[1])) and len(set(rows[:, 4].tolist())) > 16
+        for start in (s for w, s in zip(G.WIN_CLIP, G.WIN_START) if w == c):
+            plain = SW.window(G.CLIPS[c], start, G.WIN)
+            assert plain.any() and np.array_equal(R.window(rows, start, G.WIN, tables), plain)
+
+
 def test_ops_tables_and_tick_rule():
     from gan_des_midi_music_gen_amd import ops
     assert ops.tick_rule() == (R.TICK_MUL, R.TICK_DIV) and ops.tick_rule(1000000, 480) == (735, 8)

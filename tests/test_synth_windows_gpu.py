@@ -183,6 +183,30 @@ def test_equals_synth_pcm_on_ticks():
     assert np.array_equal(old.cpu().numpy(), DR.pcm(ticks, 0, count))
 
 
+def test_gm_instance_with_the_plain_tables_is_the_plain_instance(mirror):
+    """gdm_synth_windows_gm with the plain wave for all 16 families, env = (A, R) and end_max = off_max + R equals
+    gdm_synth_windows bit for bit, whatever the programs: A R = 2^21 in both and every product stays below 2^43.  The
+    chord clip and the crowd clip (a second tile), their windows above, the full store (WIN) and the tail store."""
+    from gan_des_midi_music_gen_amd import ops
+    clips = [CLIPS[1], CLIPS[2]]
+    picked = [w for w, c in enumerate(WIN_CLIP) if c in (1, 2)]
+    win_clip = _up([WIN_CLIP[w] - 1 for w in picked], np.int32)
+    win_start = _up([WIN_START[w] for w in picked], np.int64)
+    notes, off_max, ptr = _tables(clips)
+    twins = [SW.as_gm(c, 31 + i) for i, c in enumerate(clips)]
+    rows, end_max = (_up(np.concatenate([t[k] for t in twins]), np.int64) for k in (0, 1))
+    assert len(picked) == 4 and len(set(((rows[:, 4] & 127) >> 3).tolist())) == 16 and WIN % 8 == 0
+    assert torch.equal(end_max, off_max + R) and torch.equal(rows[:, :4], notes)
+    wave, inc = ops.synth_tables(notes.device)
+    env = _up([[ops.SYNTH_ATTACK, ops.SYNTH_RELEASE]] * ops.SYNTH_GM_FAMILIES, np.int32)
+    tables = (wave.repeat(ops.SYNTH_GM_FAMILIES, 1).contiguous(), env, inc)
+    for win_len in (WIN, WIN - 3):
+        plain = ops.synth_windows(notes, off_max, ptr, win_clip, win_start, win_len)[:, :win_len]
+        gm = ops.synth_windows_gm(rows, end_max, ptr, win_clip, win_start, win_len, tables=tables)[:, :win_len]
+        assert torch.equal(gm, plain), f"win_len {win_len}: {int((gm != plain).sum())} samples differ"
+        assert np.array_equal(plain.cpu().numpy(), mirror[picked][:, :win_len])
+
+
 # ---- host checks ---------------------------------------------------------------------------------------------------------
 def test_host_checks_return_before_any_launch():
     from gan_des_midi_music_gen_amd import _lib, ops
