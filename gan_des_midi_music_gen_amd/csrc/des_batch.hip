@@ -13,36 +13,22 @@
 // LDS holds the event list, the per-node scalars, the global generator and the seeder; the node generators live there
 // too when dim <= kLdsGenDim (15 nodes: 37 KB), otherwise in the caller's workspace together with the routing tables
 // and the FIFO rings (L2-resident: about 330 KB per sample at dim 61, capacity 254).
+// The prologue up to the chain, the LDS block and the workspace layout are des_wave.h's, shared with the log-free
+// statistics kernel of des_stats.hip.
 // Bounds: every index the chain computes is checked in des_sim.h before it forms an address; every loop is bounded by
 // max_events, max_records or the draw budget.
 #include "gdm_common.h"
 #include "des_sim.h"
+#include "des_wave.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kMaxDim = GDM_DES_BATCH_MAX_DIM;
-#ifndef GDM_DES_LDS_GEN_DIM
-#define GDM_DES_LDS_GEN_DIM 15        // (an experiment build may move it: 0 keeps every node generator in the workspace)
-#endif
-constexpr int kLdsGenDim = GDM_DES_LDS_GEN_DIM;
+using des_wave::kMaxDim;
+using des_wave::ws_layout;
 constexpr int kPackThreads = 256;
 typedef des::Sim<des::MathPortable, des::OutSoa> DevSim;
-
-struct WsLayout {
-  size_t keys, children, cdf, ring, per_sample;
-};
-__host__ __device__ inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-__host__ __device__ inline WsLayout ws_layout(int dim, int max_queue_cap) {
-  WsLayout w;
-  w.keys = 0;
-  w.children = w.keys + align16((size_t)dim * DES_MT_N * 4);
-  w.cdf = w.children + align16((size_t)dim * dim * 4);
-  w.ring = w.cdf + align16((size_t)dim * dim * 8);
-  w.per_sample = w.ring + align16((size_t)dim * max_queue_cap * 8);
-  return w;
-}
 
 __global__ __launch_bounds__(GDM_WAVE) void des_batch_kernel(
     const double* __restrict__ adj, int dim, const double* __restrict__ loc, const double* __restrict__ scale,
@@ -53,94 +39,34 @@ __global__ __launch_bounds__(GDM_WAVE) void des_batch_kernel(
     int32_t* __restrict__ node, int32_t* __restrict__ kind, int64_t* __restrict__ n_records,
     int32_t* __restrict__ stop_reason, unsigned char* __restrict__ workspace) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];       // node generators when dim <= kLdsGenDim
-  __shared__ des::Ev s_heap[kMaxDim + 1];
-  __shared__ double s_loc[kMaxDim], s_scale[kMaxDim], s_gauss[kMaxDim + 2];
-  __shared__ uint32_t s_gkey[DES_MT_N], s_skey[DES_MT_N], s_node_seed[kMaxDim];
-  __shared__ int32_t s_qcap[kMaxDim], s_in_service[kMaxDim], s_qhead[kMaxDim], s_qlen[kMaxDim], s_nchild[kMaxDim];
-  __shared__ int32_t s_pos[kMaxDim + 2], s_has_gauss[kMaxDim + 2];
-  __shared__ uint8_t s_is_source[kMaxDim], s_bflags[kMaxDim];
-  __shared__ int s_ok;
+  __shared__ des_wave::Lds lds;
 
   const int b = blockIdx.x, lane = threadIdx.x;
-  const WsLayout w = ws_layout(dim, max_queue_cap);
+  const des_wave::WsLayout w = ws_layout(dim, max_queue_cap, false);
   unsigned char* ws = workspace + (size_t)b * w.per_sample;
 
   DevSim s;
-  s.dim = dim;
-  s.loc = s_loc;
-  s.scale = s_scale;
-  s.qcap = s_qcap;
-  s.is_source = s_is_source;
-  s.in_service = s_in_service;
-  s.qhead = s_qhead;
-  s.qlen = s_qlen;
-  s.nchild = s_nchild;
-  s.bflags = s_bflags;
-  s.children = reinterpret_cast<int32_t*>(ws + w.children);
-  s.cdf = reinterpret_cast<double*>(ws + w.cdf);
-  s.ring = reinterpret_cast<int64_t*>(ws + w.ring);
-  s.ring_stride = max_queue_cap;
-  s.node_keys = dim <= kLdsGenDim ? reinterpret_cast<uint32_t*>(s_dyn) : reinterpret_cast<uint32_t*>(ws + w.keys);
-  s.global_key = s_gkey;
-  s.seeder_key = s_skey;
-  s.pos = s_pos;
-  s.has_gauss = s_has_gauss;
-  s.gauss = s_gauss;
-  s.heap = s_heap;
-  s.heap_cap = dim + 1;
   const int64_t rec0 = (int64_t)b * max_records;
   s.out = des::OutSoa{value + rec0, event_id + rec0, node + rec0, kind + rec0};
   s.out_cap = max_records;
   s.max_records = max_records;
-  s.draws_left = (int64_t)DES_DRAW_FACTOR * (max_events + dim + 1);
-  s.reset();
-
-  // ---- all lanes: parameters to LDS, the global generator's words
-  for (int i = lane; i < dim; i += GDM_WAVE) {
-    s_loc[i] = loc[(int64_t)b * dim + i];
-    s_scale[i] = scale[(int64_t)b * dim + i];
-    s_qcap[i] = queue_cap[(int64_t)b * dim + i];
-  }
-  for (int i = lane; i < DES_MT_N; i += GDM_WAVE) s_gkey[i] = mt_key[(int64_t)b * DES_MT_N + i];
-  __syncthreads();
-  // ---- one node per lane: source flags and routing tables
-  s.setup_nodes(adj + (int64_t)b * dim * dim, lane, GDM_WAVE);
-  __syncthreads();
-  // ---- lane 0: the checks of the batch entries, then the seeder's draws
-  if (lane == 0) {
-    const int64_t sd = seed[b];
-    const int32_t p0 = mt_pos[b];
-    const int ok = s.spec_ok(sd, p0) ? 1 : 0;
-    s_ok = ok;
-    if (ok) {
-      s.draw_node_seeds((uint32_t)sd, s_node_seed);
-      s_pos[dim] = p0;
-      s_has_gauss[dim] = mt_has_gauss[b];
-      s_gauss[dim] = mt_gauss[b];
-    }
-  }
-  __syncthreads();
-  const int ok = s_ok;
-  // ---- one generator per lane: init_genrand
-  if (ok) s.seed_nodes(s_node_seed, lane, GDM_WAVE);
-  __syncthreads();
+  // ---- all lanes: the shared prologue (des_wave.h)
+  const bool ok = des_wave::prologue(s, lds, s_dyn, ws, w, b, lane, adj, dim, loc, scale, queue_cap, seed, max_queue_cap,
+                                     max_events, mt_key, mt_pos, mt_has_gauss, mt_gauss);
   // ---- lane 0: the chain
   if (lane == 0) {
     int reason = DES_STOP_ERROR;
     int64_t n = 0;
     if (ok) {
       reason = s.run(number_of_customers[b], max_events);
-      mt_pos[b] = s_pos[dim];
-      mt_has_gauss[b] = s_has_gauss[dim];
-      mt_gauss[b] = s_gauss[dim];
+      des_wave::store_generator_scalars(lds, dim, b, mt_pos, mt_has_gauss, mt_gauss);
       n = reason == DES_STOP_ERROR ? 0 : (s.n_out < max_records ? s.n_out : max_records);
     }
     n_records[b] = n;
     stop_reason[b] = reason;
   }
   __syncthreads();
-  if (ok)
-    for (int i = lane; i < DES_MT_N; i += GDM_WAVE) mt_key[(int64_t)b * DES_MT_N + i] = s_gkey[i];
+  if (ok) des_wave::store_generator_words(lds, b, lane, mt_key);
 }
 
 // counts -> rec_ptr (exclusive scan, one workgroup), then the records of sample b move from b * max_records down to
@@ -213,7 +139,7 @@ __global__ void des_math_probe_kernel(const double* __restrict__ x, int64_t n, d
 
 extern "C" int64_t gdm_des_batch_workspace_bytes(int B, int dim, int max_queue_cap) {
   if (B < 1 || dim < 1 || dim > kMaxDim || max_queue_cap < 1 || max_queue_cap > GDM_DES_BATCH_MAX_QUEUE_CAP) return -1;
-  return (int64_t)(ws_layout(dim, max_queue_cap).per_sample * (size_t)B);
+  return (int64_t)(ws_layout(dim, max_queue_cap, false).per_sample * (size_t)B);
 }
 
 extern "C" int gdm_des_run_batch(const double* adj, int B, int dim, const double* loc, const double* scale,
@@ -241,7 +167,7 @@ extern "C" int gdm_des_run_batch(const double* adj, int B, int dim, const double
     gdm_set_error("gdm_des_run_batch: workspace too small or not 16-byte aligned (%lld bytes needed)", (long long)need);
     return GDM_EWORKSPACE;
   }
-  const size_t lds_dyn = dim <= kLdsGenDim ? (size_t)dim * DES_MT_N * 4 : 0;
+  const size_t lds_dyn = des_wave::lds_dyn_bytes(dim);
   hipLaunchKernelGGL(des_batch_kernel, dim3(B), dim3(GDM_WAVE), lds_dyn, (hipStream_t)stream, adj, dim, loc, scale,
                      queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records, mt_key, mt_pos,
                      has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,

@@ -38,9 +38,9 @@ struct MathLibm {
 static_assert(sizeof(des::OutAos::Rec) == sizeof(gdm_des_event), "record layout");
 
 // Host storage of one simulation, sized from the spec
-template <class Math, class Out>
+template <class Math, class Out, class Stats = des::NoStats>
 struct HostSim {
-  des::Sim<Math, Out> s;
+  des::Sim<Math, Out, Stats> s;
   std::vector<uint8_t> is_source, bflags;
   std::vector<int32_t> in_service, qhead, qlen, nchild, children, pos, has_gauss;
   std::vector<double> cdf, gauss;
@@ -136,6 +136,75 @@ int run_batch_host(const double* adj, int B, int dim, const double* loc, const d
   return GDM_OK;
 }
 
+// The statistics mode: the same chain with the null sink and the accumulators of des::NodeStats writing straight into
+// the caller's (B, dim) rows; what des_stats.hip runs one wave per sample.
+struct StatsOut {
+  int64_t *served, *reneges, *generated;
+  int32_t* max_queue;
+  double *time_in_service, *time_in_queue, *queue_area, *arrival_time, *clock, *end_time;
+  int64_t *total_customers, *events, *n_records;
+  int32_t* stop_reason;
+  double* queue_time;
+};
+
+template <class Math>
+void stats_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                      const int32_t* queue_cap, const int64_t* seed, const int64_t* number_of_customers,
+                      int max_queue_cap, int64_t max_events, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                      double* cached_gauss, const StatsOut& o) {
+  HostSim<Math, des::OutNone, des::NodeStats> h(dim, max_queue_cap);
+  std::vector<double> atime((size_t)dim * max_queue_cap), last_change(dim);
+  const int64_t hist_stride = (int64_t)max_queue_cap + 1;
+  for (int b = 0; b < B; ++b) {
+    des::Sim<Math, des::OutNone, des::NodeStats>& s = h.s;
+    const size_t row = (size_t)b * dim;
+    s.out_cap = INT64_MAX;
+    s.max_records = 0;
+    s.draws_left = (int64_t)DES_DRAW_FACTOR * (max_events + dim + 1);
+    s.loc = loc + row;
+    s.scale = scale + row;
+    s.qcap = queue_cap + row;
+    des::NodeStats& st = s.stats;
+    st.served = o.served + row;
+    st.reneges = o.reneges + row;
+    st.generated = o.generated + row;
+    st.max_queue = o.max_queue + row;
+    st.time_in_service = o.time_in_service + row;
+    st.time_in_queue = o.time_in_queue + row;
+    st.queue_area = o.queue_area + row;
+    st.arrival_time = o.arrival_time + row;
+    st.last_change = last_change.data();
+    st.atime = atime.data();
+    st.queue_time = o.queue_time ? o.queue_time + row * hist_stride : nullptr;
+    st.ring_stride = max_queue_cap;
+    st.hist_stride = hist_stride;
+    st.reset(dim, 0, 1);
+    if (st.queue_time) std::memset(st.queue_time, 0, sizeof(double) * (size_t)dim * hist_stride);
+    int reason = DES_STOP_ERROR;
+    if (s.spec_ok(seed[b], mt_pos[b])) {
+      h.prepare(adj + row * dim, s.loc, s.scale, s.qcap, (uint32_t)seed[b], mt_key + (size_t)b * DES_MT_N, mt_pos[b],
+                has_gauss[b], cached_gauss[b]);
+      reason = s.run(number_of_customers[b], max_events);
+    }
+    const bool keep = reason != DES_STOP_ERROR;           // a sample that errors: zeros, its generator as it came
+    if (keep) {
+      std::memcpy(mt_key + (size_t)b * DES_MT_N, s.global_key, DES_MT_N * sizeof(uint32_t));
+      mt_pos[b] = s.pos[dim];
+      has_gauss[b] = s.has_gauss[dim];
+      cached_gauss[b] = s.gauss[dim];
+    } else {
+      st.reset(dim, 0, 1);
+      if (st.queue_time) std::memset(st.queue_time, 0, sizeof(double) * (size_t)dim * hist_stride);
+    }
+    o.clock[b] = keep ? s.clock : 0.0;
+    o.end_time[b] = keep ? st.end_time : 0.0;
+    o.total_customers[b] = keep ? s.total_customers : 0;
+    o.events[b] = keep ? st.events : 0;
+    o.n_records[b] = keep ? s.n_out : 0;
+    o.stop_reason[b] = reason;
+  }
+}
+
 }  // namespace
 
 extern "C" int gdm_des_run(const double* adj, int dim, const double* loc, const double* scale, const int32_t* queue_cap,
@@ -219,5 +288,37 @@ extern "C" int gdm_des_math_probe_host(const double* x, int64_t n, double* log_o
     log_out[i] = l;
     factor_out[i] = des::MathPortable::sqrt(-2.0 * l / x[i]);
   }
+  return GDM_OK;
+}
+
+extern "C" int gdm_des_stats_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                        const int32_t* queue_cap, const int64_t* seed,
+                                        const int64_t* number_of_customers, int max_queue_cap, int math,
+                                        int64_t max_events, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                                        double* cached_gauss, int64_t* served, int64_t* reneges, int64_t* generated,
+                                        int32_t* max_queue, double* time_in_service, double* time_in_queue,
+                                        double* queue_area, double* arrival_time, double* clock, double* end_time,
+                                        int64_t* total_customers, int64_t* events, int64_t* n_records,
+                                        int32_t* stop_reason, double* queue_time) {
+  GDM_REQUIRE(adj && loc && scale && queue_cap && seed && number_of_customers && mt_key && mt_pos && has_gauss &&
+                  cached_gauss && served && reneges && generated && max_queue && time_in_service && time_in_queue &&
+                  queue_area && arrival_time && clock && end_time && total_customers && events && n_records &&
+                  stop_reason,
+              "gdm_des_stats_batch_host: null pointer");
+  GDM_REQUIRE(B >= 1 && dim >= 1 && dim <= GDM_DES_BATCH_HOST_MAX_DIM && max_queue_cap >= 1 &&
+                  max_queue_cap <= GDM_DES_BATCH_MAX_QUEUE_CAP,
+              "gdm_des_stats_batch_host: B >= 1, 1 <= dim <= %d, 1 <= max_queue_cap <= %d", GDM_DES_BATCH_HOST_MAX_DIM,
+              GDM_DES_BATCH_MAX_QUEUE_CAP);
+  GDM_REQUIRE(max_events >= 1 && max_events <= GDM_DES_BATCH_MAX_EVENTS,
+              "gdm_des_stats_batch_host: max_events must be in 1..%lld", (long long)GDM_DES_BATCH_MAX_EVENTS);
+  GDM_REQUIRE(math == 0 || math == 1, "gdm_des_stats_batch_host: math must be 0 (libm) or 1 (portable)");
+  const StatsOut o{served, reneges, generated, max_queue, time_in_service, time_in_queue, queue_area, arrival_time,
+                   clock, end_time, total_customers, events, n_records, stop_reason, queue_time};
+  if (math == 0)
+    stats_batch_host<MathLibm>(adj, B, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events,
+                               mt_key, mt_pos, has_gauss, cached_gauss, o);
+  else
+    stats_batch_host<des::MathPortable>(adj, B, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap,
+                                        max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
   return GDM_OK;
 }

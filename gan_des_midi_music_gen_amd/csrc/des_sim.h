@@ -26,6 +26,10 @@
 // per event is out of reach of a healthy run and stops `while service <= 0` for loc << 0 after a bounded time
 // (DES_STOP_BUDGET).  gdm_des_run passes INT64_MAX: today's behaviour.
 //
+// What a run leaves behind is two more policies.  Out is the record sink: the 'Music' log as an array of structs, as four
+// field arrays, or nothing at all (OutNone).  Stats is the accumulator set: NoStats (empty, every hook a no-op: the logging
+// builds) or NodeStats, the per-node queueing statistics of the reference's Server / Source objects.
+//
 // Math is a policy (template parameter): log / sqrt of the polar method.  DesMathPortable is plain double arithmetic
 // (+ - * / and bit manipulation, contraction off, no FMA) and gives the same bits on the host and on gfx950; the host
 // core of gdm_des_run uses libm's (what numpy calls), which no portable implementation can match bit for bit.
@@ -197,7 +201,89 @@ struct OutSoa {
   }
 };
 
-template <class Math, class Out>
+// No records at all (the statistics mode): Sim::n_out keeps counting, so the number of records the run would have
+// written is a free statistic.
+struct OutNone {
+  DES_HD void put(int64_t, double, int64_t, int, int) const {}
+};
+
+// ---- statistics policies: the accumulators every Server / Source of the reference carries (simulation_v3.py:207-217,
+// 280-281), driven by hooks at the reference's own lines.  NoStats is empty, every hook a no-op: the logging builds.
+struct NoStats {
+  DES_HD void pop(double) const {}
+  DES_HD void event() const {}
+  DES_HD void service(int, double) const {}
+  DES_HD void renege(int) const {}
+  DES_HD void generate(int, double) const {}
+  DES_HD void enqueue(int, int64_t, double, int64_t) const {}
+  DES_HD void dequeue(int, int64_t, double, int64_t) const {}
+  DES_HD void finish(const uint8_t*, const int32_t*, int) const {}
+};
+
+// Storage is the caller's: (dim) per array, atime (dim, ring_stride) beside the id ring and indexed like it, queue_time
+// (dim, hist_stride) or null.  served .. arrival_time are accumulated in the reference's order and can match it bit
+// for bit.  Time at queue length is NOT summed per popped event over all servers as the reference does (472-484, an
+// O(dim) loop): a server's share is added when its queue length changes and once at the end, (t - last_change) at a
+// time, t = the time of the last popped event -- the same sum in exact arithmetic, rounded differently.
+struct NodeStats {
+  int64_t* served;            // total_customers_served (596)
+  int64_t* reneges;           // 564
+  int64_t* generated;         // customers_generated (530, 579)
+  int32_t* max_queue;         // max_queue_length (560-561)
+  double* time_in_service;    // total_time_in_service (606)
+  double* time_in_queue;      // total_time_in_queue (641)
+  double* queue_area;         // sum over k of k * queue_length_times[k]
+  double* arrival_time;       // Source.arrival_times (526, 578)
+  double* last_change;        // scratch: when the node's queue length last changed
+  double* atime;              // (dim, ring_stride): Event.arrival_time of the queued customers (558)
+  double* queue_time;         // (dim, hist_stride): queue_length_times, dense; null = not wanted
+  int64_t ring_stride, hist_stride;
+  double end_time;            // the reference's previous_time: the time of the last popped event
+  int64_t events;             // processed events
+
+  DES_HD void reset(int dim, int first, int step) {
+    for (int i = first; i < dim; i += step) {
+      served[i] = reneges[i] = generated[i] = 0;
+      max_queue[i] = 0;
+      time_in_service[i] = time_in_queue[i] = queue_area[i] = arrival_time[i] = last_change[i] = 0.0;
+    }
+    end_time = 0.0;
+    events = 0;
+  }
+  DES_HD void pop(double t) { end_time = t; }
+  DES_HD void event() { ++events; }
+  DES_HD void service(int node, double s) {
+    ++served[node];
+    time_in_service[node] += s;
+  }
+  DES_HD void renege(int node) { ++reneges[node]; }
+  DES_HD void generate(int source, double dt) {
+    arrival_time[source] += dt;
+    ++generated[source];
+  }
+  DES_HD void integrate(int node, double t, int64_t len) {
+    const double d = t - last_change[node];
+    queue_area[node] += d * (double)len;
+    if (queue_time && len >= 0 && len < hist_stride) queue_time[(int64_t)node * hist_stride + len] += d;
+    last_change[node] = t;
+  }
+  // slot: the ring slot Sim checked and used for the customer's id; len: the queue length before the change
+  DES_HD void enqueue(int node, int64_t slot, double t, int64_t len) {
+    atime[(int64_t)node * ring_stride + slot] = t;
+    integrate(node, t, len);
+    if (len + 1 > (int64_t)max_queue[node]) max_queue[node] = (int32_t)(len + 1);
+  }
+  DES_HD void dequeue(int node, int64_t slot, double t, int64_t len) {
+    time_in_queue[node] += t - atime[(int64_t)node * ring_stride + slot];
+    integrate(node, t, len);
+  }
+  DES_HD void finish(const uint8_t* is_source, const int32_t* qlen, int dim) {
+    for (int i = 0; i < dim; ++i)
+      if (!is_source[i]) integrate(i, end_time, qlen[i]);
+  }
+};
+
+template <class Math, class Out, class Stats = NoStats>
 struct Sim {
   // ---- storage, set by the caller ----
   int dim;
@@ -223,6 +309,7 @@ struct Sim {
   Ev* heap;
   int heap_cap;
   Out out;
+  Stats stats;
   int64_t out_cap;
   int64_t max_records;        // 0 = no cap
   int64_t draws_left;
@@ -434,6 +521,7 @@ struct Sim {
     if (scale[server_id] == 0.0 && loc[server_id] <= 0.0) { fail(); return; }   // upstream: the loop never ends
     while (service <= 0 && !stop) service = norm_rvs(server_id);
     if (stop) return;
+    stats.service(server_id, service);
     log(service, event_id, server_id, 2);
     if (stop) return;
     push(Ev{clock + service, event_id, 2, server_id, -1, 0});
@@ -453,10 +541,14 @@ struct Sim {
       if (slot < 0 || slot >= ring_stride) { fail(); return; }
       ring[(int64_t)server_id * ring_stride + slot] = id;
       qlen[server_id] = (int32_t)(n + 1);
-    }                                                  // else: the customer reneges
+      stats.enqueue(server_id, slot, clock, n);
+    } else {
+      stats.renege(server_id);                         // the customer reneges
+    }
     if (source >= 0) {
       const double dt = norm_rvs(source);
       if (stop) return;
+      stats.generate(source, dt);
       push(Ev{clock + dt, total_customers, 1, server_id, source, 0});
       ++total_customers;
     }
@@ -482,6 +574,7 @@ struct Sim {
         if (h < 0 || h >= ring_stride) { fail(); return; }
         const int64_t customer = ring[(int64_t)server_id * ring_stride + h];
         qhead[server_id] = (int32_t)(h + 1 >= ring_stride ? 0 : h + 1);
+        stats.dequeue(server_id, h, clock, qlen[server_id]);
         --qlen[server_id];
         schedule_departure(server_id, customer);
         if (stop) return;
@@ -501,6 +594,7 @@ struct Sim {
       if (!is_source[i]) continue;
       const double dt = norm_rvs(i);
       if (stop) break;
+      stats.generate(i, dt);
       const int next = destination(i);
       if (stop) break;
       push(Ev{clock + dt, total_customers, 1, next, i, 0});
@@ -510,12 +604,15 @@ struct Sim {
     int64_t processed = 0;
     while (!stop && heap_n > 0) {
       const Ev evt = pop();
+      stats.pop(evt.time);                             // counted in the time integration before the break (472-486)
       if (total_customers > number_of_customers - 1) { reason = DES_STOP_CUSTOMERS; break; }
       clock = evt.time;
+      stats.event();
       if (evt.type == 1) process_arrival(evt.server, evt.source, evt.id);
       else process_departure(evt.server, evt.id);
       if (++processed >= max_events && max_events > 0) { reason = DES_STOP_EVENTS; break; }   // (reference: wall clock)
     }
+    stats.finish(is_source, qlen, dim);
     return stop ? stop : reason;
   }
 };

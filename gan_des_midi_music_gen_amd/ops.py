@@ -1102,6 +1102,53 @@ def des_run_batch(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, h
     return value, event_id, node, kind, rec_ptr, n_records, stop
 
 
+# ---- the same simulator without a log: per-node queueing statistics (csrc/des_stats.hip) ------------------------------------
+DES_STATS_NODE_FIELDS = (("served", torch.int64), ("reneges", torch.int64), ("generated", torch.int64),
+                         ("max_queue", torch.int32), ("time_in_service", torch.float64),
+                         ("time_in_queue", torch.float64), ("queue_area", torch.float64),
+                         ("arrival_time", torch.float64))                                      # (B, dim)
+DES_STATS_SAMPLE_FIELDS = (("clock", torch.float64), ("end_time", torch.float64), ("total_customers", torch.int64),
+                           ("events", torch.int64), ("n_records", torch.int64), ("stop_reason", torch.int32))   # (B)
+
+
+def des_stats_workspace_bytes(b, dim, max_queue_cap):
+    n = _lib.load().gdm_des_stats_workspace_bytes(int(b), int(dim), int(max_queue_cap))
+    if n < 0:
+        raise GdmError(f"des_run_stats: B={b}, dim={dim}, max_queue_cap={max_queue_cap} out of range")
+    return n
+
+
+def des_run_stats(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *, max_queue_cap,
+                  max_events=200000, histogram=False, workspace_tensor=None):
+    """B simulations in one launch, no records: the device tensors of ``des_run_batch`` in (generator states UPDATED
+    IN PLACE) -> dict of device tensors: DES_STATS_NODE_FIELDS (B,dim), DES_STATS_SAMPLE_FIELDS (B) and ``queue_time``
+    (B,dim,max_queue_cap+1) f64, the time spent at every queue length, or None without ``histogram``.  Nothing is read
+    back."""
+    _need_gpu(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss)
+    if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
+        raise GdmError("des_run_stats: adj must be (B, dim, dim)")
+    b, dim = adj.shape[0], adj.shape[1]
+    for t, shape, dt in ((adj, (b, dim, dim), torch.float64), (loc, (b, dim), torch.float64),
+                         (scale, (b, dim), torch.float64), (queue_cap, (b, dim), torch.int32), (seed, (b,), torch.int64),
+                         (customers, (b,), torch.int64), (mt_key, (b, 624), torch.int32), (mt_pos, (b,), torch.int32),
+                         (has_gauss, (b,), torch.int32), (gauss, (b,), torch.float64)):
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise GdmError(f"des_run_stats: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
+                           f"{tuple(t.shape)}")
+    dev = adj.device
+    out = {name: torch.empty((b, dim), dtype=dt, device=dev) for name, dt in DES_STATS_NODE_FIELDS}
+    out.update({name: torch.empty(b, dtype=dt, device=dev) for name, dt in DES_STATS_SAMPLE_FIELDS})
+    out["queue_time"] = (torch.empty((b, dim, int(max_queue_cap) + 1), dtype=torch.float64, device=dev) if histogram
+                         else None)
+    need = des_stats_workspace_bytes(b, dim, max_queue_cap)
+    ws = workspace(need, dev) if workspace_tensor is None else workspace_tensor
+    _call("gdm_des_stats_batch", _p(adj), b, dim, _p(loc), _p(scale), _p(queue_cap), _p(seed), _p(customers),
+          int(max_queue_cap), int(max_events), _p(mt_key), _p(mt_pos), _p(has_gauss), _p(gauss),
+          *(_p(out[name]) for name, _dt in DES_STATS_NODE_FIELDS + DES_STATS_SAMPLE_FIELDS), _p(out["queue_time"]),
+          _p(ws), ws.numel(), _stream())
+    return out
+
+
 def des_pack(n_records, rec_ptr, value, event_id, node, kind, max_records):
     """The pack step of ``des_run_batch`` alone, in place (device tensors as ``des_run_batch`` returns them)."""
     _need_gpu(n_records, rec_ptr, value, event_id, node, kind)

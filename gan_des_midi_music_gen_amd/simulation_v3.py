@@ -30,6 +30,18 @@ Differences, on purpose:
     In both cases the reference fails when it takes the event off the list, before the arrival is logged; the records
     written up to that point stay in its log file, while ``Sim.run`` here returns nothing.
 
+  * the queueing statistics of the reference's ``Server`` / ``Source`` objects and ``Sim.calculate_metrics`` (752-824) are
+    not attributes of ``Sim`` (``record_history`` stays refused) but the result of a log-free batched run: ``run_stats``
+    / ``run_stats_host`` / ``run_stats_device`` return the accumulators as arrays with a leading B (``BatchStats``),
+    ``metrics`` the derived quantities under the reference's names, NaN where the reference has no dict entry (and
+    where it raises ZeroDivisionError because ``Clock == 0``), ``replicate`` their mean / std / sem over seeded runs of
+    one net.  Counts and the sums the reference accumulates once per event (service, queue and inter-arrival times,
+    ``Clock``) are the reference's bits with ``math=0``; the time spent at each queue length is integrated when a
+    queue changes instead of on every event for every server (472-484), the same sum rounded differently (a few
+    1e-16 relative; tests/test_des_stats.py).  ``clock`` is the reference's ``Clock`` and ``end_time`` its
+    ``previous_time``: the event that triggers the ``number_of_customers`` stop is counted in the time integration
+    but ``Clock`` is not advanced to it.  A sample that ends in an error returns zeros and keeps its generator state.
+
 ``run_batch`` / ``run_batch_host`` simulate B specs of one size at once, every sample FROM ITS OWN snapshot of numpy's
 global stream (``gdm_des_run_batch`` on a HIP device: one wave per sample, csrc/des_batch.hip; ``gdm_des_run_batch_host``
 on the host).  Both run the event logic of csrc/des_sim.h, the same source ``gdm_des_run`` is compiled from.  With
@@ -319,6 +331,202 @@ def run_batch(specs, *, device=None, max_events=200000, max_records=5001, states
     if device is None:
         return run_batch_host(*arrays, states, math=1, max_events=max_events, max_records=max_records)
     return run_batch_device(*arrays, states, device=device, max_events=max_events, max_records=max_records)
+
+
+# ---- batched statistics: the same runs without a log ---------------------------------------------------------------------
+STATS_NODE_FIELDS = ("served", "reneges", "generated", "max_queue", "time_in_service", "time_in_queue", "queue_area",
+                     "arrival_time")
+STATS_SAMPLE_FIELDS = ("clock", "end_time", "total_customers", "events", "n_records", "stop_reason")
+BatchStats = collections.namedtuple("BatchStats", STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS +
+                                    ("queue_time", "is_source", "mt_key", "mt_pos", "has_gauss", "gauss"))
+BatchStats.__doc__ = """Per-node accumulators of B simulations (``gdm_des_stats_batch[_host]``, include/gdm.h): (B,dim)
+served, reneges, generated (int64), max_queue (int32), time_in_service, time_in_queue, queue_area, arrival_time
+(float64); (B) clock, end_time (float64), total_customers, events, n_records (int64), stop_reason (int32); queue_time
+(B,dim,max_queue_cap+1) float64 or None; is_source (B,dim) bool; the generator states after the runs as in BatchLog."""
+_STATS_DTYPES = dict(served=np.int64, reneges=np.int64, generated=np.int64, max_queue=np.int32,
+                     time_in_service=np.float64, time_in_queue=np.float64, queue_area=np.float64,
+                     arrival_time=np.float64, clock=np.float64, end_time=np.float64, total_customers=np.int64,
+                     events=np.int64, n_records=np.int64, stop_reason=np.int32)
+
+
+def run_stats_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, math=1, max_events=200000,
+                   max_queue_cap=None, histogram=False):
+    """``gdm_des_stats_batch_host`` on the numpy arrays of ``run_batch_host``: the same runs, no records -> BatchStats
+    of numpy arrays.  math 0 = libm (the reference's bits), 1 = portable (the device's bits)."""
+    lib = _lib.load()
+    adj = np.ascontiguousarray(adj, dtype=np.float64)
+    b, dim = adj.shape[0], adj.shape[1]
+    assert adj.shape == (b, dim, dim), adj.shape
+    loc = np.ascontiguousarray(loc, dtype=np.float64).reshape(b, dim)
+    scale = np.ascontiguousarray(scale, dtype=np.float64).reshape(b, dim)
+    queue_cap = np.ascontiguousarray(queue_cap, dtype=np.int32).reshape(b, dim)
+    seed = np.ascontiguousarray(seed, dtype=np.int64).reshape(b)
+    customers = np.ascontiguousarray(customers, dtype=np.int64).reshape(b)
+    k, p, h, g = (np.array(a) for a in pack_states(states, b))
+    if max_queue_cap is None:
+        max_queue_cap = max(1, int(queue_cap.max()))
+    out = {n: np.zeros((b, dim), dtype=_STATS_DTYPES[n]) for n in STATS_NODE_FIELDS}
+    out.update({n: np.zeros(b, dtype=_STATS_DTYPES[n]) for n in STATS_SAMPLE_FIELDS})
+    hist = np.zeros((b, dim, int(max_queue_cap) + 1), dtype=np.float64) if histogram else None
+    rc = lib.gdm_des_stats_batch_host(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data, queue_cap.ctypes.data,
+                                      seed.ctypes.data, customers.ctypes.data, int(max_queue_cap), int(math),
+                                      int(max_events), k.ctypes.data, p.ctypes.data, h.ctypes.data, g.ctypes.data,
+                                      *(out[n].ctypes.data for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS),
+                                      hist.ctypes.data if histogram else None)
+    _lib.check(rc, "gdm_des_stats_batch_host")
+    is_source = np.diagonal(adj, axis1=1, axis2=2) > 0
+    return BatchStats(*(out[n] for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS), hist, is_source, k, p, h, g)
+
+
+def run_stats_device(adj, loc, scale, queue_cap, seed, customers, states=None, *, device, max_events=200000,
+                     max_queue_cap=None, histogram=False, workspace_tensor=None):
+    """``gdm_des_stats_batch``: the arrays of ``run_batch_device`` (numpy, or device tensors that stay where they are --
+    ``adj`` straight from ``ops.des_routing``) -> BatchStats of device tensors, bit-identical to
+    ``run_stats_host(math=1)``.  Nothing is read back."""
+    import torch
+    from . import ops
+    dev = torch.device(device)
+
+    def up(a, dt):
+        if torch.is_tensor(a):
+            return a.to(device=dev, dtype=dt).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(dt).contiguous()
+
+    b = adj.shape[0]
+    if max_queue_cap is None:
+        if torch.is_tensor(queue_cap):
+            raise ValueError("run_stats_device: pass max_queue_cap with a device queue_cap (it sizes the workspace)")
+        max_queue_cap = max(1, int(np.asarray(queue_cap).max()))
+    if isinstance(states, (tuple, list)) and len(states) == 4 and torch.is_tensor(states[0]):
+        k, p, h, g = (up(t, dt) for t, dt in zip(states, (torch.int32, torch.int32, torch.int32, torch.float64)))
+    else:
+        key, pos, has, gauss = pack_states(states, b)
+        k, p, h, g = (up(key.view(np.int32), torch.int32), up(pos, torch.int32), up(has, torch.int32),
+                      up(gauss, torch.float64))
+    adj = up(adj, torch.float64)
+    out = ops.des_run_stats(adj, up(loc, torch.float64), up(scale, torch.float64), up(queue_cap, torch.int32),
+                            up(seed, torch.int64), up(customers, torch.int64), k, p, h, g, max_queue_cap=max_queue_cap,
+                            max_events=max_events, histogram=histogram, workspace_tensor=workspace_tensor)
+    is_source = torch.diagonal(adj, dim1=1, dim2=2) > 0
+    return BatchStats(*(out[n] for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS), out["queue_time"], is_source, k, p, h,
+                      g)
+
+
+def run_stats(specs, *, device=None, max_events=200000, states=None, histogram=False):
+    """``run_batch`` without a log: B ``DesSpec`` of one size, each from its own generator state -> BatchStats (numpy
+    arrays from the host mirror with portable math for device=None, device tensors with the same bits otherwise)."""
+    arrays = spec_arrays(specs)
+    if device is None:
+        return run_stats_host(*arrays, states, math=1, max_events=max_events, histogram=histogram)
+    return run_stats_device(*arrays, states, device=device, max_events=max_events, histogram=histogram)
+
+
+METRIC_NAMES = ("avg_time_at_server", "avg_queue_time", "server_utilizations", "max_queue_lengths", "renege_rate",
+                "service_times", "arrival_times", "customers_served_per_server", "avg_queue_length",
+                "avg_server_length")
+TOTAL_NAMES = ("total_U", "total_L", "total_LQ", "total_W", "total_WQ")
+
+
+def metrics(stats):
+    """The quantities of the reference's ``Sim.calculate_metrics`` (752-801) from a BatchStats, after one read-back:
+    dict of float64 numpy arrays under the reference's names -- METRIC_NAMES (B,dim), ``queue_length_probabilities``
+    (B,dim,K+1) when the histogram exists, TOTAL_NAMES (B) with the reference's formulas as written (797-801: total_L
+    counts the utilisations, total_W the queue times twice).  NaN where the reference has no entry: a server that
+    served nobody (its dict comprehensions leave it out), a server quantity on a source and the other way round, and
+    every per-time quantity where ``clock == 0`` (ZeroDivisionError upstream).  Totals are ``nansum``s."""
+    def host(a):
+        return None if a is None else np.asarray(a.cpu() if hasattr(a, "cpu") else a)
+
+    st = BatchStats(*(host(a) for a in stats))
+    f = np.float64
+    server = ~st.is_source.astype(bool)
+    busy = server & (st.served > 0)
+    nan = np.full(st.served.shape, np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        def per(num, den, where):
+            return np.where(where, np.asarray(num, dtype=f) / np.asarray(den, dtype=f), nan)
+
+        ticking = (st.clock != 0)[:, None]
+        clock = st.clock[:, None]
+        m = {
+            "avg_time_at_server": per(st.time_in_service + st.time_in_queue, st.served, busy),
+            "avg_queue_time": per(st.time_in_queue, st.served, busy),
+            "server_utilizations": per(st.time_in_service, clock, server & ticking),
+            "max_queue_lengths": np.where(server, st.max_queue.astype(f), nan),
+            "renege_rate": per(st.reneges, st.served, busy),
+            "service_times": per(st.time_in_service, st.served, busy),
+            "arrival_times": per(st.arrival_time, st.generated, ~server & (st.generated > 0)),
+            "customers_served_per_server": np.where(server, st.served.astype(f), nan),
+            "avg_queue_length": per(st.queue_area, clock, server & ticking),
+        }
+        m["avg_server_length"] = m["avg_queue_length"] + m["server_utilizations"]
+        if st.queue_time is not None:
+            m["queue_length_probabilities"] = np.where((server & ticking)[:, :, None],
+                                                       st.queue_time / clock[:, :, None], np.nan)
+    per_time = np.where(st.clock != 0, 0.0, np.nan)
+    u, lq = np.nansum(m["server_utilizations"], axis=1), np.nansum(m["avg_queue_length"], axis=1)
+    w, wq = np.nansum(m["avg_time_at_server"], axis=1), np.nansum(m["avg_queue_time"], axis=1)
+    m["total_U"] = u + per_time
+    m["total_L"] = (lq + u) + per_time
+    m["total_LQ"] = lq + per_time
+    m["total_W"] = w + wq
+    m["total_WQ"] = wq
+    return m
+
+
+Replications = collections.namedtuple("Replications", "stats metrics mean std sem n valid")
+Replications.__doc__ = """``replicate``'s result: the BatchStats and ``metrics`` of the R runs, and per metric name the
+``mean``, ``std`` (ddof 1), ``sem`` = std / sqrt(n) and ``n`` over the runs of ``valid`` (R) bool -- those that stopped
+neither with an error nor on the draw budget -- that have a value (are not NaN) at that node."""
+
+
+def replication_states(seeds):
+    """The default global stream of replication r: ``np.random.RandomState([seeds[r], 1])``.  Array seeding
+    (init_by_array), so it is neither ``RandomState(seeds[r])`` -- the stream the per-node seeds are drawn from -- nor
+    any node's own stream."""
+    return [np.random.RandomState([int(s), 1]).get_state() for s in seeds]
+
+
+def replicate(spec, seeds, *, device=None, max_events=200000, states=None):
+    """R = len(seeds) seeded runs of ONE net (a ``DesSpec``; its own ``seeds`` are not used) in one batch, then
+    ``metrics`` and their mean / std (ddof 1) / sem / n over the replications -> Replications.  ``states``: the R global
+    generator states (default ``replication_states(seeds)``).  No interval is formed: sem and n are what one needs."""
+    from . import ops
+    seeds = [int(s) for s in np.asarray(seeds).reshape(-1)]
+    r = len(seeds)
+    if r == 0:
+        raise ValueError("replicate: no seeds")
+    if any(d[0] != "normal" for d in spec.distributions):
+        raise NotImplementedError("replicate: the deterministic core implements 'normal' distributions only")
+    one = np.asarray(spec.sim_matrix, dtype=np.float64)
+    dim = one.shape[0]
+    adj = np.ascontiguousarray(np.broadcast_to(one, (r, dim, dim)))
+    loc = np.tile(np.array([float(d[1]) for d in spec.distributions], dtype=np.float64), (r, 1))
+    scale = np.tile(np.array([float(d[2]) for d in spec.distributions], dtype=np.float64), (r, 1))
+    qcap = np.tile(np.asarray(list(spec.queue_list), dtype=np.int32), (r, 1))
+    customers = np.full(r, int(spec.num_customers), dtype=np.int64)
+    if states is None:
+        states = replication_states(seeds)
+    arrays = (adj, loc, scale, qcap, np.asarray(seeds, dtype=np.int64), customers, states)
+    if device is None:
+        stats = run_stats_host(*arrays, math=1, max_events=max_events)
+    else:
+        stats = run_stats_device(*arrays, device=device, max_events=max_events)
+    m = metrics(stats)
+    stop = np.asarray(stats.stop_reason.cpu() if hasattr(stats.stop_reason, "cpu") else stats.stop_reason)
+    valid = (stop != ops.DES_STOP_ERROR) & (stop != ops.DES_STOP_BUDGET)
+    mean, std, sem, n = {}, {}, {}, {}
+    for name, a in m.items():
+        a = a[valid]
+        have = ~np.isnan(a)
+        n[name] = have.sum(axis=0)
+        total = np.where(have, a, 0.0).sum(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean[name] = np.where(n[name] > 0, total / n[name], np.nan)
+            dev2 = np.where(have, (a - mean[name]) ** 2, 0.0).sum(axis=0)
+            std[name] = np.where(n[name] > 1, np.sqrt(dev2 / (n[name] - 1)), np.nan)
+            sem[name] = std[name] / np.sqrt(n[name])
+    return Replications(stats, m, mean, std, sem, n, valid)
 
 
 def math_probe_host(x):

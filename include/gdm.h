@@ -462,6 +462,53 @@ int gdm_des_pack(int B, int64_t max_records, const int64_t* n_records, int64_t* 
 int gdm_des_math_probe_host(const double* x, int64_t n, double* log_out, double* factor_out);
 int gdm_des_math_probe(const double* x, int64_t n, double* log_out, double* factor_out, void* stream);
 
+/* ---- the batched simulator WITHOUT a log: per-node queueing statistics (csrc/des_stats.hip, csrc/des_sim.h) ----------
+ * The same event chain as gdm_des_run_batch[_host] -- same inputs, same generator states in and out, same stop reasons
+ * (never GDM_DES_STOP_RECORDS: there is no record cap) -- that writes no records and returns the accumulators the
+ * reference's Server / Source objects carry after Sim.run (SIMULATOR/simulation_v3.py:207-217, 280-281), the inputs of
+ * Sim.calculate_metrics (752-824).  (B, dim) arrays, a server's entries zero on a source row and the other way round:
+ *   served          i64  total_customers_served, ScheduleDeparture :596
+ *   time_in_service f64  total_time_in_service, += service in event order, :606
+ *   reneges         i64  the else branch of ProcessArrival, :564
+ *   max_queue       i32  max_queue_length, the queue size after an enqueue, :560-561
+ *   time_in_queue   f64  total_time_in_queue, += Clock - arrival_time at the dequeue in event order, :641 (:558)
+ *   arrival_time    f64  Source.arrival_times, Initialization :526 and ProcessArrival :578
+ *   generated       i64  Source.customers_generated, :530 and :579
+ *   queue_area      f64  sum over k of k * queue_length_times[k] (:768 before the division by Clock)
+ * and optionally queue_time (B, dim, max_queue_cap + 1) f64 = queue_length_times as a dense array (NULL: skipped).
+ * The reference adds evt.time - previous_time to queue_length_times[queue.size()] of EVERY server on every popped
+ * event (:472-484); here a server's share is added when its queue length changes and once at the end, so queue_area
+ * and queue_time are the same sums rounded differently; the other arrays are accumulated in the reference's order.
+ * (B) arrays: clock f64 = the reference's Clock and end_time f64 = its previous_time -- the event that triggers the
+ * number_of_customers stop is popped and counted in the time integration (:472-484 run before the break at :486) but
+ * Clock is not advanced to it; the final flush goes to end_time --; total_customers, events (processed), n_records
+ * (the records the logging entries would have written, uncapped) i64; stop_reason i32.
+ * A sample that stops with GDM_DES_STOP_ERROR returns zeros in every statistic and keeps the generator state it came
+ * with.
+ * gdm_des_stats_batch_host: host arrays, dim <= GDM_DES_BATCH_HOST_MAX_DIM, math 0 = libm, 1 = portable.
+ * gdm_des_stats_batch: device arrays, portable math, bit-identical to the host entry with math = 1; one wave per
+ *   sample, accumulators in LDS, one launch.  dim <= GDM_DES_BATCH_MAX_DIM; arrays aligned to their element size;
+ *   workspace: 16-byte aligned device memory of gdm_des_stats_workspace_bytes(B, dim, max_queue_cap) bytes (the layout
+ *   of gdm_des_batch_workspace_bytes plus the ring of arrival times; -1 for arguments out of range).  Everything is
+ *   validated on the host before the launch (GDM_EINVAL, no launch).                                                 */
+int gdm_des_stats_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                             const int32_t* queue_cap, const int64_t* seed, const int64_t* number_of_customers,
+                             int max_queue_cap, int math, int64_t max_events, uint32_t* mt_key, int32_t* mt_pos,
+                             int32_t* has_gauss, double* cached_gauss, int64_t* served, int64_t* reneges,
+                             int64_t* generated, int32_t* max_queue, double* time_in_service, double* time_in_queue,
+                             double* queue_area, double* arrival_time, double* clock, double* end_time,
+                             int64_t* total_customers, int64_t* events, int64_t* n_records, int32_t* stop_reason,
+                             double* queue_time);
+int64_t gdm_des_stats_workspace_bytes(int B, int dim, int max_queue_cap);
+int gdm_des_stats_batch(const double* adj, int B, int dim, const double* loc, const double* scale,
+                        const int32_t* queue_cap, const int64_t* seed, const int64_t* number_of_customers,
+                        int max_queue_cap, int64_t max_events, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                        double* cached_gauss, int64_t* served, int64_t* reneges, int64_t* generated,
+                        int32_t* max_queue, double* time_in_service, double* time_in_queue, double* queue_area,
+                        double* arrival_time, double* clock, double* end_time, int64_t* total_customers,
+                        int64_t* events, int64_t* n_records, int32_t* stop_reason, double* queue_time, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ---- generic convolution lowering helpers (model 2 discriminator, model 1 generator) ----------------------------
  * im2col for Conv2d fwd / dW and col2im (gather form, deterministic) for Conv2d dX and ConvTranspose2d fwd.
  * Activations are channels-last (B,H,W,C) unless `src_planar` (NCHW fp32 input planes, e.g. the piano-roll).
