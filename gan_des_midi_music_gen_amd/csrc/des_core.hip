@@ -38,9 +38,9 @@ struct MathLibm {
 static_assert(sizeof(des::OutAos::Rec) == sizeof(gdm_des_event), "record layout");
 
 // Host storage of one simulation, sized from the spec
-template <class Math, class Out, class Stats = des::NoStats>
+template <class Math, class Out, class Stats = des::NoStats, class Dist = des::NormalOnly>
 struct HostSim {
-  des::Sim<Math, Out, Stats> s;
+  des::Sim<Math, Out, Stats, Dist> s;
   std::vector<uint8_t> is_source, bflags;
   std::vector<int32_t> in_service, qhead, qlen, nchild, children, pos, has_gauss;
   std::vector<double> cdf, gauss;
@@ -137,7 +137,8 @@ int run_batch_host(const double* adj, int B, int dim, const double* loc, const d
 }
 
 // The statistics mode: the same chain with the null sink and the accumulators of des::NodeStats writing straight into
-// the caller's (B, dim) rows; what des_stats.hip runs one wave per sample.
+// the caller's (B, dim) rows; what des_stats.hip runs one wave per sample.  Dist = des::NormalOnly for
+// gdm_des_stats_batch_host (kind is not read), des::AnyDist for gdm_des_stats_batch_dist_host.
 struct StatsOut {
   int64_t *served, *reneges, *generated;
   int32_t* max_queue;
@@ -147,17 +148,22 @@ struct StatsOut {
   double* queue_time;
 };
 
-template <class Math>
-void stats_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+// the kinds of sample b, where the policy has any
+inline void bind_kind(des::NormalOnly&, const int32_t*, size_t) {}
+inline void bind_kind(des::AnyDist& d, const int32_t* kind, size_t row) { d.kind = kind + row; }
+
+template <class Math, class Dist>
+void stats_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale, const int32_t* kind,
                       const int32_t* queue_cap, const int64_t* seed, const int64_t* number_of_customers,
                       int max_queue_cap, int64_t max_events, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
                       double* cached_gauss, const StatsOut& o) {
-  HostSim<Math, des::OutNone, des::NodeStats> h(dim, max_queue_cap);
+  HostSim<Math, des::OutNone, des::NodeStats, Dist> h(dim, max_queue_cap);
   std::vector<double> atime((size_t)dim * max_queue_cap), last_change(dim);
   const int64_t hist_stride = (int64_t)max_queue_cap + 1;
   for (int b = 0; b < B; ++b) {
-    des::Sim<Math, des::OutNone, des::NodeStats>& s = h.s;
+    des::Sim<Math, des::OutNone, des::NodeStats, Dist>& s = h.s;
     const size_t row = (size_t)b * dim;
+    bind_kind(s.dist, kind, row);
     s.out_cap = INT64_MAX;
     s.max_records = 0;
     s.draws_left = (int64_t)DES_DRAW_FACTOR * (max_events + dim + 1);
@@ -203,6 +209,26 @@ void stats_batch_host(const double* adj, int B, int dim, const double* loc, cons
     o.n_records[b] = keep ? s.n_out : 0;
     o.stop_reason[b] = reason;
   }
+}
+
+// the argument checks of both host statistics entries; `who` names the entry in the message
+int check_stats_host(const char* who, const double* adj, int B, int dim, const double* loc, const double* scale,
+                     const int32_t* queue_cap, const int64_t* seed, const int64_t* number_of_customers,
+                     int max_queue_cap, int math, int64_t max_events, const uint32_t* mt_key, const int32_t* mt_pos,
+                     const int32_t* has_gauss, const double* cached_gauss, const StatsOut& o) {
+  GDM_REQUIRE(adj && loc && scale && queue_cap && seed && number_of_customers && mt_key && mt_pos && has_gauss &&
+                  cached_gauss && o.served && o.reneges && o.generated && o.max_queue && o.time_in_service &&
+                  o.time_in_queue && o.queue_area && o.arrival_time && o.clock && o.end_time && o.total_customers &&
+                  o.events && o.n_records && o.stop_reason,
+              "%s: null pointer", who);
+  GDM_REQUIRE(B >= 1 && dim >= 1 && dim <= GDM_DES_BATCH_HOST_MAX_DIM && max_queue_cap >= 1 &&
+                  max_queue_cap <= GDM_DES_BATCH_MAX_QUEUE_CAP,
+              "%s: B >= 1, 1 <= dim <= %d, 1 <= max_queue_cap <= %d", who, GDM_DES_BATCH_HOST_MAX_DIM,
+              GDM_DES_BATCH_MAX_QUEUE_CAP);
+  GDM_REQUIRE(max_events >= 1 && max_events <= GDM_DES_BATCH_MAX_EVENTS, "%s: max_events must be in 1..%lld", who,
+              (long long)GDM_DES_BATCH_MAX_EVENTS);
+  GDM_REQUIRE(math == 0 || math == 1, "%s: math must be 0 (libm) or 1 (portable)", who);
+  return GDM_OK;
 }
 
 }  // namespace
@@ -300,25 +326,49 @@ extern "C" int gdm_des_stats_batch_host(const double* adj, int B, int dim, const
                                         double* queue_area, double* arrival_time, double* clock, double* end_time,
                                         int64_t* total_customers, int64_t* events, int64_t* n_records,
                                         int32_t* stop_reason, double* queue_time) {
-  GDM_REQUIRE(adj && loc && scale && queue_cap && seed && number_of_customers && mt_key && mt_pos && has_gauss &&
-                  cached_gauss && served && reneges && generated && max_queue && time_in_service && time_in_queue &&
-                  queue_area && arrival_time && clock && end_time && total_customers && events && n_records &&
-                  stop_reason,
-              "gdm_des_stats_batch_host: null pointer");
-  GDM_REQUIRE(B >= 1 && dim >= 1 && dim <= GDM_DES_BATCH_HOST_MAX_DIM && max_queue_cap >= 1 &&
-                  max_queue_cap <= GDM_DES_BATCH_MAX_QUEUE_CAP,
-              "gdm_des_stats_batch_host: B >= 1, 1 <= dim <= %d, 1 <= max_queue_cap <= %d", GDM_DES_BATCH_HOST_MAX_DIM,
-              GDM_DES_BATCH_MAX_QUEUE_CAP);
-  GDM_REQUIRE(max_events >= 1 && max_events <= GDM_DES_BATCH_MAX_EVENTS,
-              "gdm_des_stats_batch_host: max_events must be in 1..%lld", (long long)GDM_DES_BATCH_MAX_EVENTS);
-  GDM_REQUIRE(math == 0 || math == 1, "gdm_des_stats_batch_host: math must be 0 (libm) or 1 (portable)");
   const StatsOut o{served, reneges, generated, max_queue, time_in_service, time_in_queue, queue_area, arrival_time,
                    clock, end_time, total_customers, events, n_records, stop_reason, queue_time};
+  const int rc = check_stats_host("gdm_des_stats_batch_host", adj, B, dim, loc, scale, queue_cap, seed,
+                                  number_of_customers, max_queue_cap, math, max_events, mt_key, mt_pos, has_gauss,
+                                  cached_gauss, o);
+  if (rc != GDM_OK) return rc;
   if (math == 0)
-    stats_batch_host<MathLibm>(adj, B, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events,
-                               mt_key, mt_pos, has_gauss, cached_gauss, o);
+    stats_batch_host<MathLibm, des::NormalOnly>(adj, B, dim, loc, scale, nullptr, queue_cap, seed, number_of_customers,
+                                                max_queue_cap, max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
   else
-    stats_batch_host<des::MathPortable>(adj, B, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap,
-                                        max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
+    stats_batch_host<des::MathPortable, des::NormalOnly>(adj, B, dim, loc, scale, nullptr, queue_cap, seed,
+                                                         number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,
+                                                         has_gauss, cached_gauss, o);
+  return GDM_OK;
+}
+
+extern "C" int gdm_des_stats_batch_dist_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                             const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
+                                             const int64_t* number_of_customers, int max_queue_cap, int math,
+                                             int64_t max_events, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                                             double* cached_gauss, int64_t* served, int64_t* reneges,
+                                             int64_t* generated, int32_t* max_queue, double* time_in_service,
+                                             double* time_in_queue, double* queue_area, double* arrival_time,
+                                             double* clock, double* end_time, int64_t* total_customers,
+                                             int64_t* events, int64_t* n_records, int32_t* stop_reason,
+                                             double* queue_time) {
+  const StatsOut o{served, reneges, generated, max_queue, time_in_service, time_in_queue, queue_area, arrival_time,
+                   clock, end_time, total_customers, events, n_records, stop_reason, queue_time};
+  GDM_REQUIRE(kind, "gdm_des_stats_batch_dist_host: null pointer");
+  const int rc = check_stats_host("gdm_des_stats_batch_dist_host", adj, B, dim, loc, scale, queue_cap, seed,
+                                  number_of_customers, max_queue_cap, math, max_events, mt_key, mt_pos, has_gauss,
+                                  cached_gauss, o);
+  if (rc != GDM_OK) return rc;
+  for (int64_t i = 0; i < (int64_t)B * dim; ++i)
+    GDM_REQUIRE(kind[i] >= GDM_DES_DIST_NORMAL && kind[i] <= GDM_DES_DIST_UNIFORM,
+                "gdm_des_stats_batch_dist_host: kind %d at sample %lld, node %lld is none of GDM_DES_DIST_*", kind[i],
+                (long long)(i / dim), (long long)(i % dim));
+  if (math == 0)
+    stats_batch_host<MathLibm, des::AnyDist>(adj, B, dim, loc, scale, kind, queue_cap, seed, number_of_customers,
+                                             max_queue_cap, max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
+  else
+    stats_batch_host<des::MathPortable, des::AnyDist>(adj, B, dim, loc, scale, kind, queue_cap, seed,
+                                                      number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,
+                                                      has_gauss, cached_gauss, o);
   return GDM_OK;
 }

@@ -30,6 +30,9 @@
 // field arrays, or nothing at all (OutNone).  Stats is the accumulator set: NoStats (empty, every hook a no-op: the logging
 // builds) or NodeStats, the per-node queueing statistics of the reference's Server / Source objects.
 //
+// Dist is the distribution policy: NormalOnly (empty: every draw is norm_rvs, the bridges' nets) or AnyDist, a kind per
+// node -- normal, exponential or uniform.
+//
 // Math is a policy (template parameter): log / sqrt of the polar method.  DesMathPortable is plain double arithmetic
 // (+ - * / and bit manipulation, contraction off, no FMA) and gives the same bits on the host and on gfx950; the host
 // core of gdm_des_run uses libm's (what numpy calls), which no portable implementation can match bit for bit.
@@ -41,6 +44,9 @@
 #else
 #define DES_HD
 #endif
+// a policy's hooks are part of the function that calls them, whatever the inliner's budget says: a NormalOnly build is
+// the code it was before there were distribution policies, and an AnyDist build keeps its Sim in registers
+#define DES_HOOK DES_HD inline __attribute__((always_inline))
 
 #ifdef __clang__
 #pragma clang fp contract(off)
@@ -283,8 +289,45 @@ struct NodeStats {
   }
 };
 
-template <class Math, class Out, class Stats = NoStats>
+// ---- distribution policies: what a node's service / inter-arrival time is drawn from.  NormalOnly is empty and makes
+// the three draw sites today's norm_rvs (the logging builds, the bridges' nets).  AnyDist carries one kind per node and
+// adds the two kinds of the reference's Server / Source (simulation_v3.py:181-192, 263-274) that are ONE uniform double
+// on the node's legacy stream, in scipy's own order of operations (`vals * scale + loc`, rv_continuous.rvs):
+//   kind 1 'exponential'  stats.expon(scale=s).rvs(random_state=rng)      = (-log(1.0 - rng.random_sample())) * s + 0.0
+//   kind 2 'uniform'      stats.uniform(loc, s).rvs(random_state=rng)     = rng.random_sample() * s + loc
+// scale == 0 returns loc (0.0 for the exponential, whatever loc[] holds) and draws nothing, as scipy does.
+#define DES_DIST_NORMAL 0
+#define DES_DIST_EXPONENTIAL 1
+#define DES_DIST_UNIFORM 2
+struct NormalOnly {
+  template <class S>
+  DES_HOOK double rvs(S& s, int node) const { return s.norm_rvs(node); }
+  // with scale == 0 the node's value is 0.0 whatever loc[] holds (schedule_departure: `while (service <= 0)`)
+  DES_HOOK bool ignores_loc(int) const { return false; }
+  DES_HOOK bool kinds_ok(int) const { return true; }
+};
+struct AnyDist {
+  const int32_t* kind;        // (dim) DES_DIST_*
+  template <class S>
+  DES_HOOK double rvs(S& s, int node) const {
+    const int32_t k = kind[node];
+    if (k == DES_DIST_NORMAL) return s.norm_rvs(node);
+    if (s.scale[node] == 0.0) return k == DES_DIST_EXPONENTIAL ? 0.0 : s.loc[node];
+    const double u = s.next_double(node);                 // both are one uniform double
+    if (k == DES_DIST_EXPONENTIAL) return (-S::math::log(1.0 - u)) * s.scale[node] + 0.0;
+    return u * s.scale[node] + s.loc[node];
+  }
+  DES_HOOK bool ignores_loc(int node) const { return kind[node] == DES_DIST_EXPONENTIAL; }
+  DES_HOOK bool kinds_ok(int dim) const {
+    for (int i = 0; i < dim; ++i)
+      if (kind[i] < DES_DIST_NORMAL || kind[i] > DES_DIST_UNIFORM) return false;
+    return true;
+  }
+};
+
+template <class Math, class Out, class Stats = NoStats, class Dist = NormalOnly>
 struct Sim {
+  typedef Math math;
   // ---- storage, set by the caller ----
   int dim;
   const double* loc;          // (dim)
@@ -310,6 +353,7 @@ struct Sim {
   int heap_cap;
   Out out;
   Stats stats;
+  Dist dist;
   int64_t out_cap;
   int64_t max_records;        // 0 = no cap
   int64_t draws_left;
@@ -426,12 +470,13 @@ struct Sim {
     }
   }
   // what the batch entries require of one sample before anything runs (a refused sample stops with DES_STOP_ERROR and
-  // leaves the generator state as it came): scale >= 0, every queue fits its ring, a 32-bit seed, a valid position
+  // leaves the generator state as it came): scale >= 0, every queue fits its ring, a 32-bit seed, a valid position,
+  // every kind one of DES_DIST_*
   DES_HD bool spec_ok(int64_t seed, int32_t global_pos) const {
     if (seed < 0 || seed > 0xffffffffLL || global_pos < 0 || global_pos > DES_MT_N) return false;
     for (int i = 0; i < dim; ++i)
       if (!(scale[i] >= 0) || (int64_t)qcap[i] > ring_stride) return false;
-    return true;
+    return dist.kinds_ok(dim);
   }
   // per-node generator seeds (451-461): servers first, then sources, each in ascending node order
   DES_HD void draw_node_seeds(uint32_t seed, uint32_t* node_seed) {
@@ -518,8 +563,9 @@ struct Sim {
   DES_HD void schedule_departure(int server_id, int64_t event_id) {     // 591-612
     in_service[server_id] = 1;
     double service = 0.0;
-    if (scale[server_id] == 0.0 && loc[server_id] <= 0.0) { fail(); return; }   // upstream: the loop never ends
-    while (service <= 0 && !stop) service = norm_rvs(server_id);
+    // upstream: the loop never ends -- no draw is made (scale 0: nothing counts against the budget) and the value is <= 0
+    if (scale[server_id] == 0.0 && (dist.ignores_loc(server_id) || loc[server_id] <= 0.0)) { fail(); return; }
+    while (service <= 0 && !stop) service = dist.rvs(*this, server_id);
     if (stop) return;
     stats.service(server_id, service);
     log(service, event_id, server_id, 2);
@@ -546,7 +592,7 @@ struct Sim {
       stats.renege(server_id);                         // the customer reneges
     }
     if (source >= 0) {
-      const double dt = norm_rvs(source);
+      const double dt = dist.rvs(*this, source);
       if (stop) return;
       stats.generate(source, dt);
       push(Ev{clock + dt, total_customers, 1, server_id, source, 0});
@@ -592,7 +638,7 @@ struct Sim {
   DES_HD int run(int64_t number_of_customers, int64_t max_events) {
     for (int i = 0; i < dim && !stop; ++i) {
       if (!is_source[i]) continue;
-      const double dt = norm_rvs(i);
+      const double dt = dist.rvs(*this, i);
       if (stop) break;
       stats.generate(i, dt);
       const int next = destination(i);

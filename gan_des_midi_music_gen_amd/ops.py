@@ -1118,22 +1118,21 @@ def des_stats_workspace_bytes(b, dim, max_queue_cap):
     return n
 
 
-def des_run_stats(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *, max_queue_cap,
-                  max_events=200000, histogram=False, workspace_tensor=None):
-    """B simulations in one launch, no records: the device tensors of ``des_run_batch`` in (generator states UPDATED
-    IN PLACE) -> dict of device tensors: DES_STATS_NODE_FIELDS (B,dim), DES_STATS_SAMPLE_FIELDS (B) and ``queue_time``
-    (B,dim,max_queue_cap+1) f64, the time spent at every queue length, or None without ``histogram``.  Nothing is read
-    back."""
-    _need_gpu(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss)
+def _des_run_stats(who, kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, max_queue_cap,
+                   max_events, histogram, workspace_tensor):
+    """``des_run_stats`` (kind None: gdm_des_stats_batch) and ``des_run_stats_dist`` (gdm_des_stats_batch_dist)."""
+    _need_gpu(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss,
+              *(() if kind is None else (kind,)))
     if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
-        raise GdmError("des_run_stats: adj must be (B, dim, dim)")
+        raise GdmError(f"{who}: adj must be (B, dim, dim)")
     b, dim = adj.shape[0], adj.shape[1]
     for t, shape, dt in ((adj, (b, dim, dim), torch.float64), (loc, (b, dim), torch.float64),
                          (scale, (b, dim), torch.float64), (queue_cap, (b, dim), torch.int32), (seed, (b,), torch.int64),
                          (customers, (b,), torch.int64), (mt_key, (b, 624), torch.int32), (mt_pos, (b,), torch.int32),
-                         (has_gauss, (b,), torch.int32), (gauss, (b,), torch.float64)):
+                         (has_gauss, (b,), torch.int32), (gauss, (b,), torch.float64)) + \
+                        (() if kind is None else ((kind, (b, dim), torch.int32),)):
         if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
-            raise GdmError(f"des_run_stats: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
+            raise GdmError(f"{who}: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
                            f"{tuple(t.shape)}")
     dev = adj.device
     out = {name: torch.empty((b, dim), dtype=dt, device=dev) for name, dt in DES_STATS_NODE_FIELDS}
@@ -1142,11 +1141,34 @@ def des_run_stats(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, h
                          else None)
     need = des_stats_workspace_bytes(b, dim, max_queue_cap)
     ws = workspace(need, dev) if workspace_tensor is None else workspace_tensor
-    _call("gdm_des_stats_batch", _p(adj), b, dim, _p(loc), _p(scale), _p(queue_cap), _p(seed), _p(customers),
+    _call("gdm_des_stats_batch" if kind is None else "gdm_des_stats_batch_dist", _p(adj), b, dim, _p(loc), _p(scale),
+          *(() if kind is None else (_p(kind),)), _p(queue_cap), _p(seed), _p(customers),
           int(max_queue_cap), int(max_events), _p(mt_key), _p(mt_pos), _p(has_gauss), _p(gauss),
           *(_p(out[name]) for name, _dt in DES_STATS_NODE_FIELDS + DES_STATS_SAMPLE_FIELDS), _p(out["queue_time"]),
           _p(ws), ws.numel(), _stream())
     return out
+
+
+def des_run_stats(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *, max_queue_cap,
+                  max_events=200000, histogram=False, workspace_tensor=None):
+    """B simulations in one launch, no records: the device tensors of ``des_run_batch`` in (generator states UPDATED
+    IN PLACE) -> dict of device tensors: DES_STATS_NODE_FIELDS (B,dim), DES_STATS_SAMPLE_FIELDS (B) and ``queue_time``
+    (B,dim,max_queue_cap+1) f64, the time spent at every queue length, or None without ``histogram``.  Nothing is read
+    back."""
+    return _des_run_stats("des_run_stats", None, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss,
+                          gauss, max_queue_cap, max_events, histogram, workspace_tensor)
+
+
+DES_DIST_NORMAL, DES_DIST_EXPONENTIAL, DES_DIST_UNIFORM = range(3)       # GDM_DES_DIST_*
+
+
+def des_run_stats_dist(adj, loc, scale, kind, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *,
+                       max_queue_cap, max_events=200000, histogram=False, workspace_tensor=None):
+    """``des_run_stats`` with a distribution kind per node (``kind`` (B,dim) int32 of DES_DIST_*; ``loc`` is not read
+    where a node is exponential): ``gdm_des_stats_batch_dist``, one launch.  A kind outside 0..2 ends that sample with
+    DES_STOP_ERROR."""
+    return _des_run_stats("des_run_stats_dist", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
+                          has_gauss, gauss, max_queue_cap, max_events, histogram, workspace_tensor)
 
 
 def des_pack(n_records, rec_ptr, value, event_id, node, kind, max_records):

@@ -17,7 +17,8 @@ Differences, on purpose:
     WALL CLOCK (simulation_v3.py:496-499: the reference's results depend on how fast the machine is; ``max_sim_time`` is
     accepted and ignored);
   * only what the bridges construct is supported: 'normal' distributions, ``logging_mode='Music'``, probability routing
-    (no 'queue' / 'branch' nodes, no animation, no metric history) -- anything else raises NotImplementedError;
+    (no 'queue' / 'branch' nodes, no animation, no metric history) -- anything else raises NotImplementedError (the
+    log-free statistics run below also takes 'exponential' and 'uniform' nodes);
   * the log records are also kept as arrays (``sim.music_log``), so a caller need not go through the log file;
   * where the reference's run ends in an exception, ``Sim.run`` raises ValueError with the core's message, and a sample
     of ``run_batch`` / ``run_batch_host`` ends with stop reason 3 ("error") and an empty log, its neighbours untouched
@@ -41,6 +42,16 @@ Differences, on purpose:
     1e-16 relative; tests/test_des_stats.py).  ``clock`` is the reference's ``Clock`` and ``end_time`` its
     ``previous_time``: the event that triggers the ``number_of_customers`` stop is counted in the time integration
     but ``Clock`` is not advanced to it.  A sample that ends in an error returns zeros and keeps its generator state.
+  * the statistics run -- not ``Sim``, ``run_batch`` or the bridges -- takes nodes of DIST_KINDS: ``['normal', loc, s]``,
+    ``['exponential', s]`` and ``['uniform', loc, s]`` as the reference's ``Server`` / ``Source`` construct them
+    (181-192, 263-274).  The last two are ONE uniform double on the node's stream, in scipy's order of operations:
+    ``(-log(1.0 - u)) * s + 0.0`` and ``u * s + loc``; ``s == 0`` returns loc (0.0) without a draw.  ``dist_arrays``
+    parses specs, ``run_stats_host`` / ``run_stats_device`` take ``kind=``, ``run_stats`` / ``replicate`` route to the
+    entries with kinds (``gdm_des_stats_batch_dist[_host]``) only when some node is not normal.  Where the reference
+    would never return -- a server whose every draw is <= 0 without consuming draws: an exponential with scale 0, a
+    uniform with scale 0 and loc <= 0 -- the sample stops with reason 3; a uniform whose support is <= 0 ends on the
+    draw budget.  ``mm1k_sweep`` puts the simulated M/M/1/K beside ``queueing_theory.mm1k`` (tests/golden/des_dist.npz
+    records the reference's own runs of the same nets; ``tools/des_validate.py`` prints the table).
 
 ``run_batch`` / ``run_batch_host`` simulate B specs of one size at once, every sample FROM ITS OWN snapshot of numpy's
 global stream (``gdm_des_run_batch`` on a HIP device: one wave per sample, csrc/des_batch.hip; ``gdm_des_run_batch_host``
@@ -255,6 +266,47 @@ def spec_arrays(specs):
     return adj, loc, scale, qcap, seed, customers
 
 
+DIST_KINDS = ("normal", "exponential", "uniform")     # GDM_DES_DIST_*: the index is the kind
+
+
+def dist_row(distributions, who="dist_arrays"):
+    """One spec's ``distributions`` -> (kind, loc, scale) lists: ``['normal', loc, s]`` and ``['uniform', loc, s]`` as
+    written, ``['exponential', s]`` as loc 0, scale s (scipy's ``expon(scale=s)``).  NotImplementedError names any
+    other kind."""
+    kind, loc, scale = [], [], []
+    for d in distributions:
+        if d[0] not in DIST_KINDS:
+            raise NotImplementedError(f"{who}: distribution {d[0]!r} (the statistics entries implement "
+                                      f"{', '.join(DIST_KINDS)})")
+        kind.append(DIST_KINDS.index(d[0]))
+        loc.append(0.0 if d[0] == "exponential" else float(d[1]))
+        scale.append(float(d[1]) if d[0] == "exponential" else float(d[2]))
+    return kind, loc, scale
+
+
+def dist_arrays(specs):
+    """``spec_arrays`` for specs whose nodes may be any of DIST_KINDS -> (adj, kind, loc, scale, queue_cap, seed,
+    customers) numpy arrays with a leading B; kind (B,dim) int32, the index into DIST_KINDS."""
+    if len(specs) == 0:
+        raise ValueError("run_stats: no specs")
+    dim = np.asarray(specs[0].sim_matrix).shape[0]
+    rows = []
+    for sp in specs:
+        if np.asarray(sp.sim_matrix).shape != (dim, dim) or len(sp.distributions) != dim or len(sp.queue_list) != dim:
+            raise ValueError("run_stats: every spec of a batch must have the same number of nodes")
+        if np.asarray(sp.seeds).size != 1:
+            raise ValueError("run_stats: one seed (one run) per spec")
+        rows.append(dist_row(sp.distributions, "run_stats"))
+    adj = np.ascontiguousarray([np.asarray(sp.sim_matrix, dtype=np.float64) for sp in specs])
+    kind = np.ascontiguousarray([r[0] for r in rows], dtype=np.int32)
+    loc = np.ascontiguousarray([r[1] for r in rows], dtype=np.float64)
+    scale = np.ascontiguousarray([r[2] for r in rows], dtype=np.float64)
+    qcap = np.ascontiguousarray([list(sp.queue_list) for sp in specs], dtype=np.int32)
+    seed = np.ascontiguousarray([int(np.asarray(sp.seeds).reshape(-1)[0]) for sp in specs], dtype=np.int64)
+    customers = np.ascontiguousarray([int(sp.num_customers) for sp in specs], dtype=np.int64)
+    return adj, kind, loc, scale, qcap, seed, customers
+
+
 def run_batch_device(adj, loc, scale, queue_cap, seed, customers, states=None, *, device, max_events=200000,
                      max_records=5001, max_queue_cap=None, workspace_tensor=None):
     """``gdm_des_run_batch``: the arrays of ``run_batch_host`` (numpy, or device tensors that stay where they are --
@@ -350,9 +402,10 @@ _STATS_DTYPES = dict(served=np.int64, reneges=np.int64, generated=np.int64, max_
 
 
 def run_stats_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, math=1, max_events=200000,
-                   max_queue_cap=None, histogram=False):
+                   max_queue_cap=None, histogram=False, kind=None):
     """``gdm_des_stats_batch_host`` on the numpy arrays of ``run_batch_host``: the same runs, no records -> BatchStats
-    of numpy arrays.  math 0 = libm (the reference's bits), 1 = portable (the device's bits)."""
+    of numpy arrays.  math 0 = libm (the reference's bits), 1 = portable (the device's bits).  ``kind`` (B,dim), the
+    index into DIST_KINDS per node: ``gdm_des_stats_batch_dist_host``; None: every node is normal."""
     lib = _lib.load()
     adj = np.ascontiguousarray(adj, dtype=np.float64)
     b, dim = adj.shape[0], adj.shape[1]
@@ -368,21 +421,28 @@ def run_stats_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, 
     out = {n: np.zeros((b, dim), dtype=_STATS_DTYPES[n]) for n in STATS_NODE_FIELDS}
     out.update({n: np.zeros(b, dtype=_STATS_DTYPES[n]) for n in STATS_SAMPLE_FIELDS})
     hist = np.zeros((b, dim, int(max_queue_cap) + 1), dtype=np.float64) if histogram else None
-    rc = lib.gdm_des_stats_batch_host(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data, queue_cap.ctypes.data,
-                                      seed.ctypes.data, customers.ctypes.data, int(max_queue_cap), int(math),
-                                      int(max_events), k.ctypes.data, p.ctypes.data, h.ctypes.data, g.ctypes.data,
-                                      *(out[n].ctypes.data for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS),
-                                      hist.ctypes.data if histogram else None)
-    _lib.check(rc, "gdm_des_stats_batch_host")
+    tail = (queue_cap.ctypes.data, seed.ctypes.data, customers.ctypes.data, int(max_queue_cap), int(math),
+            int(max_events), k.ctypes.data, p.ctypes.data, h.ctypes.data, g.ctypes.data,
+            *(out[n].ctypes.data for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS),
+            hist.ctypes.data if histogram else None)
+    if kind is None:
+        rc = lib.gdm_des_stats_batch_host(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data, *tail)
+        _lib.check(rc, "gdm_des_stats_batch_host")
+    else:
+        kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(b, dim)
+        rc = lib.gdm_des_stats_batch_dist_host(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data,
+                                               kind.ctypes.data, *tail)
+        _lib.check(rc, "gdm_des_stats_batch_dist_host")
     is_source = np.diagonal(adj, axis1=1, axis2=2) > 0
     return BatchStats(*(out[n] for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS), hist, is_source, k, p, h, g)
 
 
 def run_stats_device(adj, loc, scale, queue_cap, seed, customers, states=None, *, device, max_events=200000,
-                     max_queue_cap=None, histogram=False, workspace_tensor=None):
+                     max_queue_cap=None, histogram=False, workspace_tensor=None, kind=None):
     """``gdm_des_stats_batch``: the arrays of ``run_batch_device`` (numpy, or device tensors that stay where they are --
     ``adj`` straight from ``ops.des_routing``) -> BatchStats of device tensors, bit-identical to
-    ``run_stats_host(math=1)``.  Nothing is read back."""
+    ``run_stats_host(math=1)``.  Nothing is read back.  ``kind`` as in ``run_stats_host``: ``gdm_des_stats_batch_dist``,
+    the kernel that draws normal, exponential and uniform nodes."""
     import torch
     from . import ops
     dev = torch.device(device)
@@ -404,9 +464,13 @@ def run_stats_device(adj, loc, scale, queue_cap, seed, customers, states=None, *
         k, p, h, g = (up(key.view(np.int32), torch.int32), up(pos, torch.int32), up(has, torch.int32),
                       up(gauss, torch.float64))
     adj = up(adj, torch.float64)
-    out = ops.des_run_stats(adj, up(loc, torch.float64), up(scale, torch.float64), up(queue_cap, torch.int32),
-                            up(seed, torch.int64), up(customers, torch.int64), k, p, h, g, max_queue_cap=max_queue_cap,
-                            max_events=max_events, histogram=histogram, workspace_tensor=workspace_tensor)
+    tail = (up(queue_cap, torch.int32), up(seed, torch.int64), up(customers, torch.int64), k, p, h, g)
+    kw = dict(max_queue_cap=max_queue_cap, max_events=max_events, histogram=histogram, workspace_tensor=workspace_tensor)
+    if kind is None:
+        out = ops.des_run_stats(adj, up(loc, torch.float64), up(scale, torch.float64), *tail, **kw)
+    else:
+        out = ops.des_run_stats_dist(adj, up(loc, torch.float64), up(scale, torch.float64), up(kind, torch.int32), *tail,
+                                     **kw)
     is_source = torch.diagonal(adj, dim1=1, dim2=2) > 0
     return BatchStats(*(out[n] for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS), out["queue_time"], is_source, k, p, h,
                       g)
@@ -414,11 +478,13 @@ def run_stats_device(adj, loc, scale, queue_cap, seed, customers, states=None, *
 
 def run_stats(specs, *, device=None, max_events=200000, states=None, histogram=False):
     """``run_batch`` without a log: B ``DesSpec`` of one size, each from its own generator state -> BatchStats (numpy
-    arrays from the host mirror with portable math for device=None, device tensors with the same bits otherwise)."""
-    arrays = spec_arrays(specs)
+    arrays from the host mirror with portable math for device=None, device tensors with the same bits otherwise).
+    Nodes may be any of DIST_KINDS (``dist_arrays``); the entries with kinds run only when some node is not normal."""
+    adj, kind, *rest = dist_arrays(specs)
+    kw = dict(max_events=max_events, histogram=histogram, kind=kind if kind.any() else None)   # all normal: as ever
     if device is None:
-        return run_stats_host(*arrays, states, math=1, max_events=max_events, histogram=histogram)
-    return run_stats_device(*arrays, states, device=device, max_events=max_events, histogram=histogram)
+        return run_stats_host(adj, *rest, states, math=1, **kw)
+    return run_stats_device(adj, *rest, states, device=device, **kw)
 
 
 METRIC_NAMES = ("avg_time_at_server", "avg_queue_time", "server_utilizations", "max_queue_lengths", "renege_rate",
@@ -489,29 +555,30 @@ def replication_states(seeds):
 
 def replicate(spec, seeds, *, device=None, max_events=200000, states=None):
     """R = len(seeds) seeded runs of ONE net (a ``DesSpec``; its own ``seeds`` are not used) in one batch, then
-    ``metrics`` and their mean / std (ddof 1) / sem / n over the replications -> Replications.  ``states``: the R global
+    ``metrics`` and their mean / std (ddof 1) / sem / n over the replications -> Replications.  Nodes may be any of
+    DIST_KINDS.  ``states``: the R global
     generator states (default ``replication_states(seeds)``).  No interval is formed: sem and n are what one needs."""
     from . import ops
     seeds = [int(s) for s in np.asarray(seeds).reshape(-1)]
     r = len(seeds)
     if r == 0:
         raise ValueError("replicate: no seeds")
-    if any(d[0] != "normal" for d in spec.distributions):
-        raise NotImplementedError("replicate: the deterministic core implements 'normal' distributions only")
+    kinds, locs, scales = dist_row(spec.distributions, "replicate")
     one = np.asarray(spec.sim_matrix, dtype=np.float64)
     dim = one.shape[0]
     adj = np.ascontiguousarray(np.broadcast_to(one, (r, dim, dim)))
-    loc = np.tile(np.array([float(d[1]) for d in spec.distributions], dtype=np.float64), (r, 1))
-    scale = np.tile(np.array([float(d[2]) for d in spec.distributions], dtype=np.float64), (r, 1))
+    loc = np.tile(np.array(locs, dtype=np.float64), (r, 1))
+    scale = np.tile(np.array(scales, dtype=np.float64), (r, 1))
+    kind = np.tile(np.array(kinds, dtype=np.int32), (r, 1)) if any(kinds) else None
     qcap = np.tile(np.asarray(list(spec.queue_list), dtype=np.int32), (r, 1))
     customers = np.full(r, int(spec.num_customers), dtype=np.int64)
     if states is None:
         states = replication_states(seeds)
     arrays = (adj, loc, scale, qcap, np.asarray(seeds, dtype=np.int64), customers, states)
     if device is None:
-        stats = run_stats_host(*arrays, math=1, max_events=max_events)
+        stats = run_stats_host(*arrays, math=1, max_events=max_events, kind=kind)
     else:
-        stats = run_stats_device(*arrays, device=device, max_events=max_events)
+        stats = run_stats_device(*arrays, device=device, max_events=max_events, kind=kind)
     m = metrics(stats)
     stop = np.asarray(stats.stop_reason.cpu() if hasattr(stats.stop_reason, "cpu") else stats.stop_reason)
     valid = (stop != ops.DES_STOP_ERROR) & (stop != ops.DES_STOP_BUDGET)
@@ -527,6 +594,87 @@ def replicate(spec, seeds, *, device=None, max_events=200000, states=None):
             std[name] = np.where(n[name] > 1, np.sqrt(dev2 / (n[name] - 1)), np.nan)
             sem[name] = std[name] / np.sqrt(n[name])
     return Replications(stats, m, mean, std, sem, n, valid)
+
+
+# ---- simulation beside theory: M/M/1/K -------------------------------------------------------------------------------
+SWEEP_NAMES = ("blocked_fraction", "utilisation", "avg_queue_length", "avg_queue_time", "queue_length_probabilities")
+Mm1kSweep = collections.namedtuple("Mm1kSweep", "lam mu queue_cap seeds stats values mean sem n theory z")
+Mm1kSweep.__doc__ = """``mm1k_sweep``'s result for C configurations x R seeds: lam, mu, queue_cap (C); the BatchStats of
+the C * R runs (configuration-major: run c * R + r); and per name of SWEEP_NAMES ``values`` (C, R) -- (C, R, K + 1), K =
+max(queue_cap), for ``queue_length_probabilities``, NaN beyond a configuration's own capacity --, their ``mean``,
+``sem`` (std with ddof 1 / sqrt(n)) and ``n`` over the runs that neither errored nor ran out of draws, the
+``queueing_theory.mm1k`` value ``theory`` and ``z`` = (mean - theory) / sem (0 where both differences are 0)."""
+
+
+def mm1k_spec(lam, mu, queue_cap, customers, seed=0):
+    """The 2-node net source -> server with exponential inter-arrival (mean 1 / lam) and service (mean 1 / mu) times
+    and ``queue_cap`` waiting places, as a ``DesSpec``."""
+    from .matrix_sim_process import DesSpec
+    adj = np.array([[1.0, 1.0], [0.0, 0.0]])
+    return DesSpec(adj, [["exponential", 1.0 / float(lam)], ["exponential", 1.0 / float(mu)]],
+                   [int(queue_cap), int(queue_cap)], np.array([int(seed)]), int(customers), 1.0, np.zeros(2), np.zeros(2))
+
+
+def mm1k_sweep(lams, mus, queue_caps, seeds, *, customers, device=None, max_events=None, math=1):
+    """Simulated M/M/1/K beside ``queueing_theory.mm1k``: configuration c = (lams[c], mus[c], queue_caps[c]), every
+    configuration with every seed, ALL of them one batch (one launch on a device; ``math`` is the host mirror's).
+    Replication r of every configuration starts from the global stream ``replication_states(seeds)[r]``.  Compared
+    (SWEEP_NAMES), each a property of the server node:
+      blocked_fraction            reneges / (served + reneges): the fraction of arrivals turned away  ~ p[K]
+                                  (``metrics``' renege_rate, reneges / served, is the reference's other quantity)
+      utilisation                 time_in_service / clock                                                ~ 1 - p[0]
+      avg_queue_length            queue_area / clock                                                     ~ LQ
+      avg_queue_time              time_in_queue / served                                                 ~ WQ
+      queue_length_probabilities  queue_time / clock                                                     ~ (p0 + p1, p2, ..)
+    -> Mm1kSweep.  max_events None: 4 * customers + 64, which no run reaches (an arrival and a departure per customer)."""
+    from . import ops, queueing_theory as qt
+    lams, mus = np.asarray(lams, dtype=np.float64).reshape(-1), np.asarray(mus, dtype=np.float64).reshape(-1)
+    caps = np.asarray(queue_caps, dtype=np.int64).reshape(-1)
+    seeds = [int(s) for s in np.asarray(seeds).reshape(-1)]
+    c, r = len(lams), len(seeds)
+    if c == 0 or r == 0 or len(mus) != c or len(caps) != c:
+        raise ValueError("mm1k_sweep: lams, mus and queue_caps must have one entry per configuration, and seeds be given")
+    if (caps < 1).any():
+        raise ValueError("mm1k_sweep: queue_cap >= 1 (the simulator's rings hold at least one customer)")
+    if max_events is None:
+        max_events = 4 * int(customers) + 64
+    specs = [mm1k_spec(lams[i], mus[i], caps[i], customers, s) for i in range(c) for s in seeds]
+    states = replication_states(seeds) * c
+    adj, kind, *rest = dist_arrays(specs)
+    if device is None:
+        stats = run_stats_host(adj, *rest, states, math=math, max_events=max_events, histogram=True, kind=kind)
+    else:
+        stats = run_stats_device(adj, *rest, states, device=device, max_events=max_events, histogram=True, kind=kind)
+    m = metrics(stats)
+    st = BatchStats(*(None if a is None else np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in stats))
+    k = int(caps.max())
+    with np.errstate(divide="ignore", invalid="ignore"):
+        blocked = st.reneges[:, 1] / (st.served[:, 1] + st.reneges[:, 1]).astype(np.float64)
+    prob = m["queue_length_probabilities"][:, 1, :].copy()
+    for i in range(c):
+        prob[i * r:(i + 1) * r, caps[i] + 1:] = np.nan           # lengths the configuration cannot have
+    values = {"blocked_fraction": blocked.reshape(c, r), "utilisation": m["server_utilizations"][:, 1].reshape(c, r),
+              "avg_queue_length": m["avg_queue_length"][:, 1].reshape(c, r),
+              "avg_queue_time": m["avg_queue_time"][:, 1].reshape(c, r), "queue_length_probabilities": prob.reshape(c, r, k + 1)}
+    valid = ((st.stop_reason != ops.DES_STOP_ERROR) & (st.stop_reason != ops.DES_STOP_BUDGET)).reshape(c, r)
+    theory = {n: np.full((c, k + 1) if n == "queue_length_probabilities" else (c,), np.nan) for n in SWEEP_NAMES}
+    for i in range(c):
+        t = qt.mm1k(lams[i], mus[i], caps[i])
+        theory["blocked_fraction"][i], theory["utilisation"][i] = t["blocking"], t["utilisation"]
+        theory["avg_queue_length"][i], theory["avg_queue_time"][i] = t["LQ"], t["WQ"]
+        theory["queue_length_probabilities"][i, :caps[i] + 1] = t["queue_length_probabilities"]
+    mean, sem, n, z = {}, {}, {}, {}
+    for name, v in values.items():
+        ok = valid if v.ndim == 2 else valid[:, :, None]
+        have = ok & ~np.isnan(v)
+        n[name] = have.sum(axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean[name] = np.where(n[name] > 0, np.where(have, v, 0.0).sum(axis=1) / n[name], np.nan)
+            dev2 = np.where(have, (v - np.expand_dims(mean[name], 1)) ** 2, 0.0).sum(axis=1)
+            sem[name] = np.where(n[name] > 1, np.sqrt(dev2 / (n[name] - 1)) / np.sqrt(n[name]), np.nan)
+            d = mean[name] - theory[name]
+            z[name] = np.where(d == 0, 0.0, d / sem[name])
+    return Mm1kSweep(lams, mus, caps, np.asarray(seeds, dtype=np.int64), stats, values, mean, sem, n, theory, z)
 
 
 def math_probe_host(x):

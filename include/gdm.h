@@ -509,6 +509,44 @@ int gdm_des_stats_batch(const double* adj, int B, int dim, const double* loc, co
                         int64_t* events, int64_t* n_records, int32_t* stop_reason, double* queue_time, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- the same statistics with a distribution KIND per node (csrc/des_stats.hip: des_stats_dist_kernel; des::AnyDist in
+ * csrc/des_sim.h) ------------------------------------------------------------------------------------------------------
+ * The argument lists of gdm_des_stats_batch[_host] with `kind` (B, dim) i32 after `scale`; same outputs, stop reasons,
+ * generator-state contract and workspace (gdm_des_stats_workspace_bytes).  A node draws its service / inter-arrival
+ * time from its own legacy stream as the reference's Server / Source do (SIMULATOR/simulation_v3.py:181-192, 263-274):
+ *   GDM_DES_DIST_NORMAL       ['normal', loc, scale]   rng.standard_normal() * scale + loc  (what the entries above do)
+ *   GDM_DES_DIST_EXPONENTIAL  ['exponential', scale]   (-log(1.0 - rng.random_sample())) * scale + 0.0; loc is not read
+ *   GDM_DES_DIST_UNIFORM      ['uniform', loc, scale]  rng.random_sample() * scale + loc
+ * -- scipy's rvs, operation for operation; scale == 0 returns loc (0.0 for the exponential) and draws nothing.  With
+ * every kind 0 the results are the bytes of gdm_des_stats_batch[_host].
+ * Refused per sample (GDM_DES_STOP_ERROR, zeros, generator state kept), besides what the entries above refuse: a
+ * server that can never draw a positive service time without consuming draws -- an exponential with scale 0, a
+ * uniform with scale 0 and loc <= 0 (the reference's `while service <= 0` never ends).  A uniform that draws but whose
+ * support is <= 0 ends on the draw budget (GDM_DES_STOP_BUDGET), like a normal far below zero.
+ * A kind outside 0..2: the host entry reads its array and refuses the call (GDM_EINVAL, nothing runs); the device
+ * entry cannot, there the sample stops with GDM_DES_STOP_ERROR like any refused spec.  Everything else is validated on
+ * the host before the launch.  gdm_des_stats_batch_dist_host: math 0 = libm, 1 = portable, the device's bits.        */
+#define GDM_DES_DIST_NORMAL 0
+#define GDM_DES_DIST_EXPONENTIAL 1
+#define GDM_DES_DIST_UNIFORM 2
+int gdm_des_stats_batch_dist_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                  const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
+                                  const int64_t* number_of_customers, int max_queue_cap, int math, int64_t max_events,
+                                  uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
+                                  int64_t* served, int64_t* reneges, int64_t* generated, int32_t* max_queue,
+                                  double* time_in_service, double* time_in_queue, double* queue_area,
+                                  double* arrival_time, double* clock, double* end_time, int64_t* total_customers,
+                                  int64_t* events, int64_t* n_records, int32_t* stop_reason, double* queue_time);
+int gdm_des_stats_batch_dist(const double* adj, int B, int dim, const double* loc, const double* scale,
+                             const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
+                             const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
+                             uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
+                             int64_t* served, int64_t* reneges, int64_t* generated, int32_t* max_queue,
+                             double* time_in_service, double* time_in_queue, double* queue_area, double* arrival_time,
+                             double* clock, double* end_time, int64_t* total_customers, int64_t* events,
+                             int64_t* n_records, int32_t* stop_reason, double* queue_time, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* ---- generic convolution lowering helpers (model 2 discriminator, model 1 generator) ----------------------------
  * im2col for Conv2d fwd / dW and col2im (gather form, deterministic) for Conv2d dX and ConvTranspose2d fwd.
  * Activations are channels-last (B,H,W,C) unless `src_planar` (NCHW fp32 input planes, e.g. the piano-roll).

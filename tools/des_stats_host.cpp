@@ -17,6 +17,10 @@
 //   double queue_time[dim * (stride + 1)], uint32 key[624]
 // A case that stops with DES_STOP_ERROR gives zeros and the generator state it came with, as the batch entries do.
 // tests/test_des_stats.py writes corpus cases in this form and compares with gdm_des_stats_batch_host(math = 1).
+//
+// With DES_HOST_WITH_KIND defined (tools/des_dist_host.cpp does, and includes this file) the simulator is
+// des::Sim<MathPortable, OutNone, NodeStats, AnyDist> and every case carries int32 kind[dim] between scale and qcap:
+// an exactly sized array, so a kind read past the case's nodes shows too.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -76,6 +80,10 @@ int main(int argc, char** argv) {
     get(in, adj.data(), d * d);
     get(in, loc.data(), d);
     get(in, scale.data(), d);
+#ifdef DES_HOST_WITH_KIND
+    std::vector<int32_t> kind(d);
+    get(in, kind.data(), d);
+#endif
     get(in, qcap.data(), d);
     get(in, global_key.data(), DES_MT_N);
     const std::vector<uint32_t> key0 = global_key;
@@ -94,7 +102,12 @@ int main(int argc, char** argv) {
     std::vector<double> tis(d), tiq(d), area(d), arrival(d), last_change(d), atime(d * (size_t)stride),
         queue_time(d * hs, 0.0);
 
+#ifdef DES_HOST_WITH_KIND
+    des::Sim<des::MathPortable, des::OutNone, des::NodeStats, des::AnyDist> s;
+    s.dist.kind = kind.data();
+#else
     des::Sim<des::MathPortable, des::OutNone, des::NodeStats> s;
+#endif
     s.dim = dim;
     s.loc = loc.data();
     s.scale = scale.data();
