@@ -15,6 +15,9 @@
 // and the FIFO rings (L2-resident: about 330 KB per sample at dim 61, capacity 254).
 // The prologue up to the chain, the LDS block and the workspace layout are des_wave.h's, shared with the log-free
 // statistics kernel of des_stats.hip.
+// Two kernels over one body (batch_sample): des_batch_kernel draws 'normal' only (des::NormalOnly, the bridges' nets);
+// des_batch_dist_kernel takes a kind per node (des::AnyDist: normal, exponential, uniform), its row staged into LDS
+// (512 B more), and leaves the generator state of a sample that errors as it came.
 // Bounds: every index the chain computes is checked in des_sim.h before it forms an address; every loop is bounded by
 // max_events, max_records or the draw budget.
 #include "gdm_common.h"
@@ -30,43 +33,102 @@ using des_wave::ws_layout;
 constexpr int kPackThreads = 256;
 typedef des::Sim<des::MathPortable, des::OutSoa> DevSim;
 
-__global__ __launch_bounds__(GDM_WAVE) void des_batch_kernel(
-    const double* __restrict__ adj, int dim, const double* __restrict__ loc, const double* __restrict__ scale,
-    const int32_t* __restrict__ queue_cap, const int64_t* __restrict__ seed,
-    const int64_t* __restrict__ number_of_customers, int max_queue_cap, int64_t max_events, int64_t max_records,
-    uint32_t* __restrict__ mt_key, int32_t* __restrict__ mt_pos, int32_t* __restrict__ mt_has_gauss,
-    double* __restrict__ mt_gauss, double* __restrict__ value, int64_t* __restrict__ event_id,
-    int32_t* __restrict__ node, int32_t* __restrict__ kind, int64_t* __restrict__ n_records,
-    int32_t* __restrict__ stop_reason, unsigned char* __restrict__ workspace) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];       // node generators when dim <= kLdsGenDim
-  __shared__ des_wave::Lds lds;
+typedef des::Sim<des::MathPortable, des::OutSoa, des::NoStats, des::AnyDist> DevDistSim;
 
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const des_wave::WsLayout w = ws_layout(dim, max_queue_cap, false);
-  unsigned char* ws = workspace + (size_t)b * w.per_sample;
+// the kinds of one sample (des_batch_dist_kernel only: des_wave::Lds is the layout of the kernels that have none)
+struct DistLds {
+  int32_t kind[kMaxDim];
+};
 
-  DevSim s;
+// the inputs and outputs both kernels share
+struct BatchArgs {
+  const double* adj;
+  int dim;
+  const double *loc, *scale;
+  const int32_t* queue_cap;
+  const int64_t *seed, *number_of_customers;
+  int max_queue_cap;
+  int64_t max_events, max_records;
+  uint32_t* mt_key;
+  int32_t *mt_pos, *mt_has_gauss;
+  double *mt_gauss, *value;
+  int64_t* event_id;
+  int32_t *node, *kind;
+  int64_t* n_records;
+  int32_t* stop_reason;
+  unsigned char* workspace;
+};
+
+// One sample, every lane of its wave.  s.dist is the caller's (what it points to is staged before the call: the
+// prologue's first barrier orders it before lane 0 reads it).  kErrorKeepsState: a sample whose chain ends in
+// DES_STOP_ERROR leaves the generator state as it came (the entries with kinds, as the statistics kernels); without
+// it the state is written back whenever the spec passed the prologue's checks (gdm_des_run_batch, as ever).
+template <bool kErrorKeepsState, class SimT>
+__device__ __forceinline__ void batch_sample(SimT& s, des_wave::Lds& lds, unsigned char* s_dyn, const BatchArgs& a) {
+  const int b = blockIdx.x, lane = threadIdx.x, dim = a.dim;
+  const int64_t max_records = a.max_records;
+  const des_wave::WsLayout w = ws_layout(dim, a.max_queue_cap, false);
+  unsigned char* ws = a.workspace + (size_t)b * w.per_sample;
+
   const int64_t rec0 = (int64_t)b * max_records;
-  s.out = des::OutSoa{value + rec0, event_id + rec0, node + rec0, kind + rec0};
+  s.out = des::OutSoa{a.value + rec0, a.event_id + rec0, a.node + rec0, a.kind + rec0};
   s.out_cap = max_records;
   s.max_records = max_records;
   // ---- all lanes: the shared prologue (des_wave.h)
-  const bool ok = des_wave::prologue(s, lds, s_dyn, ws, w, b, lane, adj, dim, loc, scale, queue_cap, seed, max_queue_cap,
-                                     max_events, mt_key, mt_pos, mt_has_gauss, mt_gauss);
+  const bool ok = des_wave::prologue(s, lds, s_dyn, ws, w, b, lane, a.adj, dim, a.loc, a.scale, a.queue_cap, a.seed,
+                                     a.max_queue_cap, a.max_events, a.mt_key, a.mt_pos, a.mt_has_gauss, a.mt_gauss);
   // ---- lane 0: the chain
   if (lane == 0) {
     int reason = DES_STOP_ERROR;
     int64_t n = 0;
     if (ok) {
-      reason = s.run(number_of_customers[b], max_events);
-      des_wave::store_generator_scalars(lds, dim, b, mt_pos, mt_has_gauss, mt_gauss);
+      reason = s.run(a.number_of_customers[b], a.max_events);
+      if (!kErrorKeepsState || reason != DES_STOP_ERROR)
+        des_wave::store_generator_scalars(lds, dim, b, a.mt_pos, a.mt_has_gauss, a.mt_gauss);
       n = reason == DES_STOP_ERROR ? 0 : (s.n_out < max_records ? s.n_out : max_records);
     }
-    n_records[b] = n;
-    stop_reason[b] = reason;
+    a.n_records[b] = n;
+    a.stop_reason[b] = reason;
+    if (kErrorKeepsState) lds.ok = reason != DES_STOP_ERROR;
   }
   __syncthreads();
-  if (ok) des_wave::store_generator_words(lds, b, lane, mt_key);
+  if (kErrorKeepsState ? lds.ok != 0 : ok) des_wave::store_generator_words(lds, b, lane, a.mt_key);
+}
+
+// the parameter list both kernels share (kernel parameters stay plain __restrict__ pointers) and the BatchArgs of them
+#define DES_BATCH_PARAMS                                                                                               \
+  const double *__restrict__ adj, int dim, const double *__restrict__ loc, const double *__restrict__ scale,           \
+      const int32_t *__restrict__ queue_cap, const int64_t *__restrict__ seed,                                         \
+      const int64_t *__restrict__ number_of_customers, int max_queue_cap, int64_t max_events, int64_t max_records,     \
+      uint32_t *__restrict__ mt_key, int32_t *__restrict__ mt_pos, int32_t *__restrict__ mt_has_gauss,                 \
+      double *__restrict__ mt_gauss, double *__restrict__ value, int64_t *__restrict__ event_id,                       \
+      int32_t *__restrict__ node, int32_t *__restrict__ kind, int64_t *__restrict__ n_records,                         \
+      int32_t *__restrict__ stop_reason, unsigned char *__restrict__ workspace
+#define DES_BATCH_ARGS                                                                                                 \
+  BatchArgs {                                                                                                          \
+    adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records, mt_key,        \
+        mt_pos, mt_has_gauss, mt_gauss, value, event_id, node, kind, n_records, stop_reason, workspace                 \
+  }
+
+__global__ __launch_bounds__(GDM_WAVE) void des_batch_kernel(DES_BATCH_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];       // node generators when dim <= kLdsGenDim
+  __shared__ des_wave::Lds lds;
+  DevSim s;
+  batch_sample<false>(s, lds, s_dyn, DES_BATCH_ARGS);
+}
+
+// The logging kernel with a distribution kind per node (des::AnyDist).  flatten, as des_stats_dist_kernel: three kinds
+// at three draw sites exceed the inliner's budget, and a chain function left out of line takes the Sim by address --
+// scratch per lane and a load for every member; inlined whole there is no scratch
+__global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_batch_dist_kernel(
+    DES_BATCH_PARAMS, const int32_t* __restrict__ dist_kind) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
+  __shared__ des_wave::Lds lds;
+  __shared__ DistLds dl;
+  for (int i = threadIdx.x; i < dim; i += GDM_WAVE) dl.kind[i] = dist_kind[(int64_t)blockIdx.x * dim + i];
+  DevDistSim s;
+  s.dist.kind = dl.kind;
+  batch_sample<true>(s, lds, s_dyn, DES_BATCH_ARGS);
 }
 
 // counts -> rec_ptr (exclusive scan, one workgroup), then the records of sample b move from b * max_records down to
@@ -142,6 +204,32 @@ extern "C" int64_t gdm_des_batch_workspace_bytes(int B, int dim, int max_queue_c
   return (int64_t)(ws_layout(dim, max_queue_cap, false).per_sample * (size_t)B);
 }
 
+// the checks both device entries make on the host; `who` names the entry in the message
+static int check_batch_args(const char* who, const BatchArgs& a, int B, const int32_t* dist_kind, bool with_kind,
+                            int64_t n_records_cap, const int64_t* rec_ptr, size_t workspace_bytes) {
+  GDM_REQUIRE(a.adj && a.loc && a.scale && a.queue_cap && a.seed && a.number_of_customers && a.mt_key && a.mt_pos &&
+                  a.mt_has_gauss && a.mt_gauss && a.value && a.event_id && a.node && a.kind && rec_ptr && a.n_records &&
+                  a.stop_reason && a.workspace && (dist_kind || !with_kind),
+              "%s: null pointer", who);
+  GDM_REQUIRE(B >= 1 && B <= (1 << 20) && a.dim >= 1 && a.dim <= kMaxDim && a.max_queue_cap >= 1 &&
+                  a.max_queue_cap <= GDM_DES_BATCH_MAX_QUEUE_CAP,
+              "%s: B >= 1, 1 <= dim <= %d, 1 <= max_queue_cap <= %d", who, kMaxDim, GDM_DES_BATCH_MAX_QUEUE_CAP);
+  GDM_REQUIRE(a.max_events >= 1 && a.max_events <= GDM_DES_BATCH_MAX_EVENTS, "%s: max_events must be in 1..%lld", who,
+              (long long)GDM_DES_BATCH_MAX_EVENTS);
+  GDM_REQUIRE(a.max_records >= 1 && a.max_records <= ((int64_t)1 << 31),
+              "%s: a record cap is required (max_records >= 1)", who);
+  GDM_REQUIRE(n_records_cap >= (int64_t)B * a.max_records,
+              "%s: the record arrays must hold B * max_records = %lld records", who,
+              (long long)((int64_t)B * a.max_records));
+  GDM_REQUIRE(((uintptr_t)dist_kind & 3) == 0, "%s: kind is not aligned to its element size", who);
+  const int64_t need = gdm_des_batch_workspace_bytes(B, a.dim, a.max_queue_cap);
+  if (need < 0 || workspace_bytes < (size_t)need || ((uintptr_t)a.workspace & 15)) {
+    gdm_set_error("%s: workspace too small or not 16-byte aligned (%lld bytes needed)", who, (long long)need);
+    return GDM_EWORKSPACE;
+  }
+  return GDM_OK;
+}
+
 extern "C" int gdm_des_run_batch(const double* adj, int B, int dim, const double* loc, const double* scale,
                                  const int32_t* queue_cap, const int64_t* seed, const int64_t* number_of_customers,
                                  int max_queue_cap, int64_t max_events, int64_t max_records, uint32_t* mt_key,
@@ -149,30 +237,39 @@ extern "C" int gdm_des_run_batch(const double* adj, int B, int dim, const double
                                  int64_t* event_id, int32_t* node, int32_t* kind, int64_t n_records_cap,
                                  int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-  GDM_REQUIRE(adj && loc && scale && queue_cap && seed && number_of_customers && mt_key && mt_pos && has_gauss &&
-                  cached_gauss && value && event_id && node && kind && rec_ptr && n_records && stop_reason && workspace,
-              "gdm_des_run_batch: null pointer");
-  GDM_REQUIRE(B >= 1 && B <= (1 << 20) && dim >= 1 && dim <= kMaxDim && max_queue_cap >= 1 &&
-                  max_queue_cap <= GDM_DES_BATCH_MAX_QUEUE_CAP,
-              "gdm_des_run_batch: B >= 1, 1 <= dim <= %d, 1 <= max_queue_cap <= %d", kMaxDim, GDM_DES_BATCH_MAX_QUEUE_CAP);
-  GDM_REQUIRE(max_events >= 1 && max_events <= GDM_DES_BATCH_MAX_EVENTS,
-              "gdm_des_run_batch: max_events must be in 1..%lld", (long long)GDM_DES_BATCH_MAX_EVENTS);
-  GDM_REQUIRE(max_records >= 1 && max_records <= ((int64_t)1 << 31),
-              "gdm_des_run_batch: a record cap is required (max_records >= 1)");
-  GDM_REQUIRE(n_records_cap >= (int64_t)B * max_records,
-              "gdm_des_run_batch: the record arrays must hold B * max_records = %lld records",
-              (long long)((int64_t)B * max_records));
-  const int64_t need = gdm_des_batch_workspace_bytes(B, dim, max_queue_cap);
-  if (need < 0 || workspace_bytes < (size_t)need || ((uintptr_t)workspace & 15)) {
-    gdm_set_error("gdm_des_run_batch: workspace too small or not 16-byte aligned (%lld bytes needed)", (long long)need);
-    return GDM_EWORKSPACE;
-  }
+  const BatchArgs a{adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records,
+                    mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
+                    (unsigned char*)workspace};
+  const int rc = check_batch_args("gdm_des_run_batch", a, B, nullptr, false, n_records_cap, rec_ptr, workspace_bytes);
+  if (rc != GDM_OK) return rc;
   const size_t lds_dyn = des_wave::lds_dyn_bytes(dim);
   hipLaunchKernelGGL(des_batch_kernel, dim3(B), dim3(GDM_WAVE), lds_dyn, (hipStream_t)stream, adj, dim, loc, scale,
                      queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records, mt_key, mt_pos,
                      has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
                      (unsigned char*)workspace);
   GDM_LAUNCH_OK("gdm_des_run_batch");
+  return gdm_des_pack(B, max_records, n_records, rec_ptr, value, event_id, node, kind, stream);
+}
+
+extern "C" int gdm_des_run_batch_dist(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                      const int32_t* dist_kind, const int32_t* queue_cap, const int64_t* seed,
+                                      const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
+                                      int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                                      double* cached_gauss, double* value, int64_t* event_id, int32_t* node,
+                                      int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records,
+                                      int32_t* stop_reason, void* workspace, size_t workspace_bytes, void* stream) {
+  const BatchArgs a{adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records,
+                    mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
+                    (unsigned char*)workspace};
+  const int rc =
+      check_batch_args("gdm_des_run_batch_dist", a, B, dist_kind, true, n_records_cap, rec_ptr, workspace_bytes);
+  if (rc != GDM_OK) return rc;
+  const size_t lds_dyn = des_wave::lds_dyn_bytes(dim);
+  hipLaunchKernelGGL(des_batch_dist_kernel, dim3(B), dim3(GDM_WAVE), lds_dyn, (hipStream_t)stream, adj, dim, loc, scale,
+                     queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records, mt_key, mt_pos,
+                     has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
+                     (unsigned char*)workspace, dist_kind);
+  GDM_LAUNCH_OK("gdm_des_run_batch_dist");
   return gdm_des_pack(B, max_records, n_records, rec_ptr, value, event_id, node, kind, stream);
 }
 

@@ -5,7 +5,8 @@
 // 106-110): 'normal' service / inter-arrival distributions, logging_mode 'Music', probability routing.
 //
 // The event logic itself lives in des_sim.h (shared with the device kernel of des_batch.hip); this file holds its HOST
-// instantiations: gdm_des_run (libm math, numpy's bits) and gdm_des_run_batch_host (the batch mirror).
+// instantiations: gdm_des_run (libm math, numpy's bits), gdm_des_run_batch_host (the batch mirror) and
+// gdm_des_run_batch_dist_host (the batch mirror with a distribution kind per node, des::AnyDist).
 //
 // HOST code ("a deterministic, event-count-capped C++ DES core"): the simulation is one
 // dependent event chain per sample (des_batch.hip runs a batch of them, one wave each).  What makes it a drop-in is that it reproduces the reference's
@@ -90,18 +91,28 @@ struct HostSim {
   }
 };
 
-template <class Math>
-int run_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale, const int32_t* queue_cap,
-                   const int64_t* seed, const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
-                   int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
-                   double* value, int64_t* event_id, int32_t* node, int32_t* kind, int64_t n_records_cap,
-                   int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason) {
-  HostSim<Math, des::OutSoa> h(dim, max_queue_cap);
+// the kinds of sample b, where the policy has any
+inline void bind_kind(des::NormalOnly&, const int32_t*, size_t) {}
+inline void bind_kind(des::AnyDist& d, const int32_t* kind, size_t row) { d.kind = kind + row; }
+
+// Dist = des::NormalOnly for gdm_des_run_batch_host (dist_kind is not read), des::AnyDist for
+// gdm_des_run_batch_dist_host; `who` names the entry in the message.  kErrorKeepsState: a sample whose chain ends in
+// DES_STOP_ERROR leaves the generator state as it came (the entry with kinds, as the statistics entries); without it
+// the state is written back whenever the spec passed spec_ok (gdm_des_run_batch_host, as ever).
+template <class Math, class Dist, bool kErrorKeepsState>
+int run_batch_host(const char* who, const double* adj, int B, int dim, const double* loc, const double* scale,
+                   const int32_t* dist_kind, const int32_t* queue_cap, const int64_t* seed,
+                   const int64_t* number_of_customers, int max_queue_cap, int64_t max_events, int64_t max_records,
+                   uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss, double* value,
+                   int64_t* event_id, int32_t* node, int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr,
+                   int64_t* n_records, int32_t* stop_reason) {
+  HostSim<Math, des::OutSoa, des::NoStats, Dist> h(dim, max_queue_cap);
   int64_t at = 0;                                       // records written so far (needed, when the arrays overflow)
   bool overflow = false;
   rec_ptr[0] = 0;
   for (int b = 0; b < B; ++b) {
-    des::Sim<Math, des::OutSoa>& s = h.s;
+    des::Sim<Math, des::OutSoa, des::NoStats, Dist>& s = h.s;
+    bind_kind(s.dist, dist_kind, (size_t)b * dim);
     const int64_t room = n_records_cap > at ? n_records_cap - at : 0;
     const int64_t off = room > 0 ? at : 0;
     s.out = des::OutSoa{value + off, event_id + off, node + off, kind + off};
@@ -117,10 +128,12 @@ int run_batch_host(const double* adj, int B, int dim, const double* loc, const d
       h.prepare(adj + (size_t)b * dim * dim, s.loc, s.scale, s.qcap, (uint32_t)seed[b], mt_key + (size_t)b * DES_MT_N,
                 mt_pos[b], has_gauss[b], cached_gauss[b]);
       reason = s.run(number_of_customers[b], max_events);
-      std::memcpy(mt_key + (size_t)b * DES_MT_N, s.global_key, DES_MT_N * sizeof(uint32_t));
-      mt_pos[b] = s.pos[dim];
-      has_gauss[b] = s.has_gauss[dim];
-      cached_gauss[b] = s.gauss[dim];
+      if (!kErrorKeepsState || reason != DES_STOP_ERROR) {
+        std::memcpy(mt_key + (size_t)b * DES_MT_N, s.global_key, DES_MT_N * sizeof(uint32_t));
+        mt_pos[b] = s.pos[dim];
+        has_gauss[b] = s.has_gauss[dim];
+        cached_gauss[b] = s.gauss[dim];
+      }
       n = reason == DES_STOP_ERROR ? 0 : s.n_out;     // a sample that errors has an empty log
       overflow |= n > room;
     }
@@ -130,7 +143,7 @@ int run_batch_host(const double* adj, int B, int dim, const double* loc, const d
     stop_reason[b] = reason;
   }
   if (overflow) {
-    gdm_set_error("gdm_des_run_batch_host: record arrays too small (%lld records needed)", (long long)at);
+    gdm_set_error("%s: record arrays too small (%lld records needed)", who, (long long)at);
     return GDM_EWORKSPACE;
   }
   return GDM_OK;
@@ -147,10 +160,6 @@ struct StatsOut {
   int32_t* stop_reason;
   double* queue_time;
 };
-
-// the kinds of sample b, where the policy has any
-inline void bind_kind(des::NormalOnly&, const int32_t*, size_t) {}
-inline void bind_kind(des::AnyDist& d, const int32_t* kind, size_t row) { d.kind = kind + row; }
 
 template <class Math, class Dist>
 void stats_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale, const int32_t* kind,
@@ -278,33 +287,67 @@ extern "C" int gdm_des_run(const double* adj, int dim, const double* loc, const 
   return GDM_OK;
 }
 
+// the argument checks of both host logging entries and the dispatch on math; `who` names the entry in the message
+template <class Dist, bool kErrorKeepsState>
+int run_batch_host_entry(const char* who, const double* adj, int B, int dim, const double* loc, const double* scale,
+                         const int32_t* dist_kind, const int32_t* queue_cap, const int64_t* seed,
+                         const int64_t* number_of_customers, int max_queue_cap, int math, int64_t max_events,
+                         int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                         double* cached_gauss, double* value, int64_t* event_id, int32_t* node, int32_t* kind,
+                         int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason) {
+  GDM_REQUIRE(adj && loc && scale && queue_cap && seed && number_of_customers && mt_key && mt_pos && has_gauss &&
+                  cached_gauss && rec_ptr && n_records && stop_reason,
+              "%s: null pointer", who);
+  // the host tables are heap vectors sized by dim (HostSim): only the kernel is bound to GDM_DES_BATCH_MAX_DIM
+  GDM_REQUIRE(B >= 1 && dim >= 1 && dim <= GDM_DES_BATCH_HOST_MAX_DIM && max_queue_cap >= 1 &&
+                  max_queue_cap <= GDM_DES_BATCH_MAX_QUEUE_CAP,
+              "%s: B >= 1, 1 <= dim <= %d, 1 <= max_queue_cap <= %d", who, GDM_DES_BATCH_HOST_MAX_DIM,
+              GDM_DES_BATCH_MAX_QUEUE_CAP);
+  GDM_REQUIRE(max_events >= 1 && max_events <= GDM_DES_BATCH_MAX_EVENTS && max_records >= 0,
+              "%s: max_events must be in 1..%lld and max_records >= 0", who, (long long)GDM_DES_BATCH_MAX_EVENTS);
+  GDM_REQUIRE(n_records_cap >= 0 && (n_records_cap == 0 || (value && event_id && node && kind)),
+              "%s: record arrays missing", who);
+  GDM_REQUIRE(math == 0 || math == 1, "%s: math must be 0 (libm) or 1 (portable)", who);
+  if (math == 0)
+    return run_batch_host<MathLibm, Dist, kErrorKeepsState>(who, adj, B, dim, loc, scale, dist_kind, queue_cap, seed, number_of_customers,
+                                          max_queue_cap, max_events, max_records, mt_key, mt_pos, has_gauss,
+                                          cached_gauss, value, event_id, node, kind, n_records_cap, rec_ptr, n_records,
+                                          stop_reason);
+  return run_batch_host<des::MathPortable, Dist, kErrorKeepsState>(who, adj, B, dim, loc, scale, dist_kind, queue_cap, seed,
+                                                 number_of_customers, max_queue_cap, max_events, max_records, mt_key,
+                                                 mt_pos, has_gauss, cached_gauss, value, event_id, node, kind,
+                                                 n_records_cap, rec_ptr, n_records, stop_reason);
+}
+
 extern "C" int gdm_des_run_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale,
                                       const int32_t* queue_cap, const int64_t* seed, const int64_t* number_of_customers,
                                       int max_queue_cap, int math, int64_t max_events, int64_t max_records,
                                       uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
                                       double* value, int64_t* event_id, int32_t* node, int32_t* kind,
                                       int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason) {
-  GDM_REQUIRE(adj && loc && scale && queue_cap && seed && number_of_customers && mt_key && mt_pos && has_gauss &&
-                  cached_gauss && rec_ptr && n_records && stop_reason,
-              "gdm_des_run_batch_host: null pointer");
-  // the host tables are heap vectors sized by dim (HostSim): only the kernel is bound to GDM_DES_BATCH_MAX_DIM
-  GDM_REQUIRE(B >= 1 && dim >= 1 && dim <= GDM_DES_BATCH_HOST_MAX_DIM && max_queue_cap >= 1 &&
-                  max_queue_cap <= GDM_DES_BATCH_MAX_QUEUE_CAP,
-              "gdm_des_run_batch_host: B >= 1, 1 <= dim <= %d, 1 <= max_queue_cap <= %d", GDM_DES_BATCH_HOST_MAX_DIM,
-              GDM_DES_BATCH_MAX_QUEUE_CAP);
-  GDM_REQUIRE(max_events >= 1 && max_events <= GDM_DES_BATCH_MAX_EVENTS && max_records >= 0,
-              "gdm_des_run_batch_host: max_events must be in 1..%lld and max_records >= 0",
-              (long long)GDM_DES_BATCH_MAX_EVENTS);
-  GDM_REQUIRE(n_records_cap >= 0 && (n_records_cap == 0 || (value && event_id && node && kind)),
-              "gdm_des_run_batch_host: record arrays missing");
-  GDM_REQUIRE(math == 0 || math == 1, "gdm_des_run_batch_host: math must be 0 (libm) or 1 (portable)");
-  if (math == 0)
-    return run_batch_host<MathLibm>(adj, B, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap,
-                                    max_events, max_records, mt_key, mt_pos, has_gauss, cached_gauss, value, event_id,
-                                    node, kind, n_records_cap, rec_ptr, n_records, stop_reason);
-  return run_batch_host<des::MathPortable>(adj, B, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap,
-                                           max_events, max_records, mt_key, mt_pos, has_gauss, cached_gauss, value,
-                                           event_id, node, kind, n_records_cap, rec_ptr, n_records, stop_reason);
+  return run_batch_host_entry<des::NormalOnly, false>("gdm_des_run_batch_host", adj, B, dim, loc, scale, nullptr, queue_cap,
+                                               seed, number_of_customers, max_queue_cap, math, max_events, max_records,
+                                               mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node, kind,
+                                               n_records_cap, rec_ptr, n_records, stop_reason);
+}
+
+extern "C" int gdm_des_run_batch_dist_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                           const int32_t* dist_kind, const int32_t* queue_cap, const int64_t* seed,
+                                           const int64_t* number_of_customers, int max_queue_cap, int math,
+                                           int64_t max_events, int64_t max_records, uint32_t* mt_key, int32_t* mt_pos,
+                                           int32_t* has_gauss, double* cached_gauss, double* value, int64_t* event_id,
+                                           int32_t* node, int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr,
+                                           int64_t* n_records, int32_t* stop_reason) {
+  GDM_REQUIRE(dist_kind, "gdm_des_run_batch_dist_host: null pointer");
+  GDM_REQUIRE(B >= 1 && dim >= 1, "gdm_des_run_batch_dist_host: B >= 1, dim >= 1");
+  for (int64_t i = 0; i < (int64_t)B * dim; ++i)
+    GDM_REQUIRE(dist_kind[i] >= GDM_DES_DIST_NORMAL && dist_kind[i] <= GDM_DES_DIST_UNIFORM,
+                "gdm_des_run_batch_dist_host: kind %d at sample %lld, node %lld is none of GDM_DES_DIST_*",
+                dist_kind[i], (long long)(i / dim), (long long)(i % dim));
+  return run_batch_host_entry<des::AnyDist, true>("gdm_des_run_batch_dist_host", adj, B, dim, loc, scale, dist_kind,
+                                            queue_cap, seed, number_of_customers, max_queue_cap, math, max_events,
+                                            max_records, mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node,
+                                            kind, n_records_cap, rec_ptr, n_records, stop_reason);
 }
 
 extern "C" int gdm_des_math_probe_host(const double* x, int64_t n, double* log_out, double* factor_out) {

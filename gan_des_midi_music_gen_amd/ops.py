@@ -1064,6 +1064,43 @@ def des_batch_workspace_bytes(b, dim, max_queue_cap):
     return n
 
 
+def _des_run_batch(who, kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, max_queue_cap,
+                   max_events, max_records, workspace_tensor):
+    """``des_run_batch`` (kind None: gdm_des_run_batch) and ``des_run_batch_dist`` (gdm_des_run_batch_dist)."""
+    _need_gpu(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss,
+              *(() if kind is None else (kind,)))
+    if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
+        raise GdmError(f"{who}: adj must be (B, dim, dim)")
+    b, dim = adj.shape[0], adj.shape[1]
+    for t, shape, dt in ((adj, (b, dim, dim), torch.float64), (loc, (b, dim), torch.float64),
+                         (scale, (b, dim), torch.float64), (queue_cap, (b, dim), torch.int32), (seed, (b,), torch.int64),
+                         (customers, (b,), torch.int64), (mt_key, (b, 624), torch.int32), (mt_pos, (b,), torch.int32),
+                         (has_gauss, (b,), torch.int32), (gauss, (b,), torch.float64)) + \
+                        (() if kind is None else ((kind, (b, dim), torch.int32),)):
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise GdmError(f"{who}: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
+                           f"{tuple(t.shape)}")
+    max_records = int(max_records)
+    if max_records < 1:
+        raise GdmError(f"{who}: the device simulator needs a record cap (max_records >= 1)")
+    dev = adj.device
+    n = b * max_records
+    value = torch.empty(n, dtype=torch.float64, device=dev)
+    event_id = torch.empty(n, dtype=torch.int64, device=dev)
+    node = torch.empty(n, dtype=torch.int32, device=dev)
+    rkind = torch.empty(n, dtype=torch.int32, device=dev)
+    rec_ptr = torch.empty(b + 1, dtype=torch.int64, device=dev)
+    n_records = torch.empty(b, dtype=torch.int64, device=dev)
+    stop = torch.empty(b, dtype=torch.int32, device=dev)
+    need = des_batch_workspace_bytes(b, dim, max_queue_cap)
+    ws = workspace(need, dev) if workspace_tensor is None else workspace_tensor
+    _call("gdm_des_run_batch" if kind is None else "gdm_des_run_batch_dist", _p(adj), b, dim, _p(loc), _p(scale),
+          *(() if kind is None else (_p(kind),)), _p(queue_cap), _p(seed), _p(customers),
+          int(max_queue_cap), int(max_events), max_records, _p(mt_key), _p(mt_pos), _p(has_gauss), _p(gauss), _p(value),
+          _p(event_id), _p(node), _p(rkind), n, _p(rec_ptr), _p(n_records), _p(stop), _p(ws), ws.numel(), _stream())
+    return value, event_id, node, rkind, rec_ptr, n_records, stop
+
+
 def des_run_batch(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *, max_queue_cap,
                   max_events=200000, max_records=5001, workspace_tensor=None):
     """B simulations in one launch (+ the pack step).  Device tensors: adj (B,dim,dim) f64 (``des_routing``'s output),
@@ -1071,35 +1108,17 @@ def des_run_batch(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, h
     (uint32 bit patterns), mt_pos, has_gauss (B) i32, gauss (B) f64 are UPDATED IN PLACE.  Returns (value, event_id,
     node, kind, rec_ptr, n_records, stop_reason): the CSR record arrays hold B * max_records entries, of which
     rec_ptr[B] are records; nothing is read back."""
-    _need_gpu(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss)
-    if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
-        raise GdmError("des_run_batch: adj must be (B, dim, dim)")
-    b, dim = adj.shape[0], adj.shape[1]
-    for t, shape, dt in ((adj, (b, dim, dim), torch.float64), (loc, (b, dim), torch.float64),
-                         (scale, (b, dim), torch.float64), (queue_cap, (b, dim), torch.int32), (seed, (b,), torch.int64),
-                         (customers, (b,), torch.int64), (mt_key, (b, 624), torch.int32), (mt_pos, (b,), torch.int32),
-                         (has_gauss, (b,), torch.int32), (gauss, (b,), torch.float64)):
-        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
-            raise GdmError(f"des_run_batch: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
-                           f"{tuple(t.shape)}")
-    max_records = int(max_records)
-    if max_records < 1:
-        raise GdmError("des_run_batch: the device simulator needs a record cap (max_records >= 1)")
-    dev = adj.device
-    n = b * max_records
-    value = torch.empty(n, dtype=torch.float64, device=dev)
-    event_id = torch.empty(n, dtype=torch.int64, device=dev)
-    node = torch.empty(n, dtype=torch.int32, device=dev)
-    kind = torch.empty(n, dtype=torch.int32, device=dev)
-    rec_ptr = torch.empty(b + 1, dtype=torch.int64, device=dev)
-    n_records = torch.empty(b, dtype=torch.int64, device=dev)
-    stop = torch.empty(b, dtype=torch.int32, device=dev)
-    need = des_batch_workspace_bytes(b, dim, max_queue_cap)
-    ws = workspace(need, dev) if workspace_tensor is None else workspace_tensor
-    _call("gdm_des_run_batch", _p(adj), b, dim, _p(loc), _p(scale), _p(queue_cap), _p(seed), _p(customers),
-          int(max_queue_cap), int(max_events), max_records, _p(mt_key), _p(mt_pos), _p(has_gauss), _p(gauss), _p(value),
-          _p(event_id), _p(node), _p(kind), n, _p(rec_ptr), _p(n_records), _p(stop), _p(ws), ws.numel(), _stream())
-    return value, event_id, node, kind, rec_ptr, n_records, stop
+    return _des_run_batch("des_run_batch", None, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss,
+                          gauss, max_queue_cap, max_events, max_records, workspace_tensor)
+
+
+def des_run_batch_dist(adj, loc, scale, kind, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *,
+                       max_queue_cap, max_events=200000, max_records=5001, workspace_tensor=None):
+    """``des_run_batch`` with a distribution kind per node (``kind`` (B,dim) int32 of DES_DIST_*; ``loc`` is not read
+    where a node is exponential): ``gdm_des_run_batch_dist``, one launch + the pack step.  A kind outside 0..2 ends
+    that sample with DES_STOP_ERROR; a sample that ends so keeps its generator state."""
+    return _des_run_batch("des_run_batch_dist", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
+                          has_gauss, gauss, max_queue_cap, max_events, max_records, workspace_tensor)
 
 
 # ---- the same simulator without a log: per-node queueing statistics (csrc/des_stats.hip) ------------------------------------
@@ -1179,6 +1198,42 @@ def des_pack(n_records, rec_ptr, value, event_id, node, kind, max_records):
         raise GdmError("des_pack: rec_ptr must hold B + 1 offsets and the record arrays B * max_records entries")
     _call("gdm_des_pack", b, int(max_records), _p(n_records), _p(rec_ptr), _p(value), _p(event_id), _p(node), _p(kind),
           _stream())
+
+
+DES_TRACKS_ENODE, DES_TRACKS_EPTR = 1, 2       # GDM_DES_TRACKS_*
+DES_TRACKS_MAX_DIM = 4096                       # GDM_DES_TRACKS_MAX_DIM
+
+
+def des_log_tracks(node, kind, rec_ptr, col_of_node, n_cols, *, max_lines=5000):
+    """Device logs -> queue tracks (csrc/des_tracks.hip): node, kind (n) i32 and rec_ptr (B+1) i64 as ``des_run_batch``
+    returns them, col_of_node (B,dim) i32 (the column of a node, -1 = not tracked), ``n_cols`` columns.  Runs
+    ``gdm_des_log_tracks_count``, reads back row_ptr[B] (8 bytes, the only synchronisation), allocates, then
+    ``gdm_des_log_tracks``.  Returns (tracks (row_ptr[B], n_cols) i32, row_ptr (B+1) i64, n_rows (B) i64, status (B)
+    i32 of DES_TRACKS_*; a sample with a status has zero rows)."""
+    _need_gpu(node, kind, rec_ptr, col_of_node)
+    if col_of_node.dim() != 2:
+        raise GdmError("des_log_tracks: col_of_node must be (B, dim)")
+    b, dim = col_of_node.shape
+    n = node.numel()
+    for t, shape, dt in ((node, (n,), torch.int32), (kind, (n,), torch.int32), (rec_ptr, (b + 1,), torch.int64),
+                         (col_of_node, (b, dim), torch.int32)):
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise GdmError(f"des_log_tracks: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
+                           f"{tuple(t.shape)}")
+    n_cols = int(n_cols)
+    if not 1 <= n_cols <= dim or dim > DES_TRACKS_MAX_DIM:
+        raise GdmError(f"des_log_tracks: 1 <= n_cols <= dim <= {DES_TRACKS_MAX_DIM} (n_cols={n_cols}, dim={dim})")
+    dev = node.device
+    n_rows = torch.empty(b, dtype=torch.int64, device=dev)
+    row_ptr = torch.empty(b + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    _call("gdm_des_log_tracks_count", _p(node), _p(kind), _p(rec_ptr), n, b, dim, _p(col_of_node), int(max_lines),
+          _p(n_rows), _p(row_ptr), _p(status), _stream())
+    total = int(row_ptr[b].item())
+    tracks = torch.empty((total, n_cols), dtype=torch.int32, device=dev)
+    _call("gdm_des_log_tracks", _p(node), _p(kind), _p(rec_ptr), n, b, dim, _p(col_of_node), n_cols, int(max_lines),
+          _p(row_ptr), total, _p(tracks), _stream())
+    return tracks, row_ptr, n_rows, status
 
 
 def des_math_probe(x):

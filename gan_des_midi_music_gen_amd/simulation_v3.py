@@ -18,7 +18,7 @@ Differences, on purpose:
     accepted and ignored);
   * only what the bridges construct is supported: 'normal' distributions, ``logging_mode='Music'``, probability routing
     (no 'queue' / 'branch' nodes, no animation, no metric history) -- anything else raises NotImplementedError (the
-    log-free statistics run below also takes 'exponential' and 'uniform' nodes);
+    log-free statistics run and ``run_batch_dist`` below also take 'exponential' and 'uniform' nodes);
   * the log records are also kept as arrays (``sim.music_log``), so a caller need not go through the log file;
   * where the reference's run ends in an exception, ``Sim.run`` raises ValueError with the core's message, and a sample
     of ``run_batch`` / ``run_batch_host`` ends with stop reason 3 ("error") and an empty log, its neighbours untouched
@@ -42,7 +42,8 @@ Differences, on purpose:
     1e-16 relative; tests/test_des_stats.py).  ``clock`` is the reference's ``Clock`` and ``end_time`` its
     ``previous_time``: the event that triggers the ``number_of_customers`` stop is counted in the time integration
     but ``Clock`` is not advanced to it.  A sample that ends in an error returns zeros and keeps its generator state.
-  * the statistics run -- not ``Sim``, ``run_batch`` or the bridges -- takes nodes of DIST_KINDS: ``['normal', loc, s]``,
+  * the statistics run and ``run_batch_dist`` -- not ``Sim``, ``run_batch``, ``spec_arrays`` or the bridges -- take
+    nodes of DIST_KINDS: ``['normal', loc, s]``,
     ``['exponential', s]`` and ``['uniform', loc, s]`` as the reference's ``Server`` / ``Source`` construct them
     (181-192, 263-274).  The last two are ONE uniform double on the node's stream, in scipy's order of operations:
     ``(-log(1.0 - u)) * s + 0.0`` and ``u * s + loc``; ``s == 0`` returns loc (0.0) without a draw.  ``dist_arrays``
@@ -52,6 +53,12 @@ Differences, on purpose:
     uniform with scale 0 and loc <= 0 -- the sample stops with reason 3; a uniform whose support is <= 0 ends on the
     draw budget.  ``mm1k_sweep`` puts the simulated M/M/1/K beside ``queueing_theory.mm1k`` (tests/golden/des_dist.npz
     records the reference's own runs of the same nets; ``tools/des_validate.py`` prints the table).
+  * the LOG of such nets comes from ``run_batch_dist`` (specs) or ``run_batch_host`` / ``run_batch_device`` with
+    ``kind=`` (``gdm_des_run_batch_dist[_host]``; csrc/des_batch.hip: des_batch_dist_kernel): the same draws, refusals
+    and stop reasons as the statistics run, the records of ``run_batch``.  With ``math=0`` the log is the reference's,
+    record for record and bit for bit (tests/golden/des_log_dist.npz).  Unlike ``run_batch`` a sample that stops with
+    reason 3 keeps the generator state it came with, as in the statistics run.  ``write_music_log`` writes any such
+    log as the reference's ``logs/simulation.log``; ``simlog_to_vid`` turns it into queue tracks and an animation.
 
 ``run_batch`` / ``run_batch_host`` simulate B specs of one size at once, every sample FROM ITS OWN snapshot of numpy's
 global stream (``gdm_des_run_batch`` on a HIP device: one wave per sample, csrc/des_batch.hip; ``gdm_des_run_batch_host``
@@ -149,10 +156,16 @@ class Sim:
             self.stop_reason = STOP_REASONS[reason]
         self.music_log = np.concatenate(logs) if logs else np.zeros(0, dtype=EVENT_DTYPE)
         if self.log_file is not None:
-            with open(self.log_file, "w") as f:
-                for v, eid, node, kind in self.music_log:
-                    f.write(f"INFO:root:{float(v)!r} - {int(eid)} - {int(node)} - {KIND_NAMES[kind]}\n")
+            write_music_log(self.music_log, self.log_file)
         return self.music_log
+
+
+def write_music_log(records, path):
+    """EVENT_DTYPE records (``Sim.music_log``, ``sample_log`` of a BatchLog) -> the 'Music' log file the reference's
+    ``logging.info`` writes (``logs/simulation.log``): ``INFO:root:<repr of the value> - <id> - <node> - <kind>``."""
+    with open(path, "w") as f:
+        for v, eid, node, kind in records:
+            f.write(f"INFO:root:{float(v)!r} - {int(eid)} - {int(node)} - {KIND_NAMES[kind]}\n")
 
 
 def run_spec(spec, max_events=200000, generate_log=False, log_path="logs/"):
@@ -207,10 +220,11 @@ def sample_log(log, b):
 
 
 def run_batch_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, math=1, max_events=200000,
-                   max_records=5001, max_queue_cap=None):
+                   max_records=5001, max_queue_cap=None, kind=None):
     """``gdm_des_run_batch_host`` on numpy arrays: adj (B,dim,dim), loc, scale, queue_cap (B,dim), seed, customers (B).
     math 0 = libm (the reference's bits), 1 = portable (the device's bits).  max_records 0 = no cap.  -> BatchLog of
-    numpy arrays; the record arrays are cut to rec_ptr[B]."""
+    numpy arrays; the record arrays are cut to rec_ptr[B].  ``kind`` (B,dim), the index into DIST_KINDS per node:
+    ``gdm_des_run_batch_dist_host``; None: every node is normal."""
     lib = _lib.load()
     adj = np.ascontiguousarray(adj, dtype=np.float64)
     b, dim = adj.shape[0], adj.shape[1]
@@ -224,25 +238,29 @@ def run_batch_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, 
     max_events, max_records = int(max_events), int(max_records)
     if max_queue_cap is None:
         max_queue_cap = max(1, int(queue_cap.max()))
+    if kind is None:
+        name, kinds = "gdm_des_run_batch_host", ()
+    else:
+        kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(b, dim)
+        name, kinds = "gdm_des_run_batch_dist_host", (kind.ctypes.data,)
+    entry = getattr(lib, name)
     per = 4 * max_events + 4 * dim + 64                    # at most four records per processed event
     cap = b * (min(per, max_records) if max_records > 0 else per)
     while True:
         value, eid = np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.int64)
-        node, kind = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+        node, rkind = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
         rec_ptr, n_rec, stop = np.zeros(b + 1, dtype=np.int64), np.zeros(b, dtype=np.int64), np.zeros(b, dtype=np.int32)
         k, p, h, g = key.copy(), pos.copy(), has.copy(), gauss.copy()
-        rc = lib.gdm_des_run_batch_host(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data,
-                                        queue_cap.ctypes.data, seed.ctypes.data, customers.ctypes.data,
-                                        int(max_queue_cap), int(math), max_events, max_records, k.ctypes.data,
-                                        p.ctypes.data, h.ctypes.data, g.ctypes.data, value.ctypes.data, eid.ctypes.data,
-                                        node.ctypes.data, kind.ctypes.data, cap, rec_ptr.ctypes.data, n_rec.ctypes.data,
-                                        stop.ctypes.data)
+        rc = entry(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data, *kinds, queue_cap.ctypes.data,
+                   seed.ctypes.data, customers.ctypes.data, int(max_queue_cap), int(math), max_events, max_records,
+                   k.ctypes.data, p.ctypes.data, h.ctypes.data, g.ctypes.data, value.ctypes.data, eid.ctypes.data,
+                   node.ctypes.data, rkind.ctypes.data, cap, rec_ptr.ctypes.data, n_rec.ctypes.data, stop.ctypes.data)
         if rc == -3 and int(rec_ptr[-1]) > cap:            # GDM_EWORKSPACE: again from the ORIGINAL generator states
             cap = int(rec_ptr[-1])
             continue
-        _lib.check(rc, "gdm_des_run_batch_host")
+        _lib.check(rc, name)
         n = int(rec_ptr[-1])
-        return BatchLog(value[:n], eid[:n], node[:n], kind[:n], rec_ptr, n_rec, stop, k, p, h, g)
+        return BatchLog(value[:n], eid[:n], node[:n], rkind[:n], rec_ptr, n_rec, stop, k, p, h, g)
 
 
 def spec_arrays(specs):
@@ -308,9 +326,10 @@ def dist_arrays(specs):
 
 
 def run_batch_device(adj, loc, scale, queue_cap, seed, customers, states=None, *, device, max_events=200000,
-                     max_records=5001, max_queue_cap=None, workspace_tensor=None):
+                     max_records=5001, max_queue_cap=None, workspace_tensor=None, kind=None):
     """``gdm_des_run_batch``: the arrays of ``run_batch_host`` (numpy, or device tensors that stay where they are --
-    ``adj`` straight from ``ops.des_routing``) -> BatchLog of device tensors.  Nothing is read back."""
+    ``adj`` straight from ``ops.des_routing``) -> BatchLog of device tensors.  Nothing is read back.  ``kind`` as in
+    ``run_batch_host``: ``gdm_des_run_batch_dist``, the kernel that draws normal, exponential and uniform nodes."""
     import torch
     from . import ops
     dev = torch.device(device)
@@ -333,10 +352,14 @@ def run_batch_device(adj, loc, scale, queue_cap, seed, customers, states=None, *
         key, pos, has, gauss = pack_states(states, b)
         k, p, h, g = (up(key.view(np.int32), torch.int32), up(pos, torch.int32), up(has, torch.int32),
                       up(gauss, torch.float64))
-    out = ops.des_run_batch(up(adj, torch.float64), up(loc, torch.float64), up(scale, torch.float64),
-                            up(queue_cap, torch.int32), up(seed, torch.int64), up(customers, torch.int64), k, p, h, g,
-                            max_queue_cap=max_queue_cap, max_events=max_events, max_records=max_records,
-                            workspace_tensor=workspace_tensor)
+    tail = (up(queue_cap, torch.int32), up(seed, torch.int64), up(customers, torch.int64), k, p, h, g)
+    kw = dict(max_queue_cap=max_queue_cap, max_events=max_events, max_records=max_records,
+              workspace_tensor=workspace_tensor)
+    if kind is None:
+        out = ops.des_run_batch(up(adj, torch.float64), up(loc, torch.float64), up(scale, torch.float64), *tail, **kw)
+    else:
+        out = ops.des_run_batch_dist(up(adj, torch.float64), up(loc, torch.float64), up(scale, torch.float64),
+                                     up(kind, torch.int32), *tail, **kw)
     return BatchLog(*out, k, p, h, g)
 
 
@@ -383,6 +406,20 @@ def run_batch(specs, *, device=None, max_events=200000, max_records=5001, states
     if device is None:
         return run_batch_host(*arrays, states, math=1, max_events=max_events, max_records=max_records)
     return run_batch_device(*arrays, states, device=device, max_events=max_events, max_records=max_records)
+
+
+def run_batch_dist(specs, *, device=None, math=1, max_events=200000, max_records=5001, states=None):
+    """``run_batch`` for specs whose nodes may be any of DIST_KINDS (``dist_arrays``) -> BatchLog, the log whose
+    statistics ``run_stats`` returns.  The entries with kinds (``gdm_des_run_batch_dist[_host]``) run only when some
+    node is not normal.  ``math`` is the host mirror's (device=None): 0 = libm, the reference's bits, 1 = portable, the
+    device's.  The consumers of a BatchLog (``log_to_notes``, ``log_to_rolls``, ``ops.des_log_to_notes_pc``,
+    ``simlog_to_vid.log_tracks``) take it as it is; ``write_music_log(sample_log(log, b), path)`` writes sample b as
+    the reference's ``logs/simulation.log``."""
+    adj, kind, *rest = dist_arrays(specs)
+    kw = dict(max_events=max_events, max_records=max_records, kind=kind if kind.any() else None)   # all normal: as ever
+    if device is None:
+        return run_batch_host(adj, *rest, states, math=math, **kw)
+    return run_batch_device(adj, *rest, states, device=device, **kw)
 
 
 # ---- batched statistics: the same runs without a log ---------------------------------------------------------------------

@@ -547,6 +547,63 @@ int gdm_des_stats_batch_dist(const double* adj, int B, int dim, const double* lo
                              int64_t* n_records, int32_t* stop_reason, double* queue_time, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ---- the LOGGING simulator with a distribution KIND per node (csrc/des_batch.hip: des_batch_dist_kernel; des::AnyDist in
+ * csrc/des_sim.h) ------------------------------------------------------------------------------------------------------
+ * The argument lists of gdm_des_run_batch[_host] with `dist_kind` (B, dim) i32 of GDM_DES_DIST_* between `scale` and
+ * `queue_cap`, as the two statistics entries above order them (the records' own `kind` output keeps its place); same
+ * records, CSR layout, stop reasons, workspace (gdm_des_batch_workspace_bytes) and pack step.  The draws are those of
+ * gdm_des_stats_batch_dist[_host], so the log is the one whose statistics those entries return.
+ * A sample that stops with GDM_DES_STOP_ERROR has an empty log and KEEPS the generator state it came with (the rule of
+ * the statistics entries; gdm_des_run_batch[_host] write the state back after an error inside the chain).  With every
+ * kind 0 and no such sample the results are the bytes of gdm_des_run_batch[_host].
+ * Refused per sample, besides what the entries without kinds refuse: an exponential server with scale 0 and a uniform
+ * server with scale 0 and loc <= 0, when a customer reaches it.  A kind outside 0..2: the host entry reads its array
+ * and refuses the call (GDM_EINVAL, nothing runs); the device entry cannot, there the sample stops with
+ * GDM_DES_STOP_ERROR.  gdm_des_run_batch_dist_host: math 0 = libm (the reference's bits), 1 = portable, the device's. */
+int gdm_des_run_batch_dist_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                const int32_t* dist_kind, const int32_t* queue_cap, const int64_t* seed,
+                                const int64_t* number_of_customers, int max_queue_cap, int math, int64_t max_events,
+                                int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                                double* cached_gauss, double* value, int64_t* event_id, int32_t* node, int32_t* kind,
+                                int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason);
+int gdm_des_run_batch_dist(const double* adj, int B, int dim, const double* loc, const double* scale,
+                           const int32_t* dist_kind, const int32_t* queue_cap, const int64_t* seed,
+                           const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
+                           int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                           double* cached_gauss, double* value, int64_t* event_id, int32_t* node, int32_t* kind,
+                           int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- log -> queue tracks (csrc/des_tracks.hip; the reference's MMGAN_MIDI_DES/simlog_to_vid.ipynb, first cell) --------
+ * Per sample b, over the first max_lines records of its log [rec_ptr[b], rec_ptr[b + 1]) ('processing' records count
+ * towards max_lines and change nothing): an arrival (kind 0) at node n adds 1 to n's counter, a departure (kind 1)
+ * subtracts 1; after each of the two, if the sum of all counters is > 0, a row with the counters of the tracked nodes
+ * is appended; row 0 is a row of zeros.  col_of_node (B, dim) i32: the column of a node, -1 = not tracked; S columns.
+ * A reneged arrival is never subtracted: the numbers are arrivals minus departures, not queue lengths (the notebook's
+ * behaviour, kept).  Unlike the notebook, whose regular expression drops a line whose clock prints in exponent
+ * notation, every record counts.
+ * status (B) i32: 0, GDM_DES_TRACKS_ENODE (an arrival or departure at a node that is not tracked: the notebook's
+ * KeyError) or GDM_DES_TRACKS_EPTR (offsets outside the record arrays); such a sample has ZERO rows.
+ * gdm_des_log_tracks_count: device arrays -> n_rows (B) i64 and row_ptr (B + 1) i64, their exclusive scan.
+ * gdm_des_log_tracks: device arrays, row_ptr as the count wrote it -> tracks (n_rows_cap >= row_ptr[B] rows, S) i32,
+ *   sample b's rows at row_ptr[b]; one workgroup per sample, a kept row written as S consecutive int32.
+ * gdm_des_log_tracks_host: both steps on host arrays, the device's oracle; also checks col_of_node (inside -1..S-1, no
+ *   column twice).  tracks NULL with n_rows_cap 0 only counts; GDM_EWORKSPACE when n_rows_cap is too small (row_ptr[B]
+ *   then holds the count needed).                                                                                     */
+#define GDM_DES_TRACKS_ENODE 1
+#define GDM_DES_TRACKS_EPTR 2
+#define GDM_DES_TRACKS_MAX_DIM 4096
+#define GDM_DES_TRACKS_MAX_LINES ((int64_t)1 << 30)
+int gdm_des_log_tracks_count(const int32_t* node, const int32_t* kind, const int64_t* rec_ptr, int64_t n_records, int B,
+                             int dim, const int32_t* col_of_node, int64_t max_lines, int64_t* n_rows, int64_t* row_ptr,
+                             int32_t* status, void* stream);
+int gdm_des_log_tracks(const int32_t* node, const int32_t* kind, const int64_t* rec_ptr, int64_t n_records, int B,
+                       int dim, const int32_t* col_of_node, int S, int64_t max_lines, const int64_t* row_ptr,
+                       int64_t n_rows_cap, int32_t* tracks, void* stream);
+int gdm_des_log_tracks_host(const int32_t* node, const int32_t* kind, const int64_t* rec_ptr, int64_t n_records, int B,
+                            int dim, const int32_t* col_of_node, int S, int64_t max_lines, int64_t* n_rows,
+                            int64_t* row_ptr, int32_t* status, int32_t* tracks, int64_t n_rows_cap);
+
 /* ---- generic convolution lowering helpers (model 2 discriminator, model 1 generator) ----------------------------
  * im2col for Conv2d fwd / dW and col2im (gather form, deterministic) for Conv2d dX and ConvTranspose2d fwd.
  * Activations are channels-last (B,H,W,C) unless `src_planar` (NCHW fp32 input planes, e.g. the piano-roll).
