@@ -142,6 +142,12 @@ SIGNATURES = {
                                          _L, _P, _P, _P]),
     "gdm_des_run_batch_dist": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P,
                                     _P, _P, _P, _Z, _P]),
+    "gdm_des_stats_batch_net_host": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _L] + [_P] * 19),
+    "gdm_des_stats_batch_net": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _L] + [_P] * 19 + [_P, _Z, _P]),
+    "gdm_des_run_batch_net_host": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        _L, _P, _P, _P]),
+    "gdm_des_run_batch_net": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P,
+                                   _P, _P, _P, _Z, _P]),
     "gdm_des_log_tracks_count": (_I, [_P, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P, _P]),
     "gdm_des_log_tracks": (_I, [_P, _P, _P, _L, _I, _I, _P, _I, _L, _P, _L, _P, _P]),
     "gdm_des_log_tracks_host": (_I, [_P, _P, _P, _L, _I, _I, _P, _I, _L, _P, _P, _P, _P, _L]),

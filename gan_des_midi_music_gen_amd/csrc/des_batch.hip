@@ -15,9 +15,10 @@
 // and the FIFO rings (L2-resident: about 330 KB per sample at dim 61, capacity 254).
 // The prologue up to the chain, the LDS block and the workspace layout are des_wave.h's, shared with the log-free
 // statistics kernel of des_stats.hip.
-// Two kernels over one body (batch_sample): des_batch_kernel draws 'normal' only (des::NormalOnly, the bridges' nets);
+// Three kernels over one body (batch_sample): des_batch_kernel draws 'normal' only (des::NormalOnly, the bridges' nets);
 // des_batch_dist_kernel takes a kind per node (des::AnyDist: normal, exponential, uniform), its row staged into LDS
-// (512 B more), and leaves the generator state of a sample that errors as it came.
+// (512 B more), and leaves the generator state of a sample that errors as it came; des_batch_net_kernel is that kernel
+// with the reference's 'queue' and 'branch' nodes as well (des::AnyNode: kinds and node state, 2 KB of LDS).
 // Bounds: every index the chain computes is checked in des_sim.h before it forms an address; every loop is bounded by
 // max_events, max_records or the draw budget.
 #include "gdm_common.h"
@@ -34,6 +35,7 @@ constexpr int kPackThreads = 256;
 typedef des::Sim<des::MathPortable, des::OutSoa> DevSim;
 
 typedef des::Sim<des::MathPortable, des::OutSoa, des::NoStats, des::AnyDist> DevDistSim;
+typedef des::Sim<des::MathPortable, des::OutSoa, des::NoStats, des::AnyNode> DevNetSim;
 
 // the kinds of one sample (des_batch_dist_kernel only: des_wave::Lds is the layout of the kernels that have none)
 struct DistLds {
@@ -131,6 +133,17 @@ __global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_batch_d
   batch_sample<true>(s, lds, s_dyn, DES_BATCH_ARGS);
 }
 
+// The logging kernel with a kind per node that may be 'queue' or 'branch' (des::AnyNode); flatten as above
+__global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_batch_net_kernel(
+    DES_BATCH_PARAMS, const int32_t* __restrict__ node_kind) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
+  __shared__ des_wave::Lds lds;
+  __shared__ des_wave::NetLds nl;
+  DevNetSim s;
+  des_wave::stage_net(s.dist, nl, node_kind, dim, blockIdx.x, threadIdx.x);
+  batch_sample<true>(s, lds, s_dyn, DES_BATCH_ARGS);
+}
+
 // counts -> rec_ptr (exclusive scan, one workgroup), then the records of sample b move from b * max_records down to
 // rec_ptr[b].  A destination never lies above its source and a sample's destination range ends at or below the next
 // sample's source, so ascending samples and ascending chunks -- each chunk read completely before it is written -- are
@@ -204,7 +217,7 @@ extern "C" int64_t gdm_des_batch_workspace_bytes(int B, int dim, int max_queue_c
   return (int64_t)(ws_layout(dim, max_queue_cap, false).per_sample * (size_t)B);
 }
 
-// the checks both device entries make on the host; `who` names the entry in the message
+// the checks the device entries make on the host; `who` names the entry in the message
 static int check_batch_args(const char* who, const BatchArgs& a, int B, const int32_t* dist_kind, bool with_kind,
                             int64_t n_records_cap, const int64_t* rec_ptr, size_t workspace_bytes) {
   GDM_REQUIRE(a.adj && a.loc && a.scale && a.queue_cap && a.seed && a.number_of_customers && a.mt_key && a.mt_pos &&
@@ -270,6 +283,28 @@ extern "C" int gdm_des_run_batch_dist(const double* adj, int B, int dim, const d
                      has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
                      (unsigned char*)workspace, dist_kind);
   GDM_LAUNCH_OK("gdm_des_run_batch_dist");
+  return gdm_des_pack(B, max_records, n_records, rec_ptr, value, event_id, node, kind, stream);
+}
+
+extern "C" int gdm_des_run_batch_net(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                     const int32_t* node_kind, const int32_t* queue_cap, const int64_t* seed,
+                                     const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
+                                     int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                                     double* cached_gauss, double* value, int64_t* event_id, int32_t* node,
+                                     int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records,
+                                     int32_t* stop_reason, void* workspace, size_t workspace_bytes, void* stream) {
+  const BatchArgs a{adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records,
+                    mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
+                    (unsigned char*)workspace};
+  const int rc =
+      check_batch_args("gdm_des_run_batch_net", a, B, node_kind, true, n_records_cap, rec_ptr, workspace_bytes);
+  if (rc != GDM_OK) return rc;
+  const size_t lds_dyn = des_wave::lds_dyn_bytes(dim);
+  hipLaunchKernelGGL(des_batch_net_kernel, dim3(B), dim3(GDM_WAVE), lds_dyn, (hipStream_t)stream, adj, dim, loc, scale,
+                     queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records, mt_key, mt_pos,
+                     has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
+                     (unsigned char*)workspace, node_kind);
+  GDM_LAUNCH_OK("gdm_des_run_batch_net");
   return gdm_des_pack(B, max_records, n_records, rec_ptr, value, event_id, node, kind, stream);
 }
 

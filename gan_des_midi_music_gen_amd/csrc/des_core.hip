@@ -5,8 +5,10 @@
 // 106-110): 'normal' service / inter-arrival distributions, logging_mode 'Music', probability routing.
 //
 // The event logic itself lives in des_sim.h (shared with the device kernel of des_batch.hip); this file holds its HOST
-// instantiations: gdm_des_run (libm math, numpy's bits), gdm_des_run_batch_host (the batch mirror) and
-// gdm_des_run_batch_dist_host (the batch mirror with a distribution kind per node, des::AnyDist).
+// instantiations: gdm_des_run (libm math, numpy's bits), gdm_des_run_batch_host (the batch mirror),
+// gdm_des_run_batch_dist_host (the batch mirror with a distribution kind per node, des::AnyDist) and
+// gdm_des_run_batch_net_host (with the reference's 'queue' and 'branch' nodes as well, des::AnyNode); the statistics
+// entries gdm_des_stats_batch[_dist|_net]_host likewise.
 //
 // HOST code ("a deterministic, event-count-capped C++ DES core"): the simulation is one
 // dependent event chain per sample (des_batch.hip runs a batch of them, one wave each).  What makes it a drop-in is that it reproduces the reference's
@@ -94,6 +96,34 @@ struct HostSim {
 // the kinds of sample b, where the policy has any
 inline void bind_kind(des::NormalOnly&, const int32_t*, size_t) {}
 inline void bind_kind(des::AnyDist& d, const int32_t* kind, size_t row) { d.kind = kind + row; }
+inline void bind_kind(des::AnyNode& d, const int32_t* kind, size_t row) { d.kind = kind + row; }
+
+// the per-node state of a policy, where it has any: bound and reset before every sample
+template <class Dist>
+struct NodeState {
+  explicit NodeState(int) {}
+  void bind(Dist&, int) {}
+};
+template <>
+struct NodeState<des::AnyNode> {
+  std::vector<int32_t> delayed;
+  std::vector<double> next_departure;
+  explicit NodeState(int dim) : delayed(dim), next_departure(dim) {}
+  void bind(des::AnyNode& d, int dim) {
+    d.delayed = delayed.data();
+    d.next_departure = next_departure.data();
+    d.reset(dim, 0, 1);
+  }
+};
+
+// every kind of a (B, dim) array within [0, last]; `who` names the entry in the message
+int check_kinds(const char* who, const int32_t* kind, int B, int dim, int last) {
+  for (int64_t i = 0; i < (int64_t)B * dim; ++i)
+    GDM_REQUIRE(kind[i] >= GDM_DES_DIST_NORMAL && kind[i] <= last,
+                "%s: kind %d at sample %lld, node %lld is none of GDM_DES_DIST_*", who, kind[i], (long long)(i / dim),
+                (long long)(i % dim));
+  return GDM_OK;
+}
 
 // Dist = des::NormalOnly for gdm_des_run_batch_host (dist_kind is not read), des::AnyDist for
 // gdm_des_run_batch_dist_host; `who` names the entry in the message.  kErrorKeepsState: a sample whose chain ends in
@@ -107,12 +137,14 @@ int run_batch_host(const char* who, const double* adj, int B, int dim, const dou
                    int64_t* event_id, int32_t* node, int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr,
                    int64_t* n_records, int32_t* stop_reason) {
   HostSim<Math, des::OutSoa, des::NoStats, Dist> h(dim, max_queue_cap);
+  NodeState<Dist> nodes(dim);
   int64_t at = 0;                                       // records written so far (needed, when the arrays overflow)
   bool overflow = false;
   rec_ptr[0] = 0;
   for (int b = 0; b < B; ++b) {
     des::Sim<Math, des::OutSoa, des::NoStats, Dist>& s = h.s;
     bind_kind(s.dist, dist_kind, (size_t)b * dim);
+    nodes.bind(s.dist, dim);
     const int64_t room = n_records_cap > at ? n_records_cap - at : 0;
     const int64_t off = room > 0 ? at : 0;
     s.out = des::OutSoa{value + off, event_id + off, node + off, kind + off};
@@ -167,12 +199,14 @@ void stats_batch_host(const double* adj, int B, int dim, const double* loc, cons
                       int max_queue_cap, int64_t max_events, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
                       double* cached_gauss, const StatsOut& o) {
   HostSim<Math, des::OutNone, des::NodeStats, Dist> h(dim, max_queue_cap);
+  NodeState<Dist> nodes(dim);
   std::vector<double> atime((size_t)dim * max_queue_cap), last_change(dim);
   const int64_t hist_stride = (int64_t)max_queue_cap + 1;
   for (int b = 0; b < B; ++b) {
     des::Sim<Math, des::OutNone, des::NodeStats, Dist>& s = h.s;
     const size_t row = (size_t)b * dim;
     bind_kind(s.dist, kind, row);
+    nodes.bind(s.dist, dim);
     s.out_cap = INT64_MAX;
     s.max_records = 0;
     s.draws_left = (int64_t)DES_DRAW_FACTOR * (max_events + dim + 1);
@@ -340,14 +374,29 @@ extern "C" int gdm_des_run_batch_dist_host(const double* adj, int B, int dim, co
                                            int64_t* n_records, int32_t* stop_reason) {
   GDM_REQUIRE(dist_kind, "gdm_des_run_batch_dist_host: null pointer");
   GDM_REQUIRE(B >= 1 && dim >= 1, "gdm_des_run_batch_dist_host: B >= 1, dim >= 1");
-  for (int64_t i = 0; i < (int64_t)B * dim; ++i)
-    GDM_REQUIRE(dist_kind[i] >= GDM_DES_DIST_NORMAL && dist_kind[i] <= GDM_DES_DIST_UNIFORM,
-                "gdm_des_run_batch_dist_host: kind %d at sample %lld, node %lld is none of GDM_DES_DIST_*",
-                dist_kind[i], (long long)(i / dim), (long long)(i % dim));
+  const int rc = check_kinds("gdm_des_run_batch_dist_host", dist_kind, B, dim, GDM_DES_DIST_UNIFORM);
+  if (rc != GDM_OK) return rc;
   return run_batch_host_entry<des::AnyDist, true>("gdm_des_run_batch_dist_host", adj, B, dim, loc, scale, dist_kind,
                                             queue_cap, seed, number_of_customers, max_queue_cap, math, max_events,
                                             max_records, mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node,
                                             kind, n_records_cap, rec_ptr, n_records, stop_reason);
+}
+
+extern "C" int gdm_des_run_batch_net_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                          const int32_t* node_kind, const int32_t* queue_cap, const int64_t* seed,
+                                          const int64_t* number_of_customers, int max_queue_cap, int math,
+                                          int64_t max_events, int64_t max_records, uint32_t* mt_key, int32_t* mt_pos,
+                                          int32_t* has_gauss, double* cached_gauss, double* value, int64_t* event_id,
+                                          int32_t* node, int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr,
+                                          int64_t* n_records, int32_t* stop_reason) {
+  GDM_REQUIRE(node_kind, "gdm_des_run_batch_net_host: null pointer");
+  GDM_REQUIRE(B >= 1 && dim >= 1, "gdm_des_run_batch_net_host: B >= 1, dim >= 1");
+  const int rc = check_kinds("gdm_des_run_batch_net_host", node_kind, B, dim, GDM_DES_DIST_BRANCH);
+  if (rc != GDM_OK) return rc;
+  return run_batch_host_entry<des::AnyNode, true>("gdm_des_run_batch_net_host", adj, B, dim, loc, scale, node_kind,
+                                                  queue_cap, seed, number_of_customers, max_queue_cap, math, max_events,
+                                                  max_records, mt_key, mt_pos, has_gauss, cached_gauss, value, event_id,
+                                                  node, kind, n_records_cap, rec_ptr, n_records, stop_reason);
 }
 
 extern "C" int gdm_des_math_probe_host(const double* x, int64_t n, double* log_out, double* factor_out) {
@@ -398,19 +447,46 @@ extern "C" int gdm_des_stats_batch_dist_host(const double* adj, int B, int dim, 
   const StatsOut o{served, reneges, generated, max_queue, time_in_service, time_in_queue, queue_area, arrival_time,
                    clock, end_time, total_customers, events, n_records, stop_reason, queue_time};
   GDM_REQUIRE(kind, "gdm_des_stats_batch_dist_host: null pointer");
-  const int rc = check_stats_host("gdm_des_stats_batch_dist_host", adj, B, dim, loc, scale, queue_cap, seed,
-                                  number_of_customers, max_queue_cap, math, max_events, mt_key, mt_pos, has_gauss,
-                                  cached_gauss, o);
+  int rc = check_stats_host("gdm_des_stats_batch_dist_host", adj, B, dim, loc, scale, queue_cap, seed,
+                            number_of_customers, max_queue_cap, math, max_events, mt_key, mt_pos, has_gauss,
+                            cached_gauss, o);
   if (rc != GDM_OK) return rc;
-  for (int64_t i = 0; i < (int64_t)B * dim; ++i)
-    GDM_REQUIRE(kind[i] >= GDM_DES_DIST_NORMAL && kind[i] <= GDM_DES_DIST_UNIFORM,
-                "gdm_des_stats_batch_dist_host: kind %d at sample %lld, node %lld is none of GDM_DES_DIST_*", kind[i],
-                (long long)(i / dim), (long long)(i % dim));
+  rc = check_kinds("gdm_des_stats_batch_dist_host", kind, B, dim, GDM_DES_DIST_UNIFORM);
+  if (rc != GDM_OK) return rc;
   if (math == 0)
     stats_batch_host<MathLibm, des::AnyDist>(adj, B, dim, loc, scale, kind, queue_cap, seed, number_of_customers,
                                              max_queue_cap, max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
   else
     stats_batch_host<des::MathPortable, des::AnyDist>(adj, B, dim, loc, scale, kind, queue_cap, seed,
+                                                      number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,
+                                                      has_gauss, cached_gauss, o);
+  return GDM_OK;
+}
+
+extern "C" int gdm_des_stats_batch_net_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                            const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
+                                            const int64_t* number_of_customers, int max_queue_cap, int math,
+                                            int64_t max_events, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                                            double* cached_gauss, int64_t* served, int64_t* reneges,
+                                            int64_t* generated, int32_t* max_queue, double* time_in_service,
+                                            double* time_in_queue, double* queue_area, double* arrival_time,
+                                            double* clock, double* end_time, int64_t* total_customers,
+                                            int64_t* events, int64_t* n_records, int32_t* stop_reason,
+                                            double* queue_time) {
+  const StatsOut o{served, reneges, generated, max_queue, time_in_service, time_in_queue, queue_area, arrival_time,
+                   clock, end_time, total_customers, events, n_records, stop_reason, queue_time};
+  GDM_REQUIRE(kind, "gdm_des_stats_batch_net_host: null pointer");
+  int rc = check_stats_host("gdm_des_stats_batch_net_host", adj, B, dim, loc, scale, queue_cap, seed,
+                            number_of_customers, max_queue_cap, math, max_events, mt_key, mt_pos, has_gauss,
+                            cached_gauss, o);
+  if (rc != GDM_OK) return rc;
+  rc = check_kinds("gdm_des_stats_batch_net_host", kind, B, dim, GDM_DES_DIST_BRANCH);
+  if (rc != GDM_OK) return rc;
+  if (math == 0)
+    stats_batch_host<MathLibm, des::AnyNode>(adj, B, dim, loc, scale, kind, queue_cap, seed, number_of_customers,
+                                             max_queue_cap, max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
+  else
+    stats_batch_host<des::MathPortable, des::AnyNode>(adj, B, dim, loc, scale, kind, queue_cap, seed,
                                                       number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,
                                                       has_gauss, cached_gauss, o);
   return GDM_OK;

@@ -31,7 +31,8 @@
 // builds) or NodeStats, the per-node queueing statistics of the reference's Server / Source objects.
 //
 // Dist is the distribution policy: NormalOnly (empty: every draw is norm_rvs, the bridges' nets) or AnyDist, a kind per
-// node -- normal, exponential or uniform.
+// node -- normal, exponential or uniform -- or AnyNode, which adds the reference's two node kinds without a distribution:
+// 'queue' (a waiting room whose departures wait for an idle child) and 'branch' (a zero-time router).
 //
 // Math is a policy (template parameter): log / sqrt of the polar method.  DesMathPortable is plain double arithmetic
 // (+ - * / and bit manipulation, contraction off, no FMA) and gives the same bits on the host and on gfx950; the host
@@ -221,9 +222,12 @@ struct NoStats {
   DES_HD void service(int, double) const {}
   DES_HD void renege(int) const {}
   DES_HD void generate(int, double) const {}
-  DES_HD void enqueue(int, int64_t, double, int64_t) const {}
+  DES_HD void enqueue(int, int64_t, double, int64_t, int64_t) const {}
   DES_HD void dequeue(int, int64_t, double, int64_t) const {}
-  DES_HD void finish(const uint8_t*, const int32_t*, int) const {}
+  DES_HD void held(int, double, int64_t) const {}
+  DES_HD void delay(int, double) const {}
+  template <class D>
+  DES_HD void finish(const uint8_t*, const int32_t*, int, const D&) const {}
 };
 
 // Storage is the caller's: (dim) per array, atime (dim, ring_stride) beside the id ring and indexed like it, queue_time
@@ -273,19 +277,24 @@ struct NodeStats {
     if (queue_time && len >= 0 && len < hist_stride) queue_time[(int64_t)node * hist_stride + len] += d;
     last_change[node] = t;
   }
-  // slot: the ring slot Sim checked and used for the customer's id; len: the queue length before the change
-  DES_HD void enqueue(int node, int64_t slot, double t, int64_t len) {
+  // slot: the ring slot Sim checked and used for the customer's id; len: the queue length before the change; held: the
+  // node's delayed departures (AnyNode; else 0), which count in the time at queue length (477) but not in max_queue (560)
+  DES_HD void enqueue(int node, int64_t slot, double t, int64_t len, int64_t held) {
     atime[(int64_t)node * ring_stride + slot] = t;
-    integrate(node, t, len);
+    integrate(node, t, len + held);
     if (len + 1 > (int64_t)max_queue[node]) max_queue[node] = (int32_t)(len + 1);
   }
   DES_HD void dequeue(int node, int64_t slot, double t, int64_t len) {
     time_in_queue[node] += t - atime[(int64_t)node * ring_stride + slot];
     integrate(node, t, len);
   }
-  DES_HD void finish(const uint8_t* is_source, const int32_t* qlen, int dim) {
+  // the number of delayed departures of a node is about to change; len: queue length + delayed departures before it
+  DES_HD void held(int node, double t, int64_t len) { integrate(node, t, len); }
+  DES_HD void delay(int node, double dt) { time_in_queue[node] += dt; }                // 697
+  template <class D>
+  DES_HD void finish(const uint8_t* is_source, const int32_t* qlen, int dim, const D& dist) {
     for (int i = 0; i < dim; ++i)
-      if (!is_source[i]) integrate(i, end_time, qlen[i]);
+      if (!is_source[i]) integrate(i, end_time, qlen[i] + dist.held(i));
   }
 };
 
@@ -299,14 +308,28 @@ struct NodeStats {
 #define DES_DIST_NORMAL 0
 #define DES_DIST_EXPONENTIAL 1
 #define DES_DIST_UNIFORM 2
-struct NormalOnly {
+// What a policy without node kinds answers at the sites where AnyNode (below) acts: nothing is held back, every server
+// draws its service time, no departure waits.  Constants and empty bodies: the code is what it was without them.
+struct PlainNodes {
+  DES_HOOK bool timeless(int) const { return false; }
+  DES_HOOK bool waits(int) const { return false; }
+  DES_HOOK int64_t held(int) const { return 0; }
+  DES_HOOK void scheduled(int, double) const {}
+  DES_HOOK void idle(int) const {}
+  template <class S>
+  DES_HOOK void popped(S&, int, int) const {}
+  // a departure with nowhere to go: queue-type nodes (delayed departures) are AnyNode's
+  template <class S>
+  DES_HOOK void delay(S& s, int, int64_t) const { s.fail(); }
+};
+struct NormalOnly : PlainNodes {
   template <class S>
   DES_HOOK double rvs(S& s, int node) const { return s.norm_rvs(node); }
   // with scale == 0 the node's value is 0.0 whatever loc[] holds (schedule_departure: `while (service <= 0)`)
   DES_HOOK bool ignores_loc(int) const { return false; }
   DES_HOOK bool kinds_ok(int) const { return true; }
 };
-struct AnyDist {
+struct AnyDist : PlainNodes {
   const int32_t* kind;        // (dim) DES_DIST_*
   template <class S>
   DES_HOOK double rvs(S& s, int node) const {
@@ -322,6 +345,76 @@ struct AnyDist {
     for (int i = 0; i < dim; ++i)
       if (kind[i] < DES_DIST_NORMAL || kind[i] > DES_DIST_UNIFORM) return false;
     return true;
+  }
+};
+
+// ---- the node policy with the reference's two kinds WITHOUT a distribution (Server.__init__, 193-197) beside AnyDist's:
+//   kind 3 'queue'   a waiting room in front of its children.  Service time 0, no draw.  Its departure takes no routing
+//                    draw (get_destination returns None, 707): the first idle child that is a server is taken (628-633);
+//                    if there is none and the node is no sink, the departure is scheduled again at the earliest next
+//                    departure among the children (656-673, schedule_delayed_departure 679-697) -- exactly another
+//                    event's time, so Python's heapq order decides; a delayed event that pops first is delayed again
+//   kind 4 'branch'  a router: service time 0, no draw, routed like any server on the global stream
+// Both are servers with in_service, a FIFO and a capacity.  `delayed` is the reference's Server.delayed_departures (0 or
+// 1: the event list holds one departure per server), `next_departure` its EventList.servers_next_departure: +inf until
+// the node first schedules a departure (sources never do), 0 once it goes idle.  Admission and the time at queue length
+// count queue + delayed (557, 477).  As a SOURCE either kind raises upstream (Source.__init__: "Distribution not
+// supported") and ends the sample here; so does a delayed time of +inf (every child a source: the run is not defined by
+// the inputs alone).  Kinds 0..2 draw through AnyDist's own code.
+#define DES_DIST_QUEUE 3
+#define DES_DIST_BRANCH 4
+struct AnyNode {
+  const int32_t* kind;        // (dim) DES_DIST_*
+  int32_t* delayed;           // (dim)
+  double* next_departure;     // (dim)
+  DES_HD void reset(int dim, int first, int step) const {
+    for (int i = first; i < dim; i += step) {
+      delayed[i] = 0;
+      next_departure[i] = double_of(0x7ff0000000000000ULL);
+    }
+  }
+  template <class S>
+  DES_HOOK double rvs(S& s, int node) const {
+    if (kind[node] >= DES_DIST_QUEUE) {                     // only a source gets here (timeless)
+      s.fail();
+      return 0.0;
+    }
+    return AnyDist{{}, kind}.rvs(s, node);
+  }
+  DES_HOOK bool ignores_loc(int node) const { return kind[node] == DES_DIST_EXPONENTIAL; }
+  DES_HOOK bool kinds_ok(int dim) const {
+    for (int i = 0; i < dim; ++i)
+      if (kind[i] < DES_DIST_NORMAL || kind[i] > DES_DIST_BRANCH) return false;
+    return true;
+  }
+  DES_HOOK bool timeless(int node) const { return kind[node] >= DES_DIST_QUEUE; }
+  DES_HOOK bool waits(int node) const { return kind[node] == DES_DIST_QUEUE; }
+  DES_HOOK int64_t held(int node) const { return delayed[node]; }
+  DES_HOOK void scheduled(int node, double t) const { next_departure[node] = t; }       // 609
+  DES_HOOK void idle(int node) const { next_departure[node] = 0.0; }                    // 648
+  template <class S>
+  DES_HOOK void popped(S& s, int node, int was_delayed) const {                         // 622-624
+    if (!was_delayed) return;
+    s.stats.held(node, s.clock, (int64_t)s.qlen[node] + delayed[node]);
+    --delayed[node];
+  }
+  template <class S>
+  DES_HOOK void delay(S& s, int node, int64_t id) const {                               // 656-673, 679-697
+    double t = double_of(0x7ff0000000000000ULL);
+    const int32_t* ch = s.children + (int64_t)node * s.dim;
+    const int n = s.nchild[node] < s.dim ? s.nchild[node] : s.dim;
+    for (int k = 0; k < n; ++k) {
+      const int c = ch[k];
+      if (c < 0 || c >= s.dim || c == node) continue;
+      if (next_departure[c] < t) t = next_departure[c];
+    }
+    if (!(t < double_of(0x7ff0000000000000ULL))) { s.fail(); return; }
+    s.in_service[node] = 1;
+    s.stats.held(node, s.clock, (int64_t)s.qlen[node] + delayed[node]);
+    ++delayed[node];
+    s.push(Ev{t, id, 2, node, -1, 1});
+    next_departure[node] = t;
+    s.stats.delay(node, t - s.clock);
   }
 };
 
@@ -471,7 +564,7 @@ struct Sim {
   }
   // what the batch entries require of one sample before anything runs (a refused sample stops with DES_STOP_ERROR and
   // leaves the generator state as it came): scale >= 0, every queue fits its ring, a 32-bit seed, a valid position,
-  // every kind one of DES_DIST_*
+  // every kind one the policy knows
   DES_HD bool spec_ok(int64_t seed, int32_t global_pos) const {
     if (seed < 0 || seed > 0xffffffffLL || global_pos < 0 || global_pos > DES_MT_N) return false;
     for (int i = 0; i < dim; ++i)
@@ -563,14 +656,17 @@ struct Sim {
   DES_HD void schedule_departure(int server_id, int64_t event_id) {     // 591-612
     in_service[server_id] = 1;
     double service = 0.0;
-    // upstream: the loop never ends -- no draw is made (scale 0: nothing counts against the budget) and the value is <= 0
-    if (scale[server_id] == 0.0 && (dist.ignores_loc(server_id) || loc[server_id] <= 0.0)) { fail(); return; }
-    while (service <= 0 && !stop) service = dist.rvs(*this, server_id);
-    if (stop) return;
+    if (!dist.timeless(server_id)) {                   // (598: a queue or branch node draws nothing, its service is 0)
+      // upstream: the loop never ends -- no draw is made (scale 0: nothing counts against the budget) and the value is <= 0
+      if (scale[server_id] == 0.0 && (dist.ignores_loc(server_id) || loc[server_id] <= 0.0)) { fail(); return; }
+      while (service <= 0 && !stop) service = dist.rvs(*this, server_id);
+      if (stop) return;
+    }
     stats.service(server_id, service);
     log(service, event_id, server_id, 2);
     if (stop) return;
     push(Ev{clock + service, event_id, 2, server_id, -1, 0});
+    dist.scheduled(server_id, clock + service);
   }
   DES_HD void process_arrival(int server_id, int source, int64_t id) {  // 536-588
     log(clock, id, server_id, 0);
@@ -579,7 +675,7 @@ struct Sim {
     if (in_service[server_id] == 0) {
       schedule_departure(server_id, id);
       if (stop) return;
-    } else if ((int64_t)qlen[server_id] < (int64_t)qcap[server_id]) {
+    } else if ((int64_t)qlen[server_id] + dist.held(server_id) < (int64_t)qcap[server_id]) {
       const int64_t n = qlen[server_id];
       if (n < 0 || n >= ring_stride) { fail(); return; }
       int64_t slot = (int64_t)qhead[server_id] + n;
@@ -587,7 +683,7 @@ struct Sim {
       if (slot < 0 || slot >= ring_stride) { fail(); return; }
       ring[(int64_t)server_id * ring_stride + slot] = id;
       qlen[server_id] = (int32_t)(n + 1);
-      stats.enqueue(server_id, slot, clock, n);
+      stats.enqueue(server_id, slot, clock, n, dist.held(server_id));
     } else {
       stats.renege(server_id);                         // the customer reneges
     }
@@ -599,11 +695,12 @@ struct Sim {
       ++total_customers;
     }
   }
-  DES_HD void process_departure(int server_id, int64_t id) {            // 615-677
+  DES_HD void process_departure(int server_id, int64_t id, int was_delayed) {            // 615-677
     log(clock, id, server_id, 1);
     if (stop) return;
     if (server_id < 0 || server_id >= dim) { fail(); return; }
-    int next = destination(server_id);
+    dist.popped(*this, server_id, was_delayed);
+    int next = dist.waits(server_id) ? -1 : destination(server_id);
     if (stop) return;
     const bool sink = (bflags[server_id] & DES_BRANCH_SINK) != 0;
     if (next < 0) {                                    // sink-like node: first idle child that is a server (628-633)
@@ -620,16 +717,17 @@ struct Sim {
         if (h < 0 || h >= ring_stride) { fail(); return; }
         const int64_t customer = ring[(int64_t)server_id * ring_stride + h];
         qhead[server_id] = (int32_t)(h + 1 >= ring_stride ? 0 : h + 1);
-        stats.dequeue(server_id, h, clock, qlen[server_id]);
+        stats.dequeue(server_id, h, clock, qlen[server_id] + dist.held(server_id));
         --qlen[server_id];
         schedule_departure(server_id, customer);
         if (stop) return;
       } else {
         in_service[server_id] = 0;
+        dist.idle(server_id);
       }
       if (!sink) process_arrival(next, -1, id);
     } else {
-      fail();                                          // queue-type nodes (delayed departures): not produced by the bridges
+      dist.delay(*this, server_id, id);                // queue-type nodes (delayed departures): AnyNode only, else an error
     }
   }
 
@@ -655,10 +753,10 @@ struct Sim {
       clock = evt.time;
       stats.event();
       if (evt.type == 1) process_arrival(evt.server, evt.source, evt.id);
-      else process_departure(evt.server, evt.id);
+      else process_departure(evt.server, evt.id, evt.pad);
       if (++processed >= max_events && max_events > 0) { reason = DES_STOP_EVENTS; break; }   // (reference: wall clock)
     }
-    stats.finish(is_source, qlen, dim);
+    stats.finish(is_source, qlen, dim, dist);
     return stop ? stop : reason;
   }
 };

@@ -4,15 +4,18 @@
 // accumulators every Server / Source of the reference carries (SIMULATOR/simulation_v3.py:207-217, 280-281), from
 // which Sim.calculate_metrics (752-824) derives utilisation, waiting times, renege rates and L / LQ / W / WQ.
 //
-// Two kernels over one body (stats_sample): des_stats_kernel draws 'normal' only (des::NormalOnly, the bridges' nets);
-// des_stats_dist_kernel takes a kind per node (des::AnyDist: normal, exponential, uniform), its row staged into LDS.
+// Three kernels over one body (stats_sample): des_stats_kernel draws 'normal' only (des::NormalOnly, the bridges' nets);
+// des_stats_dist_kernel takes a kind per node (des::AnyDist: normal, exponential, uniform), its row staged into LDS;
+// des_stats_net_kernel takes the reference's 'queue' and 'branch' nodes as well (des::AnyNode), with the two per-node
+// arrays of that policy -- delayed departures, next departure time -- in LDS beside the kinds.
 //
 // Mapping as in des_batch.hip, one WAVE per sample (des_wave.h is the shared prologue): all lanes stage the parameters,
 // build the routing tables and seed the node generators; lane 0 runs the chain; then ALL lanes write the (dim) rows
 // with ordinary vector stores.  No record arrays, no pack step.
 // LDS: the block of des_wave.h (16.2 KB) + eight 8-byte and one 4-byte accumulator per node (8.5 KB at the maximum of
 // 128 nodes) + the node generators when dim <= 15 (36.6 KB): 61.3 KB, below the 64 KB a workgroup may have; the kinds
-// of des_stats_dist_kernel add 512 B (61.8 KB).  Global memory holds what a sample cannot keep there: routing tables,
+// of des_stats_dist_kernel add 512 B (61.8 KB), the kinds and node state of des_stats_net_kernel 2 KB (63.3 KB: the
+// static_assert below adds the blocks up).  Global memory holds what a sample cannot keep there: routing tables,
 // the FIFO ring of customer ids and, slot for slot beside it, the ring of their arrival times (workspace), and the
 // optional time-at-queue-length histogram (an output).
 // Bounds: every index the chain computes is checked in des_sim.h before it forms an address -- the arrival-time ring
@@ -30,6 +33,7 @@ namespace {
 using des_wave::kMaxDim;
 typedef des::Sim<des::MathPortable, des::OutNone, des::NodeStats> StatSim;
 typedef des::Sim<des::MathPortable, des::OutNone, des::NodeStats, des::AnyDist> DistSim;
+typedef des::Sim<des::MathPortable, des::OutNone, des::NodeStats, des::AnyNode> NetSim;
 
 struct StatsLds {
   int64_t served[kMaxDim], reneges[kMaxDim], generated[kMaxDim];
@@ -44,7 +48,11 @@ struct DistLds {
   int32_t kind[kMaxDim];
 };
 
-// the (B, dim) and (B) outputs of both kernels, and the inputs they share
+static_assert(sizeof(des_wave::Lds) + sizeof(StatsLds) + sizeof(des_wave::NetLds) + 16 * 3 +
+                      (size_t)des_wave::kLdsGenDim * DES_MT_N * 4 <= 64 * 1024,
+              "des_stats_net_kernel: static + dynamic LDS beyond a workgroup's 64 KB");
+
+// the (B, dim) and (B) outputs of the kernels, and the inputs they share
 struct StatsArgs {
   const double* adj;
   int dim;
@@ -174,7 +182,21 @@ __global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_stats_d
   stats_sample(s, lds, acc, s_dyn, DES_STATS_ARGS);
 }
 
-// the checks both device entries make on the host; `who` names the entry in the message
+// The statistics kernel with a kind per node that may be 'queue' or 'branch' (des::AnyNode).  flatten for the reason
+// des_stats_dist_kernel has it; the prologue's first barrier orders the staged kinds and the reset node state before
+// lane 0 reads them
+__global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_stats_net_kernel(
+    DES_STATS_PARAMS, const int32_t* __restrict__ kind) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
+  __shared__ des_wave::Lds lds;
+  __shared__ StatsLds acc;
+  __shared__ des_wave::NetLds nl;
+  NetSim s;
+  des_wave::stage_net(s.dist, nl, kind, dim, blockIdx.x, threadIdx.x);
+  stats_sample(s, lds, acc, s_dyn, DES_STATS_ARGS);
+}
+
+// the checks the device entries make on the host; `who` names the entry in the message
 int check_stats_args(const char* who, const StatsArgs& a, int B, const int32_t* kind, bool with_kind,
                      size_t workspace_bytes) {
   GDM_REQUIRE(a.adj && a.loc && a.scale && a.queue_cap && a.seed && a.number_of_customers && a.mt_key && a.mt_pos &&
@@ -257,5 +279,30 @@ extern "C" int gdm_des_stats_batch_dist(const double* adj, int B, int dim, const
                      queue_area, arrival_time, clock, end_time, total_customers, events, n_records, stop_reason,
                      queue_time, (unsigned char*)workspace, kind);
   GDM_LAUNCH_OK("gdm_des_stats_batch_dist");
+  return GDM_OK;
+}
+
+extern "C" int gdm_des_stats_batch_net(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                       const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
+                                       const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
+                                       uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
+                                       int64_t* served, int64_t* reneges, int64_t* generated, int32_t* max_queue,
+                                       double* time_in_service, double* time_in_queue, double* queue_area,
+                                       double* arrival_time, double* clock, double* end_time,
+                                       int64_t* total_customers, int64_t* events, int64_t* n_records,
+                                       int32_t* stop_reason, double* queue_time, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  const StatsArgs a{adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, mt_key,
+                    mt_pos, has_gauss, cached_gauss, served, reneges, generated, max_queue, time_in_service,
+                    time_in_queue, queue_area, arrival_time, clock, end_time, total_customers, events, n_records,
+                    stop_reason, queue_time, (unsigned char*)workspace};
+  const int rc = check_stats_args("gdm_des_stats_batch_net", a, B, kind, true, workspace_bytes);
+  if (rc != GDM_OK) return rc;
+  hipLaunchKernelGGL(des_stats_net_kernel, dim3(B), dim3(GDM_WAVE), des_wave::lds_dyn_bytes(dim), (hipStream_t)stream,
+                     adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,
+                     has_gauss, cached_gauss, served, reneges, generated, max_queue, time_in_service, time_in_queue,
+                     queue_area, arrival_time, clock, end_time, total_customers, events, n_records, stop_reason,
+                     queue_time, (unsigned char*)workspace, kind);
+  GDM_LAUNCH_OK("gdm_des_stats_batch_net");
   return GDM_OK;
 }

@@ -46,6 +46,22 @@ struct Lds {
   int ok;
 };
 
+// the kinds and the node state of one sample for the kernels over des::AnyNode (2 KB), and their staging by every lane
+// of the wave: the kinds of sample b, no delayed departure, no departure scheduled yet.  Before the prologue, whose
+// first barrier orders it before any read.
+struct NetLds {
+  double next_departure[kMaxDim];
+  int32_t kind[kMaxDim], delayed[kMaxDim];
+};
+__device__ inline void stage_net(des::AnyNode& d, NetLds& n, const int32_t* __restrict__ kind, int dim, int b,
+                                 int lane) {
+  d.kind = n.kind;
+  d.delayed = n.delayed;
+  d.next_departure = n.next_departure;
+  for (int i = lane; i < dim; i += GDM_WAVE) n.kind[i] = kind[(int64_t)b * dim + i];
+  d.reset(dim, lane, GDM_WAVE);
+}
+
 // Every lane of the wave: binds the simulator's storage (dyn: the dynamic LDS, lds_dyn_bytes(dim); ws: the sample's
 // workspace), stages sample b and leaves the node generators seeded.  Returns whether the spec passed the checks of
 // the batch entries (uniform over the wave); a refused sample runs nothing.  s.out / s.out_cap / s.max_records /

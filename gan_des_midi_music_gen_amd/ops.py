@@ -1065,8 +1065,9 @@ def des_batch_workspace_bytes(b, dim, max_queue_cap):
 
 
 def _des_run_batch(who, kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, max_queue_cap,
-                   max_events, max_records, workspace_tensor):
-    """``des_run_batch`` (kind None: gdm_des_run_batch) and ``des_run_batch_dist`` (gdm_des_run_batch_dist)."""
+                   max_events, max_records, workspace_tensor, entry=None):
+    """``des_run_batch`` (kind None: gdm_des_run_batch), ``des_run_batch_dist`` (gdm_des_run_batch_dist) and
+    ``des_run_batch_net`` (``entry``: gdm_des_run_batch_net)."""
     _need_gpu(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss,
               *(() if kind is None else (kind,)))
     if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
@@ -1094,7 +1095,7 @@ def _des_run_batch(who, kind, adj, loc, scale, queue_cap, seed, customers, mt_ke
     stop = torch.empty(b, dtype=torch.int32, device=dev)
     need = des_batch_workspace_bytes(b, dim, max_queue_cap)
     ws = workspace(need, dev) if workspace_tensor is None else workspace_tensor
-    _call("gdm_des_run_batch" if kind is None else "gdm_des_run_batch_dist", _p(adj), b, dim, _p(loc), _p(scale),
+    _call(entry or ("gdm_des_run_batch" if kind is None else "gdm_des_run_batch_dist"), _p(adj), b, dim, _p(loc), _p(scale),
           *(() if kind is None else (_p(kind),)), _p(queue_cap), _p(seed), _p(customers),
           int(max_queue_cap), int(max_events), max_records, _p(mt_key), _p(mt_pos), _p(has_gauss), _p(gauss), _p(value),
           _p(event_id), _p(node), _p(rkind), n, _p(rec_ptr), _p(n_records), _p(stop), _p(ws), ws.numel(), _stream())
@@ -1138,8 +1139,9 @@ def des_stats_workspace_bytes(b, dim, max_queue_cap):
 
 
 def _des_run_stats(who, kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, max_queue_cap,
-                   max_events, histogram, workspace_tensor):
-    """``des_run_stats`` (kind None: gdm_des_stats_batch) and ``des_run_stats_dist`` (gdm_des_stats_batch_dist)."""
+                   max_events, histogram, workspace_tensor, entry=None):
+    """``des_run_stats`` (kind None: gdm_des_stats_batch), ``des_run_stats_dist`` (gdm_des_stats_batch_dist) and
+    ``des_run_stats_net`` (``entry``: gdm_des_stats_batch_net)."""
     _need_gpu(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss,
               *(() if kind is None else (kind,)))
     if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
@@ -1160,7 +1162,7 @@ def _des_run_stats(who, kind, adj, loc, scale, queue_cap, seed, customers, mt_ke
                          else None)
     need = des_stats_workspace_bytes(b, dim, max_queue_cap)
     ws = workspace(need, dev) if workspace_tensor is None else workspace_tensor
-    _call("gdm_des_stats_batch" if kind is None else "gdm_des_stats_batch_dist", _p(adj), b, dim, _p(loc), _p(scale),
+    _call(entry or ("gdm_des_stats_batch" if kind is None else "gdm_des_stats_batch_dist"), _p(adj), b, dim, _p(loc), _p(scale),
           *(() if kind is None else (_p(kind),)), _p(queue_cap), _p(seed), _p(customers),
           int(max_queue_cap), int(max_events), _p(mt_key), _p(mt_pos), _p(has_gauss), _p(gauss),
           *(_p(out[name]) for name, _dt in DES_STATS_NODE_FIELDS + DES_STATS_SAMPLE_FIELDS), _p(out["queue_time"]),
@@ -1188,6 +1190,29 @@ def des_run_stats_dist(adj, loc, scale, kind, queue_cap, seed, customers, mt_key
     DES_STOP_ERROR."""
     return _des_run_stats("des_run_stats_dist", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
                           has_gauss, gauss, max_queue_cap, max_events, histogram, workspace_tensor)
+
+
+DES_DIST_QUEUE, DES_DIST_BRANCH = 3, 4                                   # GDM_DES_DIST_*: nodes without a distribution
+
+
+def des_run_stats_net(adj, loc, scale, kind, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *,
+                      max_queue_cap, max_events=200000, histogram=False, workspace_tensor=None):
+    """``des_run_stats_dist`` for nets with the reference's 'queue' and 'branch' nodes (``kind`` may be DES_DIST_QUEUE
+    or DES_DIST_BRANCH; ``loc`` and ``scale`` are not read there): ``gdm_des_stats_batch_net``, one launch.  A kind
+    outside 0..4 ends that sample with DES_STOP_ERROR.  The same workspace as ``des_run_stats``."""
+    return _des_run_stats("des_run_stats_net", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
+                          has_gauss, gauss, max_queue_cap, max_events, histogram, workspace_tensor,
+                          entry="gdm_des_stats_batch_net")
+
+
+def des_run_batch_net(adj, loc, scale, kind, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *,
+                      max_queue_cap, max_events=200000, max_records=5001, workspace_tensor=None):
+    """``des_run_batch_dist`` for nets with 'queue' and 'branch' nodes (``des_run_stats_net``'s kinds):
+    ``gdm_des_run_batch_net``, one launch + the pack step.  A kind outside 0..4 ends that sample with DES_STOP_ERROR; a
+    sample that ends so keeps its generator state.  The same workspace as ``des_run_batch``."""
+    return _des_run_batch("des_run_batch_net", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
+                          has_gauss, gauss, max_queue_cap, max_events, max_records, workspace_tensor,
+                          entry="gdm_des_run_batch_net")
 
 
 def des_pack(n_records, rec_ptr, value, event_id, node, kind, max_records):

@@ -36,8 +36,9 @@ def mm1k(lam, mu, queue_cap):
 
 def mmck_blocking(lam, mu, c, queue_cap):
     """The blocking probability of M/M/c/N, N = c + queue_cap: p[N] with p[n] ~ a**n / n! for n <= c and
-    a**n / (c! c**(n - c)) beyond, a = lam / mu.  c = 1 is ``mm1k(...)["blocking"]``.  (The simulator has no
-    shortest-queue routing, so c > 1 has no simulated counterpart here.)"""
+    a**n / (c! c**(n - c)) beyond, a = lam / mu.  c = 1 is ``mm1k(...)["blocking"]``.  The simulated counterpart is a
+    ``['queue']`` node in front of c servers (``simulation_v3.mmck_spec`` / ``mmck_sweep``), which holds one customer
+    even with capacity 0: compare it with ``queue_cap = max(queue_list, 1)``; ``mmck`` below is the full law."""
     lam, mu, c, queue_cap = float(lam), float(mu), int(c), int(queue_cap)
     if not (lam > 0 and mu > 0 and c >= 1 and queue_cap >= 0):
         raise ValueError("mmck_blocking: lam > 0, mu > 0, c >= 1 and queue_cap >= 0 are required")
@@ -45,6 +46,31 @@ def mmck_blocking(lam, mu, c, queue_cap):
     w = [a ** n / math.factorial(n) if n <= c else a ** n / (math.factorial(c) * float(c) ** (n - c))
          for n in range(big_n + 1)]
     return w[big_n] / math.fsum(w)
+
+
+def mmck(lam, mu, c, queue_cap):
+    """M/M/c/N with N = c + queue_cap -> the dict of ``mm1k``:
+      p           (N + 1) stationary probabilities, p[n] ~ a**n / n! for n <= c and a**n / (c! c**(n - c)) beyond
+      blocking    p[N]
+      utilisation PER SERVER: the mean number of busy servers, sum min(n, c) p[n], over c
+      L, LQ       mean number in the station / waiting: sum n p[n], sum (n - c) p[n] over n > c
+      W, WQ       Little's law with the accepted rate lam (1 - p[N])
+      queue_length_probabilities  (queue_cap + 1): the law of the number waiting, (p[0] + .. + p[c], p[c + 1], .., p[N])
+    c = 1 is ``mm1k`` (the same weights; the utilisation is summed here and 1 - p[0] there)."""
+    lam, mu, c, queue_cap = float(lam), float(mu), int(c), int(queue_cap)
+    if not (lam > 0 and mu > 0 and c >= 1 and queue_cap >= 0):
+        raise ValueError("mmck: lam > 0, mu > 0, c >= 1 and queue_cap >= 0 are required")
+    a, big_n = lam / mu, c + queue_cap
+    n = np.arange(big_n + 1, dtype=np.float64)
+    w = np.array([a ** i / math.factorial(i) if i <= c else a ** i / (math.factorial(c) * float(c) ** (i - c))
+                  for i in range(big_n + 1)], dtype=np.float64)
+    p = w / w.sum()
+    accepted = lam * (1.0 - p[big_n])
+    big_l = float((n * p).sum())
+    lq = float(((n[c:] - c) * p[c:]).sum())
+    return {"p": p, "blocking": float(p[big_n]), "utilisation": float((np.minimum(n, c) * p).sum() / c), "L": big_l,
+            "LQ": lq, "W": big_l / accepted, "WQ": lq / accepted,
+            "queue_length_probabilities": np.concatenate([[p[:c + 1].sum()], p[c + 1:]])}
 
 
 def mean_of(distribution):

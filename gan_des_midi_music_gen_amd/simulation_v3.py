@@ -18,7 +18,8 @@ Differences, on purpose:
     accepted and ignored);
   * only what the bridges construct is supported: 'normal' distributions, ``logging_mode='Music'``, probability routing
     (no 'queue' / 'branch' nodes, no animation, no metric history) -- anything else raises NotImplementedError (the
-    log-free statistics run and ``run_batch_dist`` below also take 'exponential' and 'uniform' nodes);
+    log-free statistics run and ``run_batch_dist`` below also take 'exponential' and 'uniform' nodes, and 'queue' and
+    'branch' nodes);
   * the log records are also kept as arrays (``sim.music_log``), so a caller need not go through the log file;
   * where the reference's run ends in an exception, ``Sim.run`` raises ValueError with the core's message, and a sample
     of ``run_batch`` / ``run_batch_host`` ends with stop reason 3 ("error") and an empty log, its neighbours untouched
@@ -59,6 +60,30 @@ Differences, on purpose:
     record for record and bit for bit (tests/golden/des_log_dist.npz).  Unlike ``run_batch`` a sample that stops with
     reason 3 keeps the generator state it came with, as in the statistics run.  ``write_music_log`` writes any such
     log as the reference's ``logs/simulation.log``; ``simlog_to_vid`` turns it into queue tracks and an animation.
+
+  * the reference's two node kinds WITHOUT a distribution (``Server.__init__``, 193-197) are taken by ``run_stats``,
+    ``replicate``, ``run_batch_dist`` and ``mmck_sweep`` -- NODE_KINDS = DIST_KINDS + ('queue', 'branch'); ``Sim``,
+    ``run_batch``, ``spec_arrays``, ``dist_arrays`` and the bridges keep refusing them: ``['queue']``, a waiting room in
+    front of several servers (its departure takes the first idle child that is a server, and waits -- is scheduled
+    again at the earliest next departure among its children, 656-697 -- while there is none), and ``['branch']``, a
+    zero-time router.  Both are servers with their own FIFO and ``queue_list`` capacity, draw nothing, and write a
+    ``processing`` record of value 0.  A queue node's delayed departure counts as a waiting customer in the admission
+    test and in the time at queue length (557, 477), so a queue node with ``queue_list`` 0 still holds one customer
+    and an M/M/c station built with ``mmck_spec`` is M/M/c/N with N = c + max(queue_cap, 1).  ``net_arrays`` parses
+    such specs; ``run_stats_host`` / ``run_stats_device`` / ``run_batch_host`` / ``run_batch_device`` take
+    ``net=True`` with ``kind=`` (``gdm_des_stats_batch_net[_host]``, ``gdm_des_run_batch_net[_host]``; never chosen
+    from the values in ``kind``: the entries without it refuse kind 3 as ever), the spec-level functions go there only
+    when some node is 'queue' or 'branch'.  With ``math=0`` log and statistics are the reference's
+    (tests/golden/des_net.npz); ``mmck_sweep`` puts simulated M/M/c/N beside ``queueing_theory.mmck``.  Two more rows
+    of the table above, both stop 3 with the generator state kept:
+
+        a source is a 'queue' or 'branch' node         ValueError ("Distribution not supported")   stop 3
+        a queue node must wait and every child is a     the departure is scheduled at +inf: the     stop 3
+        source (none ever schedules a departure)        run is not defined by its inputs alone
+
+  * shortest-queue routing is not built: ``FlowBranchOperator.shortest_queue`` (49-52) is set from the probabilities
+    AFTER they were normalised, so it can be true only for a node without children, which the table above covers;
+    ``use_next_available_server`` (731-736) is read on that path only.  ``Sim.run`` accepts and ignores the argument.
 
 ``run_batch`` / ``run_batch_host`` simulate B specs of one size at once, every sample FROM ITS OWN snapshot of numpy's
 global stream (``gdm_des_run_batch`` on a HIP device: one wave per sample, csrc/des_batch.hip; ``gdm_des_run_batch_host``
@@ -160,12 +185,16 @@ class Sim:
         return self.music_log
 
 
-def write_music_log(records, path):
+def write_music_log(records, path, kind=None):
     """EVENT_DTYPE records (``Sim.music_log``, ``sample_log`` of a BatchLog) -> the 'Music' log file the reference's
-    ``logging.info`` writes (``logs/simulation.log``): ``INFO:root:<repr of the value> - <id> - <node> - <kind>``."""
+    ``logging.info`` writes (``logs/simulation.log``): ``INFO:root:<repr of the value> - <id> - <node> - <kind>``.
+    ``kind``: the net's (dim) row of NODE_KINDS indices; the ``processing`` record of a 'queue' or 'branch' node is then
+    written as the reference writes it, the int ``0`` (ScheduleDeparture's ``service_time = 0``), not ``0.0``."""
+    timeless = None if kind is None else np.asarray(kind).reshape(-1) >= NODE_KINDS.index("queue")
     with open(path, "w") as f:
-        for v, eid, node, kind in records:
-            f.write(f"INFO:root:{float(v)!r} - {int(eid)} - {int(node)} - {KIND_NAMES[kind]}\n")
+        for v, eid, node, k in records:
+            text = "0" if timeless is not None and k == PROCESSING and timeless[int(node)] else repr(float(v))
+            f.write(f"INFO:root:{text} - {int(eid)} - {int(node)} - {KIND_NAMES[k]}\n")
 
 
 def run_spec(spec, max_events=200000, generate_log=False, log_path="logs/"):
@@ -220,11 +249,14 @@ def sample_log(log, b):
 
 
 def run_batch_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, math=1, max_events=200000,
-                   max_records=5001, max_queue_cap=None, kind=None):
+                   max_records=5001, max_queue_cap=None, kind=None, net=False):
     """``gdm_des_run_batch_host`` on numpy arrays: adj (B,dim,dim), loc, scale, queue_cap (B,dim), seed, customers (B).
     math 0 = libm (the reference's bits), 1 = portable (the device's bits).  max_records 0 = no cap.  -> BatchLog of
     numpy arrays; the record arrays are cut to rec_ptr[B].  ``kind`` (B,dim), the index into DIST_KINDS per node:
-    ``gdm_des_run_batch_dist_host``; None: every node is normal."""
+    ``gdm_des_run_batch_dist_host``; None: every node is normal.  ``net=True`` (with ``kind``, the index into NODE_KINDS):
+    ``gdm_des_run_batch_net_host``, which also takes 'queue' and 'branch' nodes."""
+    if net and kind is None:
+        raise ValueError("run_batch_host: net=True needs kind")
     lib = _lib.load()
     adj = np.ascontiguousarray(adj, dtype=np.float64)
     b, dim = adj.shape[0], adj.shape[1]
@@ -242,7 +274,7 @@ def run_batch_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, 
         name, kinds = "gdm_des_run_batch_host", ()
     else:
         kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(b, dim)
-        name, kinds = "gdm_des_run_batch_dist_host", (kind.ctypes.data,)
+        name, kinds = "gdm_des_run_batch_net_host" if net else "gdm_des_run_batch_dist_host", (kind.ctypes.data,)
     entry = getattr(lib, name)
     per = 4 * max_events + 4 * dim + 64                    # at most four records per processed event
     cap = b * (min(per, max_records) if max_records > 0 else per)
@@ -287,22 +319,26 @@ def spec_arrays(specs):
 DIST_KINDS = ("normal", "exponential", "uniform")     # GDM_DES_DIST_*: the index is the kind
 
 
-def dist_row(distributions, who="dist_arrays"):
+NODE_KINDS = DIST_KINDS + ("queue", "branch")         # the entries with node kinds (_net) take these as well
+
+
+def dist_row(distributions, who="dist_arrays", kinds=DIST_KINDS):
     """One spec's ``distributions`` -> (kind, loc, scale) lists: ``['normal', loc, s]`` and ``['uniform', loc, s]`` as
     written, ``['exponential', s]`` as loc 0, scale s (scipy's ``expon(scale=s)``).  NotImplementedError names any
-    other kind."""
+    other kind.  ``kinds=NODE_KINDS``: ``['queue']`` and ``['branch']`` too, as loc 0, scale 0."""
     kind, loc, scale = [], [], []
     for d in distributions:
-        if d[0] not in DIST_KINDS:
+        if d[0] not in kinds:
             raise NotImplementedError(f"{who}: distribution {d[0]!r} (the statistics entries implement "
-                                      f"{', '.join(DIST_KINDS)})")
-        kind.append(DIST_KINDS.index(d[0]))
-        loc.append(0.0 if d[0] == "exponential" else float(d[1]))
-        scale.append(float(d[1]) if d[0] == "exponential" else float(d[2]))
+                                      f"{', '.join(kinds)})")
+        kind.append(kinds.index(d[0]))
+        timeless = d[0] in ("queue", "branch")
+        loc.append(0.0 if d[0] == "exponential" or timeless else float(d[1]))
+        scale.append(0.0 if timeless else float(d[1]) if d[0] == "exponential" else float(d[2]))
     return kind, loc, scale
 
 
-def dist_arrays(specs):
+def dist_arrays(specs, who="run_stats", kinds=DIST_KINDS):
     """``spec_arrays`` for specs whose nodes may be any of DIST_KINDS -> (adj, kind, loc, scale, queue_cap, seed,
     customers) numpy arrays with a leading B; kind (B,dim) int32, the index into DIST_KINDS."""
     if len(specs) == 0:
@@ -314,7 +350,7 @@ def dist_arrays(specs):
             raise ValueError("run_stats: every spec of a batch must have the same number of nodes")
         if np.asarray(sp.seeds).size != 1:
             raise ValueError("run_stats: one seed (one run) per spec")
-        rows.append(dist_row(sp.distributions, "run_stats"))
+        rows.append(dist_row(sp.distributions, who, kinds))
     adj = np.ascontiguousarray([np.asarray(sp.sim_matrix, dtype=np.float64) for sp in specs])
     kind = np.ascontiguousarray([r[0] for r in rows], dtype=np.int32)
     loc = np.ascontiguousarray([r[1] for r in rows], dtype=np.float64)
@@ -325,11 +361,20 @@ def dist_arrays(specs):
     return adj, kind, loc, scale, qcap, seed, customers
 
 
+def net_arrays(specs, who="net_arrays"):
+    """``dist_arrays`` for specs whose nodes may be any of NODE_KINDS: ``['queue']`` and ``['branch']`` get kind 3 and 4,
+    loc 0 and scale 0 (neither is read).  For the entries taken with ``net=True``."""
+    return dist_arrays(specs, who, NODE_KINDS)
+
+
 def run_batch_device(adj, loc, scale, queue_cap, seed, customers, states=None, *, device, max_events=200000,
-                     max_records=5001, max_queue_cap=None, workspace_tensor=None, kind=None):
+                     max_records=5001, max_queue_cap=None, workspace_tensor=None, kind=None, net=False):
     """``gdm_des_run_batch``: the arrays of ``run_batch_host`` (numpy, or device tensors that stay where they are --
     ``adj`` straight from ``ops.des_routing``) -> BatchLog of device tensors.  Nothing is read back.  ``kind`` as in
-    ``run_batch_host``: ``gdm_des_run_batch_dist``, the kernel that draws normal, exponential and uniform nodes."""
+    ``run_batch_host``: ``gdm_des_run_batch_dist``, the kernel that draws normal, exponential and uniform nodes;
+    ``net=True``: ``gdm_des_run_batch_net``, the kernel that also takes 'queue' and 'branch' nodes."""
+    if net and kind is None:
+        raise ValueError("run_batch_device: net=True needs kind")
     import torch
     from . import ops
     dev = torch.device(device)
@@ -358,8 +403,9 @@ def run_batch_device(adj, loc, scale, queue_cap, seed, customers, states=None, *
     if kind is None:
         out = ops.des_run_batch(up(adj, torch.float64), up(loc, torch.float64), up(scale, torch.float64), *tail, **kw)
     else:
-        out = ops.des_run_batch_dist(up(adj, torch.float64), up(loc, torch.float64), up(scale, torch.float64),
-                                     up(kind, torch.int32), *tail, **kw)
+        entry = ops.des_run_batch_net if net else ops.des_run_batch_dist
+        out = entry(up(adj, torch.float64), up(loc, torch.float64), up(scale, torch.float64), up(kind, torch.int32),
+                    *tail, **kw)
     return BatchLog(*out, k, p, h, g)
 
 
@@ -414,9 +460,11 @@ def run_batch_dist(specs, *, device=None, math=1, max_events=200000, max_records
     node is not normal.  ``math`` is the host mirror's (device=None): 0 = libm, the reference's bits, 1 = portable, the
     device's.  The consumers of a BatchLog (``log_to_notes``, ``log_to_rolls``, ``ops.des_log_to_notes_pc``,
     ``simlog_to_vid.log_tracks``) take it as it is; ``write_music_log(sample_log(log, b), path)`` writes sample b as
-    the reference's ``logs/simulation.log``."""
-    adj, kind, *rest = dist_arrays(specs)
-    kw = dict(max_events=max_events, max_records=max_records, kind=kind if kind.any() else None)   # all normal: as ever
+    the reference's ``logs/simulation.log``.  Nodes may also be 'queue' or 'branch' (NODE_KINDS): then, and only then,
+    the entries ``gdm_des_run_batch_net[_host]`` run; pass the spec's ``kind`` row to ``write_music_log``."""
+    adj, kind, *rest = net_arrays(specs, "run_stats")
+    kw = dict(max_events=max_events, max_records=max_records, kind=kind if kind.any() else None,   # all normal: as ever
+              net=bool((kind >= len(DIST_KINDS)).any()))
     if device is None:
         return run_batch_host(adj, *rest, states, math=math, **kw)
     return run_batch_device(adj, *rest, states, device=device, **kw)
@@ -439,10 +487,13 @@ _STATS_DTYPES = dict(served=np.int64, reneges=np.int64, generated=np.int64, max_
 
 
 def run_stats_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, math=1, max_events=200000,
-                   max_queue_cap=None, histogram=False, kind=None):
+                   max_queue_cap=None, histogram=False, kind=None, net=False):
     """``gdm_des_stats_batch_host`` on the numpy arrays of ``run_batch_host``: the same runs, no records -> BatchStats
     of numpy arrays.  math 0 = libm (the reference's bits), 1 = portable (the device's bits).  ``kind`` (B,dim), the
-    index into DIST_KINDS per node: ``gdm_des_stats_batch_dist_host``; None: every node is normal."""
+    index into DIST_KINDS per node: ``gdm_des_stats_batch_dist_host``; None: every node is normal.  ``net=True`` (with
+    ``kind``, the index into NODE_KINDS): ``gdm_des_stats_batch_net_host``, which also takes 'queue' and 'branch' nodes."""
+    if net and kind is None:
+        raise ValueError("run_stats_host: net=True needs kind")
     lib = _lib.load()
     adj = np.ascontiguousarray(adj, dtype=np.float64)
     b, dim = adj.shape[0], adj.shape[1]
@@ -467,19 +518,22 @@ def run_stats_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, 
         _lib.check(rc, "gdm_des_stats_batch_host")
     else:
         kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(b, dim)
-        rc = lib.gdm_des_stats_batch_dist_host(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data,
-                                               kind.ctypes.data, *tail)
-        _lib.check(rc, "gdm_des_stats_batch_dist_host")
+        name = "gdm_des_stats_batch_net_host" if net else "gdm_des_stats_batch_dist_host"
+        rc = getattr(lib, name)(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data, kind.ctypes.data, *tail)
+        _lib.check(rc, name)
     is_source = np.diagonal(adj, axis1=1, axis2=2) > 0
     return BatchStats(*(out[n] for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS), hist, is_source, k, p, h, g)
 
 
 def run_stats_device(adj, loc, scale, queue_cap, seed, customers, states=None, *, device, max_events=200000,
-                     max_queue_cap=None, histogram=False, workspace_tensor=None, kind=None):
+                     max_queue_cap=None, histogram=False, workspace_tensor=None, kind=None, net=False):
     """``gdm_des_stats_batch``: the arrays of ``run_batch_device`` (numpy, or device tensors that stay where they are --
     ``adj`` straight from ``ops.des_routing``) -> BatchStats of device tensors, bit-identical to
     ``run_stats_host(math=1)``.  Nothing is read back.  ``kind`` as in ``run_stats_host``: ``gdm_des_stats_batch_dist``,
-    the kernel that draws normal, exponential and uniform nodes."""
+    the kernel that draws normal, exponential and uniform nodes; ``net=True``: ``gdm_des_stats_batch_net``, the kernel
+    that also takes 'queue' and 'branch' nodes."""
+    if net and kind is None:
+        raise ValueError("run_stats_device: net=True needs kind")
     import torch
     from . import ops
     dev = torch.device(device)
@@ -506,8 +560,8 @@ def run_stats_device(adj, loc, scale, queue_cap, seed, customers, states=None, *
     if kind is None:
         out = ops.des_run_stats(adj, up(loc, torch.float64), up(scale, torch.float64), *tail, **kw)
     else:
-        out = ops.des_run_stats_dist(adj, up(loc, torch.float64), up(scale, torch.float64), up(kind, torch.int32), *tail,
-                                     **kw)
+        entry = ops.des_run_stats_net if net else ops.des_run_stats_dist
+        out = entry(adj, up(loc, torch.float64), up(scale, torch.float64), up(kind, torch.int32), *tail, **kw)
     is_source = torch.diagonal(adj, dim1=1, dim2=2) > 0
     return BatchStats(*(out[n] for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS), out["queue_time"], is_source, k, p, h,
                       g)
@@ -516,9 +570,11 @@ def run_stats_device(adj, loc, scale, queue_cap, seed, customers, states=None, *
 def run_stats(specs, *, device=None, max_events=200000, states=None, histogram=False):
     """``run_batch`` without a log: B ``DesSpec`` of one size, each from its own generator state -> BatchStats (numpy
     arrays from the host mirror with portable math for device=None, device tensors with the same bits otherwise).
-    Nodes may be any of DIST_KINDS (``dist_arrays``); the entries with kinds run only when some node is not normal."""
-    adj, kind, *rest = dist_arrays(specs)
-    kw = dict(max_events=max_events, histogram=histogram, kind=kind if kind.any() else None)   # all normal: as ever
+    Nodes may be any of NODE_KINDS (``net_arrays``); the entries with kinds run only when some node is not normal, those
+    with node kinds (``gdm_des_stats_batch_net[_host]``) only when some node is 'queue' or 'branch'."""
+    adj, kind, *rest = net_arrays(specs, "run_stats")
+    kw = dict(max_events=max_events, histogram=histogram, kind=kind if kind.any() else None,   # all normal: as ever
+              net=bool((kind >= len(DIST_KINDS)).any()))
     if device is None:
         return run_stats_host(adj, *rest, states, math=1, **kw)
     return run_stats_device(adj, *rest, states, device=device, **kw)
@@ -593,14 +649,15 @@ def replication_states(seeds):
 def replicate(spec, seeds, *, device=None, max_events=200000, states=None):
     """R = len(seeds) seeded runs of ONE net (a ``DesSpec``; its own ``seeds`` are not used) in one batch, then
     ``metrics`` and their mean / std (ddof 1) / sem / n over the replications -> Replications.  Nodes may be any of
-    DIST_KINDS.  ``states``: the R global
+    NODE_KINDS.  ``states``: the R global
     generator states (default ``replication_states(seeds)``).  No interval is formed: sem and n are what one needs."""
     from . import ops
     seeds = [int(s) for s in np.asarray(seeds).reshape(-1)]
     r = len(seeds)
     if r == 0:
         raise ValueError("replicate: no seeds")
-    kinds, locs, scales = dist_row(spec.distributions, "replicate")
+    kinds, locs, scales = dist_row(spec.distributions, "replicate", NODE_KINDS)
+    net = any(k >= len(DIST_KINDS) for k in kinds)
     one = np.asarray(spec.sim_matrix, dtype=np.float64)
     dim = one.shape[0]
     adj = np.ascontiguousarray(np.broadcast_to(one, (r, dim, dim)))
@@ -613,9 +670,9 @@ def replicate(spec, seeds, *, device=None, max_events=200000, states=None):
         states = replication_states(seeds)
     arrays = (adj, loc, scale, qcap, np.asarray(seeds, dtype=np.int64), customers, states)
     if device is None:
-        stats = run_stats_host(*arrays, math=1, max_events=max_events, kind=kind)
+        stats = run_stats_host(*arrays, math=1, max_events=max_events, kind=kind, net=net)
     else:
-        stats = run_stats_device(*arrays, device=device, max_events=max_events, kind=kind)
+        stats = run_stats_device(*arrays, device=device, max_events=max_events, kind=kind, net=net)
     m = metrics(stats)
     stop = np.asarray(stats.stop_reason.cpu() if hasattr(stats.stop_reason, "cpu") else stats.stop_reason)
     valid = (stop != ops.DES_STOP_ERROR) & (stop != ops.DES_STOP_BUDGET)
@@ -700,6 +757,13 @@ def mm1k_sweep(lams, mus, queue_caps, seeds, *, customers, device=None, max_even
         theory["blocked_fraction"][i], theory["utilisation"][i] = t["blocking"], t["utilisation"]
         theory["avg_queue_length"][i], theory["avg_queue_time"][i] = t["LQ"], t["WQ"]
         theory["queue_length_probabilities"][i, :caps[i] + 1] = t["queue_length_probabilities"]
+    mean, sem, n, z = _sweep_summary(values, valid, theory)
+    return Mm1kSweep(lams, mus, caps, np.asarray(seeds, dtype=np.int64), stats, values, mean, sem, n, theory, z)
+
+
+def _sweep_summary(values, valid, theory):
+    """Per name: mean, sem (std with ddof 1 / sqrt(n)) and n of ``values[name]`` (C, R[, K + 1]) over the runs of
+    ``valid`` (C, R) that have a value, and z = (mean - theory) / sem (0 where the difference is 0)."""
     mean, sem, n, z = {}, {}, {}, {}
     for name, v in values.items():
         ok = valid if v.ndim == 2 else valid[:, :, None]
@@ -711,7 +775,104 @@ def mm1k_sweep(lams, mus, queue_caps, seeds, *, customers, device=None, max_even
             sem[name] = np.where(n[name] > 1, np.sqrt(dev2 / (n[name] - 1)) / np.sqrt(n[name]), np.nan)
             d = mean[name] - theory[name]
             z[name] = np.where(d == 0, 0.0, d / sem[name])
-    return Mm1kSweep(lams, mus, caps, np.asarray(seeds, dtype=np.int64), stats, values, mean, sem, n, theory, z)
+    return mean, sem, n, z
+
+
+# ---- simulation beside theory: M/M/c/N, a queue node in front of c servers -----------------------------------------------
+MmckSweep = collections.namedtuple("MmckSweep", "c lam mu queue_cap seeds stats values mean sem n theory z")
+MmckSweep.__doc__ = """``mmck_sweep``'s result: Mm1kSweep's fields (C configurations x R seeds, run c * R + r) with ``c`` (C),
+the number of servers, in front; ``theory`` is ``queueing_theory.mmck(lam, mu, c, max(queue_cap, 1))`` and K =
+max(max(queue_cap), 1).  Nets of different c have different sizes, so ``stats`` is a host BatchStats (numpy arrays,
+whatever the device) with THREE node rows per run: the source, the queue node, and the c servers taken together (sums;
+the largest ``max_queue``)."""
+
+
+def mmck_spec(c, lam, mu, queue_cap, customers, seed=0):
+    """The multi-server station as the reference builds it, as a ``DesSpec`` of c + 2 nodes: node 0 an exponential source
+    (mean 1 / lam), node 1 a ``['queue']`` node with ``queue_cap`` places, nodes 2 .. c + 1 exponential servers (mean
+    1 / mu) without a queue of their own (capacity 0), each a sink.  The queue node hands a customer to the first idle
+    server and holds the next one back (a delayed departure) while all are busy: M/M/c/N, N = c + max(queue_cap, 1)."""
+    from .matrix_sim_process import DesSpec
+    c = int(c)
+    if c < 1:
+        raise ValueError("mmck_spec: c >= 1")
+    dim = c + 2
+    adj = np.zeros((dim, dim))
+    adj[0, 0] = adj[0, 1] = 1.0
+    adj[1, 2:] = 1.0
+    dist = [["exponential", 1.0 / float(lam)], ["queue"]] + [["exponential", 1.0 / float(mu)] for _ in range(c)]
+    return DesSpec(adj, dist, [0, int(queue_cap)] + [0] * c, np.array([int(seed)]), int(customers), 1.0, np.zeros(dim),
+                   np.zeros(dim))
+
+
+def mmck_sweep(cs, lams, mus, queue_caps, seeds, *, customers, device=None, max_events=None, math=1):
+    """Simulated M/M/c/N beside ``queueing_theory.mmck``, shaped like ``mm1k_sweep``: configuration i = (cs[i], lams[i],
+    mus[i], queue_caps[i]) on the net of ``mmck_spec``, every configuration with every seed from the global stream
+    ``replication_states(seeds)[r]``.  Configurations of one c are one batch (one launch on a device: a batch has one
+    dim); the result is in the order given.  Compared (SWEEP_NAMES), with N = c + max(queue_cap, 1):
+      blocked_fraction            reneges / (served + reneges) at the queue node                          ~ p[N]
+      utilisation                 the mean over the c servers of time_in_service / clock                  ~ sum min(n, c) p[n] / c
+      avg_queue_length            queue_area / clock at the queue node (queue + delayed departure)        ~ LQ
+      avg_queue_time              time_in_queue / served at the queue node (waits and delays)             ~ WQ
+      queue_length_probabilities  queue_time / clock at the queue node                                    ~ (p[0] + .. + p[c], p[c + 1], ..)
+    -> MmckSweep.  max_events None: 16 * customers + 64 (an arrival and two departures per customer, and a re-pop for
+    every delayed departure that loses its tie)."""
+    from . import ops, queueing_theory as qt
+    cs = np.asarray(cs, dtype=np.int64).reshape(-1)
+    lams, mus = np.asarray(lams, dtype=np.float64).reshape(-1), np.asarray(mus, dtype=np.float64).reshape(-1)
+    caps = np.asarray(queue_caps, dtype=np.int64).reshape(-1)
+    seeds = [int(s) for s in np.asarray(seeds).reshape(-1)]
+    c, r = len(lams), len(seeds)
+    if c == 0 or r == 0 or len(mus) != c or len(caps) != c or len(cs) != c:
+        raise ValueError("mmck_sweep: cs, lams, mus and queue_caps must have one entry per configuration, and seeds be "
+                         "given")
+    if (caps < 0).any() or (cs < 1).any():
+        raise ValueError("mmck_sweep: c >= 1 and queue_cap >= 0")
+    if max_events is None:
+        max_events = 16 * int(customers) + 64
+    k = max(int(caps.max()), 1)
+    rows = {name: [None] * c for name in ("blocked", "util", "lq", "wq", "prob", "valid") + BatchStats._fields}
+    for servers in sorted(set(cs.tolist())):
+        idx = [i for i in range(c) if cs[i] == servers]
+        specs = [mmck_spec(servers, lams[i], mus[i], caps[i], customers, s) for i in idx for s in seeds]
+        adj, kind, *rest = net_arrays(specs, "mmck_sweep")
+        kw = dict(max_events=max_events, histogram=True, kind=kind, net=True, max_queue_cap=k)
+        if device is None:
+            stats = run_stats_host(adj, *rest, replication_states(seeds) * len(idx), math=math, **kw)
+        else:
+            stats = run_stats_device(adj, *rest, replication_states(seeds) * len(idx), device=device, **kw)
+        m = metrics(stats)
+        st = BatchStats(*(None if a is None else np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in stats))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            blocked = st.reneges[:, 1] / (st.served[:, 1] + st.reneges[:, 1]).astype(np.float64)
+        valid = (st.stop_reason != ops.DES_STOP_ERROR) & (st.stop_reason != ops.DES_STOP_BUDGET)
+        for j, i in enumerate(idx):
+            sl = slice(j * r, (j + 1) * r)
+            prob = m["queue_length_probabilities"][sl, 1, :].copy()
+            prob[:, max(caps[i], 1) + 1:] = np.nan               # lengths the configuration cannot have
+            rows["blocked"][i], rows["util"][i] = blocked[sl], m["server_utilizations"][sl, 2:].mean(axis=1)
+            rows["lq"][i], rows["wq"][i] = m["avg_queue_length"][sl, 1], m["avg_queue_time"][sl, 1]
+            rows["prob"][i], rows["valid"][i] = prob, valid[sl]
+            for name in BatchStats._fields:                      # node rows: source, queue node, the servers together
+                a = getattr(st, name)[sl]
+                if name == "mt_key":
+                    a = a.view(np.uint32)                        # (int32 bit patterns from a device)
+                if name in STATS_NODE_FIELDS + ("queue_time", "is_source"):
+                    rest = a[:, 2:].max(axis=1) if name in ("max_queue", "is_source") else a[:, 2:].sum(axis=1)
+                    a = np.stack([a[:, 0], a[:, 1], rest], axis=1)
+                rows[name][i] = a
+    values = {"blocked_fraction": np.stack(rows["blocked"]), "utilisation": np.stack(rows["util"]),
+              "avg_queue_length": np.stack(rows["lq"]), "avg_queue_time": np.stack(rows["wq"]),
+              "queue_length_probabilities": np.stack(rows["prob"])}
+    theory = {n: np.full((c, k + 1) if n == "queue_length_probabilities" else (c,), np.nan) for n in SWEEP_NAMES}
+    for i in range(c):
+        t = qt.mmck(lams[i], mus[i], cs[i], max(caps[i], 1))
+        theory["blocked_fraction"][i], theory["utilisation"][i] = t["blocking"], t["utilisation"]
+        theory["avg_queue_length"][i], theory["avg_queue_time"][i] = t["LQ"], t["WQ"]
+        theory["queue_length_probabilities"][i, :max(caps[i], 1) + 1] = t["queue_length_probabilities"]
+    mean, sem, n, z = _sweep_summary(values, np.stack(rows["valid"]), theory)
+    stats = BatchStats(*(np.concatenate(rows[name]) for name in BatchStats._fields))
+    return MmckSweep(cs, lams, mus, caps, np.asarray(seeds, dtype=np.int64), stats, values, mean, sem, n, theory, z)
 
 
 def math_probe_host(x):

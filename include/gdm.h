@@ -574,6 +574,58 @@ int gdm_des_run_batch_dist(const double* adj, int B, int dim, const double* loc,
                            int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the simulator with the reference's 'queue' and 'branch' NODES (csrc/des_sim.h: des::AnyNode; des_stats_net_kernel,
+ * des_batch_net_kernel) ------------------------------------------------------------------------------------------------
+ * The argument lists, outputs, stop reasons, generator-state contract, workspaces (gdm_des_stats_workspace_bytes,
+ * gdm_des_batch_workspace_bytes) and pack step of the four _dist entries above; `kind` may also be
+ *   GDM_DES_DIST_QUEUE   ['queue']   a waiting room in front of several servers (Server.__init__, simulation_v3.py:196):
+ *                        service time 0 without a draw; its departure takes no routing draw but the first idle child
+ *                        that is a server, and while there is none it is scheduled again at the earliest next departure
+ *                        among the children (ProcessDeparture 656-673, schedule_delayed_departure 679-697)
+ *   GDM_DES_DIST_BRANCH  ['branch']  a router: service time 0 without a draw, routed like any server
+ * loc and scale of such a node are not read.  Each is a server with a FIFO and queue_cap; a queue node's delayed
+ * departure counts as a waiting customer in the admission test and in queue_area / queue_time (not in max_queue), and
+ * adds its delay to time_in_queue.  Every pop of a delayed departure is a processed event and a 'departure' record.
+ * (queue_time has max_queue_cap + 1 columns as ever: queue + delayed departure beyond max_queue_cap, which only tied
+ * arrivals at a full queue node can reach, has no column there and still counts in queue_area.)
+ * With every kind in 0..2 the results are the bytes of the _dist entries.
+ * Refused per sample (GDM_DES_STOP_ERROR), besides what those refuse: a SOURCE of either kind (the reference raises
+ * "Distribution not supported"), and a queue node that must wait while none of its children has ever scheduled a
+ * departure (every child a source: the delayed time is +inf).  A kind outside 0..4: the host entries refuse the call
+ * by message, the device entries stop that sample with GDM_DES_STOP_ERROR.                                           */
+#define GDM_DES_DIST_QUEUE 3
+#define GDM_DES_DIST_BRANCH 4
+int gdm_des_stats_batch_net_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                 const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
+                                 const int64_t* number_of_customers, int max_queue_cap, int math, int64_t max_events,
+                                 uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
+                                 int64_t* served, int64_t* reneges, int64_t* generated, int32_t* max_queue,
+                                 double* time_in_service, double* time_in_queue, double* queue_area,
+                                 double* arrival_time, double* clock, double* end_time, int64_t* total_customers,
+                                 int64_t* events, int64_t* n_records, int32_t* stop_reason, double* queue_time);
+int gdm_des_stats_batch_net(const double* adj, int B, int dim, const double* loc, const double* scale,
+                            const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
+                            const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
+                            uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
+                            int64_t* served, int64_t* reneges, int64_t* generated, int32_t* max_queue,
+                            double* time_in_service, double* time_in_queue, double* queue_area, double* arrival_time,
+                            double* clock, double* end_time, int64_t* total_customers, int64_t* events,
+                            int64_t* n_records, int32_t* stop_reason, double* queue_time, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int gdm_des_run_batch_net_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                               const int32_t* node_kind, const int32_t* queue_cap, const int64_t* seed,
+                               const int64_t* number_of_customers, int max_queue_cap, int math, int64_t max_events,
+                               int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                               double* cached_gauss, double* value, int64_t* event_id, int32_t* node, int32_t* kind,
+                               int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason);
+int gdm_des_run_batch_net(const double* adj, int B, int dim, const double* loc, const double* scale,
+                          const int32_t* node_kind, const int32_t* queue_cap, const int64_t* seed,
+                          const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
+                          int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                          double* cached_gauss, double* value, int64_t* event_id, int32_t* node, int32_t* kind,
+                          int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- log -> queue tracks (csrc/des_tracks.hip; the reference's MMGAN_MIDI_DES/simlog_to_vid.ipynb, first cell) --------
  * Per sample b, over the first max_lines records of its log [rec_ptr[b], rec_ptr[b + 1]) ('processing' records count
  * towards max_lines and change nothing): an arrival (kind 0) at node n adds 1 to n's counter, a departure (kind 1)

@@ -20,7 +20,9 @@
 //
 // With DES_HOST_WITH_KIND defined (tools/des_dist_host.cpp does, and includes this file) the simulator is
 // des::Sim<MathPortable, OutNone, NodeStats, AnyDist> and every case carries int32 kind[dim] between scale and qcap:
-// an exactly sized array, so a kind read past the case's nodes shows too.
+// an exactly sized array, so a kind read past the case's nodes shows too.  With DES_HOST_WITH_NODES as well
+// (tools/des_net_host.cpp) the policy is des::AnyNode -- kinds 'queue' and 'branch' too -- with its two per-node arrays,
+// delayed departures and next departure times, exactly sized like the rest.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -102,7 +104,15 @@ int main(int argc, char** argv) {
     std::vector<double> tis(d), tiq(d), area(d), arrival(d), last_change(d), atime(d * (size_t)stride),
         queue_time(d * hs, 0.0);
 
-#ifdef DES_HOST_WITH_KIND
+#if defined(DES_HOST_WITH_NODES)
+    std::vector<int32_t> delayed(d);
+    std::vector<double> next_departure(d);
+    des::Sim<des::MathPortable, des::OutNone, des::NodeStats, des::AnyNode> s;
+    s.dist.kind = kind.data();
+    s.dist.delayed = delayed.data();
+    s.dist.next_departure = next_departure.data();
+    s.dist.reset(dim, 0, 1);
+#elif defined(DES_HOST_WITH_KIND)
     des::Sim<des::MathPortable, des::OutNone, des::NodeStats, des::AnyDist> s;
     s.dist.kind = kind.data();
 #else

@@ -1,12 +1,13 @@
-"""Simulated M/M/1/K beside queueing theory (simulation_v3.mm1k_sweep, queueing_theory.mm1k): the counterpart of the
-validation harness the reference's simulator ends in.
+"""Simulated M/M/1/K and M/M/c/N beside queueing theory (simulation_v3.mm1k_sweep / mmck_sweep, queueing_theory.mm1k /
+mmck): the counterpart of the validation harness the reference's simulator ends in.
 
     python tools/des_validate.py [--device cuda] [--seeds 64] [--customers 4000]
 
 For every configuration of the default grid (rho 0.5 .. 1.5, 1 .. 5 waiting places) the source -> server net is run once
 per seed -- all configurations and seeds in ONE batch: the host mirror without --device, one kernel launch with it -- and
 each compared quantity is printed as mean +- standard error over the seeds, the closed form, and z = (mean - theory) /
-sem.  Reads nothing outside the repository."""
+sem.  Then the same table for the multi-server grid: source -> queue node -> c servers (simulation_v3.mmck_spec), one
+batch per c, beside M/M/c/N with N = c + max(cap, 1).  Reads nothing outside the repository."""
 import argparse
 import os
 import sys
@@ -18,6 +19,24 @@ sys.path.insert(0, ROOT)
 from gan_des_midi_music_gen_amd import simulation_v3 as sv  # noqa: E402
 
 GRID = ((0.5, 1.0, 1), (0.8, 1.0, 3), (1.0, 1.0, 5), (1.5, 1.0, 2), (1.6, 2.0, 4), (0.75, 0.5, 5))      # lam, mu, cap
+MMC_GRID = ((1, 0.8, 1.0, 0), (2, 1.5, 1.0, 2), (2, 1.0, 1.0, 1), (3, 2.0, 1.0, 3), (4, 6.0, 1.0, 2),
+            (3, 1.5, 1.0, 0))                                                                           # c, lam, mu, cap
+
+
+def table(sw, heads, widths, n_runs):
+    """One sweep's result, a line per compared cell; heads: per configuration, the columns in front."""
+    worst = 0.0
+    for c, head in enumerate(heads):
+        for name in sv.SWEEP_NAMES:
+            cells = [()] if sw.theory[name].ndim == 1 else [(j,) for j in range(widths[c])]
+            for j in cells:
+                i = (c,) + j
+                label = name + (f"[{j[0]}]" if j else "")
+                print(f"{head}  {label:<30} {sw.mean[name][i]:10.5f} {sw.sem[name][i]:9.5f} {sw.theory[name][i]:10.5f} "
+                      f"{sw.z[name][i]:+6.2f}  {sw.n[name][i]}")
+                worst = max(worst, abs(float(sw.z[name][i])))
+    events = np.asarray(sw.stats.events.cpu() if hasattr(sw.stats.events, "cpu") else sw.stats.events)
+    print(f"{len(heads)} configurations x {n_runs} seeds, {events.mean():.0f} events per run; largest |z| {worst:.2f}")
 
 
 def main():
@@ -26,21 +45,17 @@ def main():
     ap.add_argument("--seeds", type=int, default=64)
     ap.add_argument("--customers", type=int, default=4000)
     a = ap.parse_args()
+    seeds = np.arange(a.seeds) * 11 + 5
     lam, mu, cap = (np.array(c) for c in zip(*GRID))
-    sw = sv.mm1k_sweep(lam, mu, cap, np.arange(a.seeds) * 11 + 5, customers=a.customers, device=a.device)
+    sw = sv.mm1k_sweep(lam, mu, cap, seeds, customers=a.customers, device=a.device)
     print(f"{'lam':>5} {'mu':>5} {'cap':>3}  {'quantity':<30} {'simulated':>10} {'sem':>9} {'theory':>10} {'z':>6}  n")
-    worst = 0.0
-    for c in range(len(GRID)):
-        for name in sv.SWEEP_NAMES:
-            cells = [()] if sw.theory[name].ndim == 1 else [(j,) for j in range(int(cap[c]) + 1)]
-            for j in cells:
-                i = (c,) + j
-                label = name + (f"[{j[0]}]" if j else "")
-                print(f"{lam[c]:5.2f} {mu[c]:5.2f} {cap[c]:3d}  {label:<30} {sw.mean[name][i]:10.5f} "
-                      f"{sw.sem[name][i]:9.5f} {sw.theory[name][i]:10.5f} {sw.z[name][i]:+6.2f}  {sw.n[name][i]}")
-                worst = max(worst, abs(float(sw.z[name][i])))
-    events = np.asarray(sw.stats.events.cpu() if hasattr(sw.stats.events, "cpu") else sw.stats.events)
-    print(f"{len(GRID)} configurations x {a.seeds} seeds, {events.mean():.0f} events per run; largest |z| {worst:.2f}")
+    table(sw, [f"{lam[c]:5.2f} {mu[c]:5.2f} {cap[c]:3d}" for c in range(len(GRID))], [int(k) + 1 for k in cap], a.seeds)
+    cs, lam, mu, cap = (np.array(c) for c in zip(*MMC_GRID))
+    sw = sv.mmck_sweep(cs, lam, mu, cap, seeds, customers=a.customers, device=a.device)
+    print(f"\n{'c':>2} {'lam':>5} {'mu':>5} {'cap':>3}  {'quantity':<30} {'simulated':>10} {'sem':>9} {'theory':>10} "
+          f"{'z':>6}  n")
+    table(sw, [f"{cs[c]:2d} {lam[c]:5.2f} {mu[c]:5.2f} {cap[c]:3d}" for c in range(len(MMC_GRID))],
+          [max(int(k), 1) + 1 for k in cap], a.seeds)
 
 
 if __name__ == "__main__":
