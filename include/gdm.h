@@ -316,7 +316,8 @@ int gdm_linear_bn_act_fwd(const float* x, const float* w, const float* bias, con
  * (B-bsplit,128,T) (piano_roll, durations: the reference's stack().permute() view, network_tests.py:290) with label
  * yb.  loss[0] (+)= mean_a + mean_b; logits (B).  want_grad: dw1 (16,2,4,4), db1, dw2 (32,16,4,4), db2, dwfc (1,K),
  * dbfc.  Weights come from gdm_dcnn_pack (bf16 MFMA images + permuted fc weight + biases; rebuild after every update).
- * bf16 only; gdm_dcnn_fused_supported(T) tells whether the roll length fits (T = 50: yes).                           */
+ * bf16 only; gdm_dcnn_fused_supported(T) tells whether the roll length fits (T = 50: yes).
+ * The last 16 of the gdm_dcnn_pack_bytes(T) bytes are padding behind the biases: no kernel reads or writes them.        */
 int gdm_dcnn_fused_supported(int T);
 size_t gdm_dcnn_pack_bytes(int T);
 int gdm_dcnn_pack(const float* w1, const float* b1, const float* w2, const float* b2, const float* wfc,
