@@ -8,6 +8,8 @@
 //   waits) and the LDS images are XOR-swizzled so that fragment reads and stores are bank-conflict-free.  Two variants:
 //   K tile 64 fetched TWO tiles ahead with double-buffered LDS (one barrier per tile) for skinny long-K products that
 //   put few workgroups on a CU, and K tile 32 fetched one tile ahead (16 KB LDS) for products with many short ones.
+//   With two bf16 operands (fc1's three products) the loads are pinned in stage order, so that the wait in front of a
+//   stage's LDS stores leaves the younger stage in flight, and K tile 32 fetches two tiles ahead as well.
 //
 // Operand layouts (chosen on the host from the strides; anything else falls back to the generic kernel in gemm.hip):
 //   K-major  (k stride 1):   LDS image [row][KT k]   fragment = one ds_read_b128
@@ -18,7 +20,8 @@
 // fp32 operands are converted to bf16 on the way into LDS.  The MFMA is issued with the operands swapped (D^T), so a
 // lane ends up with 4 CONSECUTIVE n of one output row: row-major C is written 16 B (fp32) / 8 B (bf16) per lane.
 //
-// The kernel template lives in gemm_bf16_kernel.h; its instantiations are compiled in gemm_bf16_kt{32,64}_{bf16,f32}a.hip.
+// The kernel template lives in gemm_bf16_kernel.h; its instantiations are compiled in gemm_bf16_kt{32,64}_{bf16,f32}a.hip
+// and gemm_bf16_ring_kt{32,64}.hip.
 #include "gemm_common.h"
 
 namespace {
@@ -73,9 +76,22 @@ int gdm_gemm_bf16_fast_launch(const GemmArgs& g, int a_dtype, int b_dtype, const
   dim3 grid((unsigned)(((outer + 7) / 8) * 8 * MT));
   // K tile 32, one tile ahead, 16 KB LDS (many workgroups per CU); or K tile 64, two tiles ahead, 64 KB LDS
   const bool deep = p.kernel == GDM_GEMM_KERNEL_FAST_K64;
-  auto* launch = a_dtype == GDM_BF16 ? (deep ? gdm_gemm_bf16_kt64_bf16a : gdm_gemm_bf16_kt32_bf16a)
-                                     : (deep ? gdm_gemm_bf16_kt64_f32a : gdm_gemm_bf16_kt32_f32a);
-  launch(g, p.a_kmaj, b_dtype, p.b_kmaj, grid, s);
+  const bool both_bf16 = a_dtype == GDM_BF16 && b_dtype == GDM_BF16;
+  // k tiles of one workgroup: slice z of the interleaved split takes tiles z, z + split_k, ...
+  const int kt = deep ? 64 : 32;
+  const int tiles = ((g.K + kt - 1) / kt + g.split_k - 1) / g.split_k;
+  if (both_bf16 && deep) {
+    // loads pinned in stage order (the deep variant's slabs are four tiles or more: k_per_split >= 256)
+    gdm_gemm_bf16_ring_kt64(g, p.a_kmaj, p.b_kmaj, grid, s);
+  } else if (both_bf16 && tiles >= GDM_GEMM_RING_K32) {
+    // the register ring; a loop shorter than the ring would only multiply its zero tiles
+    gdm_gemm_bf16_ring_kt32(g, p.a_kmaj, p.b_kmaj, grid, s);
+  } else if (a_dtype == GDM_BF16 && deep) {
+    gdm_gemm_bf16_kt64_bf16a_f32b(g, p.a_kmaj, p.b_kmaj, grid, s);
+  } else {
+    auto* launch = a_dtype == GDM_BF16 ? gdm_gemm_bf16_kt32_bf16a : (deep ? gdm_gemm_bf16_kt64_f32a : gdm_gemm_bf16_kt32_f32a);
+    launch(g, p.a_kmaj, b_dtype, p.b_kmaj, grid, s);
+  }
   GDM_LAUNCH_OK("gdm_gemm(bf16 fast path)");
   return GDM_OK;
 }

@@ -1,7 +1,8 @@
 // The kernel template of the vectorised bf16-MFMA GEMM (gemm_bf16.hip has the description, the operand checks and the
-// dispatch).  Its 32 instantiations -- TA x A layout x TB x B layout x 2 variants, each with four epilogue bodies -- are
-// divided over gemm_bf16_kt{32,64}_{bf16,f32}a.hip by variant and A dtype: one translation unit with all of them took
-// as long to compile as everything else in the library several times over.
+// dispatch).  Its 36 instantiations -- TA x A layout x TB x B layout x 2 variants, and bf16 x bf16 with the K tile 32
+// ring as well, each with four epilogue bodies -- are divided over gemm_bf16_kt{32,64}_{bf16,f32}a.hip by variant and A
+// dtype and gemm_bf16_ring_kt{32,64}.hip: one translation unit with all of them took as long to compile as everything
+// else in the library several times over.
 #pragma once
 #include <type_traits>
 #include "buffer_ops.h"
@@ -114,13 +115,23 @@ __device__ __forceinline__ bf16x8 frag_read(const __bf16* __restrict__ img, int 
   }
 }
 
-// DEPTH = tiles fetched ahead = LDS buffers.  DEPTH 2 / KT 64: 64 KB of LDS and ~64 KB in flight per workgroup, for
-// products with few workgroups per CU (long K, split-K).  DEPTH 1 / KT 32: 16 KB of LDS, for products whose many short
-// workgroups hide each other's latency.
-template <typename TA, bool A_KMAJ, typename TB, bool B_KMAJ, int KT, int DEPTH>
+// KT 64: two LDS buffers (64 KB), one barrier per tile, for products with few workgroups per CU (long K, split-K).
+// KT 32: one LDS buffer (16 KB), two barriers per tile, for products with many short workgroups.
+// RING = register stages = tiles fetched ahead; the LDS layout does not depend on it.  The k loop is unrolled over
+// the ring (and the LDS buffers), so every stage has fixed registers and a fixed place: stage s of tile t goes to
+// LDS and is reloaded behind the barrier for tile t + RING, and its store waits for ITS loads only -- the RING - 1
+// younger stages stay in flight.  That count holds only while the loads are issued in stage order; PIN fences the
+// scheduler (sched_barrier) behind each stage's loads, in the prologue and in the loop: without it the scheduler
+// issues the prologue's stages out of order, the wait-count pass falls back to vmcnt(0) in the loop (RING 2 then
+// fetches ONE tile ahead), and the reload sinks under the tile's MFMAs.  The waits stay the compiler's own.
+// (KT, RING, PIN) = (64, 2, false) and (32, 1, false) are the instances with an fp32 operand, as they always were;
+// bf16 x bf16 runs (64, 2, true) and (32, 2, true) -- deeper rings measured slower (DESIGN.md sections 5 and 8).
+template <typename TA, bool A_KMAJ, typename TB, bool B_KMAJ, int KT, int RING, bool PIN>
 __global__ __launch_bounds__(NT) void gemm_bf16_fast(GemmArgs g) {
   constexpr int IMG = 128 * KT;                                         // elements of one operand image
-  __shared__ __attribute__((aligned(16))) __bf16 smem[2 * DEPTH * IMG];    // [buffer][A | B]
+  constexpr int NBUF = KT == 64 ? 2 : 1;                                // LDS buffers
+  constexpr int UNROLL = RING % NBUF == 0 ? RING : RING * NBUF;         // tiles per trip: every (stage, buffer) pairing
+  __shared__ __attribute__((aligned(16))) __bf16 smem[2 * NBUF * IMG];     // [buffer][A | B]
   const int t = threadIdx.x, l = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
   const int lr = l & 15, lg = l >> 4;
   // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (each with its own L2), so the MT row tiles
@@ -171,39 +182,32 @@ __global__ __launch_bounds__(NT) void gemm_bf16_fast(GemmArgs g) {
         for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(b[j], a[i], acc[i][j]);   // D^T: lane -> (m = lr, n = 4*lg + r)
     }
   };
-  Stage<TA, KT> sa[DEPTH];
-  Stage<TB, KT> sb[DEPTH];
-  if constexpr (DEPTH == 2) {
-    auto tile = [&](Stage<TA, KT>& xa, Stage<TB, KT>& xb, __bf16* As, int k0) {
+  Stage<TA, KT> sa[RING];
+  Stage<TB, KT> sb[RING];
+  auto pin = [] {
+    if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+  };
+#pragma unroll
+  for (int r = 0; r < RING; ++r) {
+    stage_load<TA, KT, A_KMAJ>(sa[r], la, ra, lda, kbeg + r * kstep, kend);
+    stage_load<TB, KT, B_KMAJ>(sb[r], lb, rb, ldb, kbeg + r * kstep, kend);
+    pin();
+  }
+  // tiles are taken UNROLL at a time; the tiles of the last trip at or past kend are zeros and are multiplied in
+  for (int k0 = kbeg; k0 < kend; k0 += UNROLL * kstep) {
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      Stage<TA, KT>& xa = sa[u % RING];
+      Stage<TB, KT>& xb = sb[u % RING];
+      __bf16* As = smem + 2 * IMG * (u % NBUF);
       __bf16* Bs = As + IMG;
-      stage_store<TA, KT>(xa, la, As);         // waits for THIS stage's loads only: the other stage's were issued later
+      if constexpr (NBUF == 1) __syncthreads();  // previous tile's fragment reads are done
+      stage_store<TA, KT>(xa, la, As);           // waits for THIS stage's loads only: the other stages' were issued later
       stage_store<TB, KT>(xb, lb, Bs);
-      __syncthreads();                         // one barrier per tile: the other LDS buffer is what laggards still read
-      stage_load<TA, KT, A_KMAJ>(xa, la, ra, lda, k0 + 2 * kstep, kend);   // two tiles ahead, always issued (zeros past kend)
-      stage_load<TB, KT, B_KMAJ>(xb, lb, rb, ldb, k0 + 2 * kstep, kend);
-      multiply(As, Bs);
-    };
-    stage_load<TA, KT, A_KMAJ>(sa[0], la, ra, lda, kbeg, kend);
-    stage_load<TB, KT, B_KMAJ>(sb[0], lb, rb, ldb, kbeg, kend);
-    stage_load<TA, KT, A_KMAJ>(sa[1], la, ra, lda, kbeg + kstep, kend);
-    stage_load<TB, KT, B_KMAJ>(sb[1], lb, rb, ldb, kbeg + kstep, kend);
-    // tiles are taken in pairs so that both register stages have a fixed place in the loop; an odd tail tile is zeros
-    for (int k0 = kbeg; k0 < kend; k0 += 2 * kstep) {
-      tile(sa[0], sb[0], smem, k0);
-      tile(sa[DEPTH - 1], sb[DEPTH - 1], smem + 2 * IMG * (DEPTH - 1), k0 + kstep);
-    }
-  } else {
-    __bf16* As = smem;
-    __bf16* Bs = smem + IMG;
-    stage_load<TA, KT, A_KMAJ>(sa[0], la, ra, lda, kbeg, kend);
-    stage_load<TB, KT, B_KMAJ>(sb[0], lb, rb, ldb, kbeg, kend);
-    for (int k0 = kbeg; k0 < kend; k0 += kstep) {
-      __syncthreads();                         // previous tile's fragment reads are done
-      stage_store<TA, KT>(sa[0], la, As);
-      stage_store<TB, KT>(sb[0], lb, Bs);
-      __syncthreads();
-      stage_load<TA, KT, A_KMAJ>(sa[0], la, ra, lda, k0 + kstep, kend);    // next tile, always issued (zeros past kend)
-      stage_load<TB, KT, B_KMAJ>(sb[0], lb, rb, ldb, k0 + kstep, kend);
+      __syncthreads();                           // (two buffers: the other one is what laggards still read)
+      stage_load<TA, KT, A_KMAJ>(xa, la, ra, lda, k0 + (u + RING) * kstep, kend);   // always issued (zeros past kend)
+      stage_load<TB, KT, B_KMAJ>(xb, lb, rb, ldb, k0 + (u + RING) * kstep, kend);
+      pin();
       multiply(As, Bs);
     }
   }
@@ -332,21 +336,16 @@ __global__ __launch_bounds__(NT) void gemm_bf16_fast(GemmArgs g) {
   }
 }
 
-// the eight instantiations of one variant (KT, DEPTH) and A dtype
-template <typename TA, int KT, int DEPTH, bool AK, typename TB>
-void launch_b(const GemmArgs& g, bool b_kmaj, dim3 grid, hipStream_t s) {
-  if (b_kmaj) hipLaunchKernelGGL((gemm_bf16_fast<TA, AK, TB, true, KT, DEPTH>), grid, dim3(NT), 0, s, g);
-  else hipLaunchKernelGGL((gemm_bf16_fast<TA, AK, TB, false, KT, DEPTH>), grid, dim3(NT), 0, s, g);
-}
-template <typename TA, int KT, int DEPTH, bool AK>
-void launch_a(const GemmArgs& g, int b_dtype, bool b_kmaj, dim3 grid, hipStream_t s) {
-  if (b_dtype == GDM_BF16) launch_b<TA, KT, DEPTH, AK, __bf16>(g, b_kmaj, grid, s);
-  else launch_b<TA, KT, DEPTH, AK, float>(g, b_kmaj, grid, s);
-}
-template <typename TA, int KT, int DEPTH>
-void launch_instances(const GemmArgs& g, bool a_kmaj, int b_dtype, bool b_kmaj, dim3 grid, hipStream_t s) {
-  if (a_kmaj) launch_a<TA, KT, DEPTH, true>(g, b_dtype, b_kmaj, grid, s);
-  else launch_a<TA, KT, DEPTH, false>(g, b_dtype, b_kmaj, grid, s);
+// the four layout instantiations of one variant (KT, RING, PIN) and operand type pair
+template <typename TA, typename TB, int KT, int RING, bool PIN>
+void launch_layouts(const GemmArgs& g, bool a_kmaj, bool b_kmaj, dim3 grid, hipStream_t s) {
+  if (a_kmaj) {
+    if (b_kmaj) hipLaunchKernelGGL((gemm_bf16_fast<TA, true, TB, true, KT, RING, PIN>), grid, dim3(NT), 0, s, g);
+    else hipLaunchKernelGGL((gemm_bf16_fast<TA, true, TB, false, KT, RING, PIN>), grid, dim3(NT), 0, s, g);
+  } else {
+    if (b_kmaj) hipLaunchKernelGGL((gemm_bf16_fast<TA, false, TB, true, KT, RING, PIN>), grid, dim3(NT), 0, s, g);
+    else hipLaunchKernelGGL((gemm_bf16_fast<TA, false, TB, false, KT, RING, PIN>), grid, dim3(NT), 0, s, g);
+  }
 }
 
 }  // namespace

@@ -34,9 +34,20 @@ struct GemmPlan {
 bool gdm_gemm_bf16_fast_ok(const GemmArgs& g, int a_dtype, int b_dtype, bool* a_kmaj, bool* b_kmaj);
 bool gdm_gemm_bf16_fast_deep(int M, int N, int split_k, int k_per_split);
 int gdm_gemm_bf16_fast_launch(const GemmArgs& g, int a_dtype, int b_dtype, const GemmPlan& p, hipStream_t s);
-// gemm_bf16_kt{32,64}_{bf16,f32}a.hip: the kernel instantiations of one variant (K tile) and A dtype
+// gemm_bf16_kt{32,64}_{bf16,f32}a.hip: the kernel instantiations of one variant (K tile) and A dtype at the variant's
+// own prefetch depth; gemm_bf16_ring_kt{32,64}.hip: the bf16 x bf16 instantiations with a deeper register ring
 void gdm_gemm_bf16_kt32_bf16a(const GemmArgs& g, bool a_kmaj, int b_dtype, bool b_kmaj, dim3 grid, hipStream_t s);
 void gdm_gemm_bf16_kt32_f32a(const GemmArgs& g, bool a_kmaj, int b_dtype, bool b_kmaj, dim3 grid, hipStream_t s);
-void gdm_gemm_bf16_kt64_bf16a(const GemmArgs& g, bool a_kmaj, int b_dtype, bool b_kmaj, dim3 grid, hipStream_t s);
+void gdm_gemm_bf16_kt64_bf16a_f32b(const GemmArgs& g, bool a_kmaj, bool b_kmaj, dim3 grid, hipStream_t s);
 void gdm_gemm_bf16_kt64_f32a(const GemmArgs& g, bool a_kmaj, int b_dtype, bool b_kmaj, dim3 grid, hipStream_t s);
+void gdm_gemm_bf16_ring_kt32(const GemmArgs& g, bool a_kmaj, bool b_kmaj, dim3 grid, hipStream_t s);
+void gdm_gemm_bf16_ring_kt64(const GemmArgs& g, bool a_kmaj, bool b_kmaj, dim3 grid, hipStream_t s);
+// register stages of the ring instances = tiles fetched ahead.  2 and 2 are the fastest of the depths measured on
+// fc1's three products (K tile 64: 2, 3, 4; K tile 32: 1, 2, 4 -- DESIGN.md section 5); experiment builds override.
+#ifndef GDM_GEMM_RING_K64
+#define GDM_GEMM_RING_K64 2
+#endif
+#ifndef GDM_GEMM_RING_K32
+#define GDM_GEMM_RING_K32 2
+#endif
 constexpr int GDM_GEMM_FAST_KT = 64;   // split-K slabs are multiples of the widest K tile
