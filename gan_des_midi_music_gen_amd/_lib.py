@@ -125,29 +125,11 @@ SIGNATURES = {
     "gdm_des_draws": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I] + [_P] * 16),
     "gdm_des_draws_host": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I] + [_P] * 15),
     "gdm_des_run": (_I,[_P, _I, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _P, _L, _P, _P]),
-    "gdm_des_run_batch_host": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P,
-                                    _P, _P]),
     "gdm_des_batch_workspace_bytes": (_L, [_I, _I, _I]),
-    "gdm_des_run_batch": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P,
-                               _P, _Z, _P]),
     "gdm_des_pack": (_I, [_I, _L, _P, _P, _P, _P, _P, _P, _P]),
     "gdm_des_math_probe_host": (_I, [_P, _L, _P, _P]),
     "gdm_des_math_probe": (_I, [_P, _L, _P, _P, _P]),
-    "gdm_des_stats_batch_host": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _L] + [_P] * 19),
     "gdm_des_stats_workspace_bytes": (_L, [_I, _I, _I]),
-    "gdm_des_stats_batch": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _L] + [_P] * 19 + [_P, _Z, _P]),
-    "gdm_des_stats_batch_dist_host": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _L] + [_P] * 19),
-    "gdm_des_stats_batch_dist": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _L] + [_P] * 19 + [_P, _Z, _P]),
-    "gdm_des_run_batch_dist_host": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P,
-                                         _L, _P, _P, _P]),
-    "gdm_des_run_batch_dist": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P,
-                                    _P, _P, _P, _Z, _P]),
-    "gdm_des_stats_batch_net_host": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _L] + [_P] * 19),
-    "gdm_des_stats_batch_net": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _L] + [_P] * 19 + [_P, _Z, _P]),
-    "gdm_des_run_batch_net_host": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P,
-                                        _L, _P, _P, _P]),
-    "gdm_des_run_batch_net": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P,
-                                   _P, _P, _P, _Z, _P]),
     "gdm_des_log_tracks_count": (_I, [_P, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P, _P]),
     "gdm_des_log_tracks": (_I, [_P, _P, _P, _L, _I, _I, _P, _I, _L, _P, _L, _P, _P]),
     "gdm_des_log_tracks_host": (_I, [_P, _P, _P, _L, _I, _I, _P, _I, _L, _P, _P, _P, _P, _L]),
@@ -165,6 +147,25 @@ SIGNATURES = {
     "gdm_maxpool2_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "gdm_maxpool2_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
 }
+
+# The twelve batch entries of the DES simulator, gdm_des_{run,stats}_batch[_dist|_net][_host] (include/gdm.h), composed
+# from the pieces of their argument lists:
+_DES_NET = [_P, _I, _I, _P, _P]                        # adj, B, dim, loc, scale
+_DES_KIND = [_P]                                       # kind (B, dim): the _dist and _net entries, behind scale
+_DES_SPEC = [_P, _P, _P, _I]                           # queue_cap, seed, number_of_customers, max_queue_cap
+_DES_MATH = [_I]                                       # math: the _host entries
+_DES_CAPS = {"run": [_L, _L], "stats": [_L]}           # max_events; the log mode: max_records
+_DES_STATE = [_P] * 4                                  # mt_key, mt_pos, has_gauss, cached_gauss
+_DES_OUT = {"run": [_P, _P, _P, _P, _L, _P, _P, _P],   # value, event_id, node, kind, n_records_cap, rec_ptr, n_records,
+                                                       # stop_reason
+            "stats": [_P] * 15}                        # eight (B, dim) rows, six (B) rows, queue_time
+_DES_DEVICE = [_P, _Z, _P]                             # workspace, workspace_bytes, stream: the device entries
+for _mode in ("run", "stats"):
+    for _policy in ("", "_dist", "_net"):
+        for _host in ("", "_host"):
+            SIGNATURES[f"gdm_des_{_mode}_batch{_policy}{_host}"] = (
+                _I, _DES_NET + (_DES_KIND if _policy else []) + _DES_SPEC + (_DES_MATH if _host else []) +
+                _DES_CAPS[_mode] + _DES_STATE + _DES_OUT[_mode] + ([] if _host else _DES_DEVICE))
 
 _lock = threading.Lock()
 _lib = None

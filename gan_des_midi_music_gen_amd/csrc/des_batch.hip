@@ -15,10 +15,12 @@
 // and the FIFO rings (L2-resident: about 330 KB per sample at dim 61, capacity 254).
 // The prologue up to the chain, the LDS block and the workspace layout are des_wave.h's, shared with the log-free
 // statistics kernel of des_stats.hip.
-// Three kernels over one body (batch_sample): des_batch_kernel draws 'normal' only (des::NormalOnly, the bridges' nets);
-// des_batch_dist_kernel takes a kind per node (des::AnyDist: normal, exponential, uniform), its row staged into LDS
-// (512 B more), and leaves the generator state of a sample that errors as it came; des_batch_net_kernel is that kernel
-// with the reference's 'queue' and 'branch' nodes as well (des::AnyNode: kinds and node state, 2 KB of LDS).
+// One kernel template over one body (batch_sample), instantiated for the three node policies of des_wave.h:
+// des_batch_kernel<NormalOnly> draws 'normal' only (the bridges' nets); des_batch_kernel<AnyDist> takes a kind per node
+// (normal, exponential, uniform), its row staged into LDS (512 B more), and leaves the generator state of a sample that
+// errors as it came; des_batch_kernel<AnyNode> is that kernel with the reference's 'queue' and 'branch' nodes as well
+// (kinds and node state, 2 KB of LDS).  (Older texts call the three des_batch_kernel, des_batch_dist_kernel,
+// des_batch_net_kernel.)  One launcher template (launch_batch) is behind the three entries.
 // Bounds: every index the chain computes is checked in des_sim.h before it forms an address; every loop is bounded by
 // max_events, max_records or the draw budget.
 #include "gdm_common.h"
@@ -32,17 +34,8 @@ namespace {
 using des_wave::kMaxDim;
 using des_wave::ws_layout;
 constexpr int kPackThreads = 256;
-typedef des::Sim<des::MathPortable, des::OutSoa> DevSim;
 
-typedef des::Sim<des::MathPortable, des::OutSoa, des::NoStats, des::AnyDist> DevDistSim;
-typedef des::Sim<des::MathPortable, des::OutSoa, des::NoStats, des::AnyNode> DevNetSim;
-
-// the kinds of one sample (des_batch_dist_kernel only: des_wave::Lds is the layout of the kernels that have none)
-struct DistLds {
-  int32_t kind[kMaxDim];
-};
-
-// the inputs and outputs both kernels share
+// the inputs and outputs the kernels share
 struct BatchArgs {
   const double* adj;
   int dim;
@@ -97,7 +90,9 @@ __device__ __forceinline__ void batch_sample(SimT& s, des_wave::Lds& lds, unsign
   if (kErrorKeepsState ? lds.ok != 0 : ok) des_wave::store_generator_words(lds, b, lane, a.mt_key);
 }
 
-// the parameter list both kernels share (kernel parameters stay plain __restrict__ pointers) and the BatchArgs of them
+// The kernels' parameter list and the BatchArgs of it, under the names the entries below use too.  Kernel parameters
+// stay plain __restrict__ pointers: with the struct as the parameter the compiler loses the no-alias facts and the
+// kernels come out longer.
 #define DES_BATCH_PARAMS                                                                                               \
   const double *__restrict__ adj, int dim, const double *__restrict__ loc, const double *__restrict__ scale,           \
       const int32_t *__restrict__ queue_cap, const int64_t *__restrict__ seed,                                         \
@@ -109,38 +104,39 @@ __device__ __forceinline__ void batch_sample(SimT& s, des_wave::Lds& lds, unsign
 #define DES_BATCH_ARGS                                                                                                 \
   BatchArgs {                                                                                                          \
     adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records, mt_key,        \
-        mt_pos, mt_has_gauss, mt_gauss, value, event_id, node, kind, n_records, stop_reason, workspace                 \
+        mt_pos, mt_has_gauss, mt_gauss, value, event_id, node, kind, n_records, stop_reason,                           \
+        (unsigned char*)workspace                                                                                      \
   }
 
-__global__ __launch_bounds__(GDM_WAVE) void des_batch_kernel(DES_BATCH_PARAMS) {
+// One kernel per node policy (des_wave.h) over that body.  flatten, as des_stats_kernel: three kinds at three draw sites
+// exceed the inliner's budget, and a chain function left out of line takes the Sim by address -- scratch per lane and a
+// load for every member; inlined whole there is no scratch.  The policy's block is staged before the prologue, whose
+// first barrier orders it before lane 0 reads it.  The policies with kinds keep the generator state of a sample that
+// errors (kErrorKeepsState above).
+template <class Policy>
+__global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_batch_kernel(
+    DES_BATCH_PARAMS, const int32_t* __restrict__ node_kind) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];       // node generators when dim <= kLdsGenDim
   __shared__ des_wave::Lds lds;
-  DevSim s;
-  batch_sample<false>(s, lds, s_dyn, DES_BATCH_ARGS);
+  __shared__ typename Policy::Block pl;
+  des::Sim<des::MathPortable, des::OutSoa, des::NoStats, typename Policy::Dist> s;
+  Policy::stage(s.dist, pl, node_kind, dim, blockIdx.x, threadIdx.x);
+  batch_sample<Policy::kHasKind>(s, lds, s_dyn, DES_BATCH_ARGS);
 }
 
-// The logging kernel with a distribution kind per node (des::AnyDist).  flatten, as des_stats_dist_kernel: three kinds
-// at three draw sites exceed the inliner's budget, and a chain function left out of line takes the Sim by address --
-// scratch per lane and a load for every member; inlined whole there is no scratch
-__global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_batch_dist_kernel(
+// des_wave::AnyDist keeps the statement order its kernel always had, the kinds staged in the kernel's own body: through
+// AnyDist::stage the compiler schedules the chain differently (83 VGPRs for 95, 142 instructions more), and at B = 256
+// that kernel measured 0.5 % above the parent's where the parent's two runs lay 0.2 % apart (DESIGN.md section 7,
+// f19).  This form gives the parent's kernel, instruction for instruction.
+template <>
+__global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_batch_kernel<des_wave::AnyDist>(
     DES_BATCH_PARAMS, const int32_t* __restrict__ dist_kind) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
   __shared__ des_wave::Lds lds;
-  __shared__ DistLds dl;
+  __shared__ des_wave::DistLds dl;
   for (int i = threadIdx.x; i < dim; i += GDM_WAVE) dl.kind[i] = dist_kind[(int64_t)blockIdx.x * dim + i];
-  DevDistSim s;
+  des::Sim<des::MathPortable, des::OutSoa, des::NoStats, des::AnyDist> s;
   s.dist.kind = dl.kind;
-  batch_sample<true>(s, lds, s_dyn, DES_BATCH_ARGS);
-}
-
-// The logging kernel with a kind per node that may be 'queue' or 'branch' (des::AnyNode); flatten as above
-__global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_batch_net_kernel(
-    DES_BATCH_PARAMS, const int32_t* __restrict__ node_kind) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-  __shared__ des_wave::Lds lds;
-  __shared__ des_wave::NetLds nl;
-  DevNetSim s;
-  des_wave::stage_net(s.dist, nl, node_kind, dim, blockIdx.x, threadIdx.x);
   batch_sample<true>(s, lds, s_dyn, DES_BATCH_ARGS);
 }
 
@@ -217,7 +213,8 @@ extern "C" int64_t gdm_des_batch_workspace_bytes(int B, int dim, int max_queue_c
   return (int64_t)(ws_layout(dim, max_queue_cap, false).per_sample * (size_t)B);
 }
 
-// the checks the device entries make on the host; `who` names the entry in the message
+// The checks the device entries make on the host; `who` names the entry in the message.  They check less than the
+// statistics entries (no alignment of the arrays but `kind`): adding that is a change of behaviour, left for another day.
 static int check_batch_args(const char* who, const BatchArgs& a, int B, const int32_t* dist_kind, bool with_kind,
                             int64_t n_records_cap, const int64_t* rec_ptr, size_t workspace_bytes) {
   GDM_REQUIRE(a.adj && a.loc && a.scale && a.queue_cap && a.seed && a.number_of_customers && a.mt_key && a.mt_pos &&
@@ -243,69 +240,52 @@ static int check_batch_args(const char* who, const BatchArgs& a, int B, const in
   return GDM_OK;
 }
 
+// what every entry does: the checks, its policy's kernel, then the pack step (`dist_kind` is nullptr where the policy
+// has none)
+template <class Policy>
+static int launch_batch(const char* who, const BatchArgs& a, int B, const int32_t* dist_kind, int64_t n_records_cap,
+                        int64_t* rec_ptr, size_t workspace_bytes, void* stream) {
+  const int rc = check_batch_args(who, a, B, dist_kind, Policy::kHasKind, n_records_cap, rec_ptr, workspace_bytes);
+  if (rc != GDM_OK) return rc;
+  hipLaunchKernelGGL(des_batch_kernel<Policy>, dim3(B), dim3(GDM_WAVE), des_wave::lds_dyn_bytes(a.dim),
+                     (hipStream_t)stream, a.adj, a.dim, a.loc, a.scale, a.queue_cap, a.seed, a.number_of_customers,
+                     a.max_queue_cap, a.max_events, a.max_records, a.mt_key, a.mt_pos, a.mt_has_gauss, a.mt_gauss,
+                     a.value, a.event_id, a.node, a.kind, a.n_records, a.stop_reason, a.workspace, dist_kind);
+  GDM_LAUNCH_OK(who);
+  return gdm_des_pack(B, a.max_records, a.n_records, rec_ptr, a.value, a.event_id, a.node, a.kind, stream);
+}
+
 extern "C" int gdm_des_run_batch(const double* adj, int B, int dim, const double* loc, const double* scale,
                                  const int32_t* queue_cap, const int64_t* seed, const int64_t* number_of_customers,
                                  int max_queue_cap, int64_t max_events, int64_t max_records, uint32_t* mt_key,
-                                 int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss, double* value,
+                                 int32_t* mt_pos, int32_t* mt_has_gauss, double* mt_gauss, double* value,
                                  int64_t* event_id, int32_t* node, int32_t* kind, int64_t n_records_cap,
                                  int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-  const BatchArgs a{adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records,
-                    mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
-                    (unsigned char*)workspace};
-  const int rc = check_batch_args("gdm_des_run_batch", a, B, nullptr, false, n_records_cap, rec_ptr, workspace_bytes);
-  if (rc != GDM_OK) return rc;
-  const size_t lds_dyn = des_wave::lds_dyn_bytes(dim);
-  hipLaunchKernelGGL(des_batch_kernel, dim3(B), dim3(GDM_WAVE), lds_dyn, (hipStream_t)stream, adj, dim, loc, scale,
-                     queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records, mt_key, mt_pos,
-                     has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
-                     (unsigned char*)workspace);
-  GDM_LAUNCH_OK("gdm_des_run_batch");
-  return gdm_des_pack(B, max_records, n_records, rec_ptr, value, event_id, node, kind, stream);
+  return launch_batch<des_wave::NormalOnly>("gdm_des_run_batch", DES_BATCH_ARGS, B, nullptr, n_records_cap, rec_ptr,
+                                            workspace_bytes, stream);
 }
 
 extern "C" int gdm_des_run_batch_dist(const double* adj, int B, int dim, const double* loc, const double* scale,
                                       const int32_t* dist_kind, const int32_t* queue_cap, const int64_t* seed,
                                       const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
-                                      int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
-                                      double* cached_gauss, double* value, int64_t* event_id, int32_t* node,
+                                      int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* mt_has_gauss,
+                                      double* mt_gauss, double* value, int64_t* event_id, int32_t* node,
                                       int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records,
                                       int32_t* stop_reason, void* workspace, size_t workspace_bytes, void* stream) {
-  const BatchArgs a{adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records,
-                    mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
-                    (unsigned char*)workspace};
-  const int rc =
-      check_batch_args("gdm_des_run_batch_dist", a, B, dist_kind, true, n_records_cap, rec_ptr, workspace_bytes);
-  if (rc != GDM_OK) return rc;
-  const size_t lds_dyn = des_wave::lds_dyn_bytes(dim);
-  hipLaunchKernelGGL(des_batch_dist_kernel, dim3(B), dim3(GDM_WAVE), lds_dyn, (hipStream_t)stream, adj, dim, loc, scale,
-                     queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records, mt_key, mt_pos,
-                     has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
-                     (unsigned char*)workspace, dist_kind);
-  GDM_LAUNCH_OK("gdm_des_run_batch_dist");
-  return gdm_des_pack(B, max_records, n_records, rec_ptr, value, event_id, node, kind, stream);
+  return launch_batch<des_wave::AnyDist>("gdm_des_run_batch_dist", DES_BATCH_ARGS, B, dist_kind, n_records_cap, rec_ptr,
+                                         workspace_bytes, stream);
 }
 
 extern "C" int gdm_des_run_batch_net(const double* adj, int B, int dim, const double* loc, const double* scale,
                                      const int32_t* node_kind, const int32_t* queue_cap, const int64_t* seed,
                                      const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
-                                     int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
-                                     double* cached_gauss, double* value, int64_t* event_id, int32_t* node,
+                                     int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* mt_has_gauss,
+                                     double* mt_gauss, double* value, int64_t* event_id, int32_t* node,
                                      int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records,
                                      int32_t* stop_reason, void* workspace, size_t workspace_bytes, void* stream) {
-  const BatchArgs a{adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records,
-                    mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
-                    (unsigned char*)workspace};
-  const int rc =
-      check_batch_args("gdm_des_run_batch_net", a, B, node_kind, true, n_records_cap, rec_ptr, workspace_bytes);
-  if (rc != GDM_OK) return rc;
-  const size_t lds_dyn = des_wave::lds_dyn_bytes(dim);
-  hipLaunchKernelGGL(des_batch_net_kernel, dim3(B), dim3(GDM_WAVE), lds_dyn, (hipStream_t)stream, adj, dim, loc, scale,
-                     queue_cap, seed, number_of_customers, max_queue_cap, max_events, max_records, mt_key, mt_pos,
-                     has_gauss, cached_gauss, value, event_id, node, kind, n_records, stop_reason,
-                     (unsigned char*)workspace, node_kind);
-  GDM_LAUNCH_OK("gdm_des_run_batch_net");
-  return gdm_des_pack(B, max_records, n_records, rec_ptr, value, event_id, node, kind, stream);
+  return launch_batch<des_wave::AnyNode>("gdm_des_run_batch_net", DES_BATCH_ARGS, B, node_kind, n_records_cap, rec_ptr,
+                                         workspace_bytes, stream);
 }
 
 extern "C" int gdm_des_pack(int B, int64_t max_records, const int64_t* n_records, int64_t* rec_ptr, double* value,

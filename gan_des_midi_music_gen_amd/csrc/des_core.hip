@@ -125,17 +125,33 @@ int check_kinds(const char* who, const int32_t* kind, int B, int dim, int last) 
   return GDM_OK;
 }
 
+// the last valid kind of a policy; none where the policy reads no kinds (des::NormalOnly)
+template <class Dist>
+constexpr int kLastKind = -1;
+template <>
+constexpr int kLastKind<des::AnyDist> = GDM_DES_DIST_UNIFORM;
+template <>
+constexpr int kLastKind<des::AnyNode> = GDM_DES_DIST_BRANCH;
+
+// the dispatch on `math` of every batch entry (checked to be 0 or 1 before): f(MathLibm{}) or f(des::MathPortable{})
+template <class F>
+auto with_math(int math, F f) {
+  return math == 0 ? f(MathLibm{}) : f(des::MathPortable{});
+}
+
 // Dist = des::NormalOnly for gdm_des_run_batch_host (dist_kind is not read), des::AnyDist for
-// gdm_des_run_batch_dist_host; `who` names the entry in the message.  kErrorKeepsState: a sample whose chain ends in
-// DES_STOP_ERROR leaves the generator state as it came (the entry with kinds, as the statistics entries); without it
-// the state is written back whenever the spec passed spec_ok (gdm_des_run_batch_host, as ever).
-template <class Math, class Dist, bool kErrorKeepsState>
+// gdm_des_run_batch_dist_host, des::AnyNode for gdm_des_run_batch_net_host; `who` names the entry in the message.
+// kErrorKeepsState: a sample whose chain ends in DES_STOP_ERROR leaves the generator state as it came (the entries
+// with kinds, as the statistics entries); without it the state is written back whenever the spec passed spec_ok
+// (gdm_des_run_batch_host, as ever).
+template <class Math, class Dist>
 int run_batch_host(const char* who, const double* adj, int B, int dim, const double* loc, const double* scale,
                    const int32_t* dist_kind, const int32_t* queue_cap, const int64_t* seed,
                    const int64_t* number_of_customers, int max_queue_cap, int64_t max_events, int64_t max_records,
                    uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss, double* value,
                    int64_t* event_id, int32_t* node, int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr,
                    int64_t* n_records, int32_t* stop_reason) {
+  constexpr bool kErrorKeepsState = kLastKind<Dist> >= 0;
   HostSim<Math, des::OutSoa, des::NoStats, Dist> h(dim, max_queue_cap);
   NodeState<Dist> nodes(dim);
   int64_t at = 0;                                       // records written so far (needed, when the arrays overflow)
@@ -183,7 +199,8 @@ int run_batch_host(const char* who, const double* adj, int B, int dim, const dou
 
 // The statistics mode: the same chain with the null sink and the accumulators of des::NodeStats writing straight into
 // the caller's (B, dim) rows; what des_stats.hip runs one wave per sample.  Dist = des::NormalOnly for
-// gdm_des_stats_batch_host (kind is not read), des::AnyDist for gdm_des_stats_batch_dist_host.
+// gdm_des_stats_batch_host (kind is not read), des::AnyDist for gdm_des_stats_batch_dist_host, des::AnyNode for
+// gdm_des_stats_batch_net_host.
 struct StatsOut {
   int64_t *served, *reneges, *generated;
   int32_t* max_queue;
@@ -274,6 +291,28 @@ int check_stats_host(const char* who, const double* adj, int B, int dim, const d
   return GDM_OK;
 }
 
+// what every host statistics entry does: the common checks, the kinds where the policy has any (AFTER the common
+// checks; the logging entries check them first), the dispatch on math
+template <class Dist>
+int stats_batch_host_entry(const char* who, const double* adj, int B, int dim, const double* loc, const double* scale,
+                           const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
+                           const int64_t* number_of_customers, int max_queue_cap, int math, int64_t max_events,
+                           uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
+                           const StatsOut& o) {
+  constexpr bool kHasKind = kLastKind<Dist> >= 0;
+  GDM_REQUIRE(kind || !kHasKind, "%s: null pointer", who);
+  int rc = check_stats_host(who, adj, B, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, math,
+                            max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
+  if (rc == GDM_OK && kHasKind) rc = check_kinds(who, kind, B, dim, kLastKind<Dist>);
+  if (rc != GDM_OK) return rc;
+  with_math(math, [&](auto m) {
+    stats_batch_host<decltype(m), Dist>(adj, B, dim, loc, scale, kind, queue_cap, seed, number_of_customers,
+                                        max_queue_cap, max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
+    return 0;
+  });
+  return GDM_OK;
+}
+
 }  // namespace
 
 extern "C" int gdm_des_run(const double* adj, int dim, const double* loc, const double* scale, const int32_t* queue_cap,
@@ -321,14 +360,21 @@ extern "C" int gdm_des_run(const double* adj, int dim, const double* loc, const 
   return GDM_OK;
 }
 
-// the argument checks of both host logging entries and the dispatch on math; `who` names the entry in the message
-template <class Dist, bool kErrorKeepsState>
+// The argument checks of the host logging entries and the dispatch on math; `who` names the entry in the message.  The
+// kinds, where the policy has any, are checked BEFORE the common checks (the statistics entries check them after).
+template <class Dist>
 int run_batch_host_entry(const char* who, const double* adj, int B, int dim, const double* loc, const double* scale,
                          const int32_t* dist_kind, const int32_t* queue_cap, const int64_t* seed,
                          const int64_t* number_of_customers, int max_queue_cap, int math, int64_t max_events,
                          int64_t max_records, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
                          double* cached_gauss, double* value, int64_t* event_id, int32_t* node, int32_t* kind,
                          int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason) {
+  if (kLastKind<Dist> >= 0) {
+    GDM_REQUIRE(dist_kind, "%s: null pointer", who);
+    GDM_REQUIRE(B >= 1 && dim >= 1, "%s: B >= 1, dim >= 1", who);
+    const int rc = check_kinds(who, dist_kind, B, dim, kLastKind<Dist>);
+    if (rc != GDM_OK) return rc;
+  }
   GDM_REQUIRE(adj && loc && scale && queue_cap && seed && number_of_customers && mt_key && mt_pos && has_gauss &&
                   cached_gauss && rec_ptr && n_records && stop_reason,
               "%s: null pointer", who);
@@ -342,15 +388,12 @@ int run_batch_host_entry(const char* who, const double* adj, int B, int dim, con
   GDM_REQUIRE(n_records_cap >= 0 && (n_records_cap == 0 || (value && event_id && node && kind)),
               "%s: record arrays missing", who);
   GDM_REQUIRE(math == 0 || math == 1, "%s: math must be 0 (libm) or 1 (portable)", who);
-  if (math == 0)
-    return run_batch_host<MathLibm, Dist, kErrorKeepsState>(who, adj, B, dim, loc, scale, dist_kind, queue_cap, seed, number_of_customers,
-                                          max_queue_cap, max_events, max_records, mt_key, mt_pos, has_gauss,
-                                          cached_gauss, value, event_id, node, kind, n_records_cap, rec_ptr, n_records,
-                                          stop_reason);
-  return run_batch_host<des::MathPortable, Dist, kErrorKeepsState>(who, adj, B, dim, loc, scale, dist_kind, queue_cap, seed,
-                                                 number_of_customers, max_queue_cap, max_events, max_records, mt_key,
-                                                 mt_pos, has_gauss, cached_gauss, value, event_id, node, kind,
-                                                 n_records_cap, rec_ptr, n_records, stop_reason);
+  return with_math(math, [&](auto m) {
+    return run_batch_host<decltype(m), Dist>(who, adj, B, dim, loc, scale, dist_kind, queue_cap, seed,
+                                             number_of_customers, max_queue_cap, max_events, max_records, mt_key,
+                                             mt_pos, has_gauss, cached_gauss, value, event_id, node, kind,
+                                             n_records_cap, rec_ptr, n_records, stop_reason);
+  });
 }
 
 extern "C" int gdm_des_run_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale,
@@ -359,7 +402,7 @@ extern "C" int gdm_des_run_batch_host(const double* adj, int B, int dim, const d
                                       uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
                                       double* value, int64_t* event_id, int32_t* node, int32_t* kind,
                                       int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason) {
-  return run_batch_host_entry<des::NormalOnly, false>("gdm_des_run_batch_host", adj, B, dim, loc, scale, nullptr, queue_cap,
+  return run_batch_host_entry<des::NormalOnly>("gdm_des_run_batch_host", adj, B, dim, loc, scale, nullptr, queue_cap,
                                                seed, number_of_customers, max_queue_cap, math, max_events, max_records,
                                                mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node, kind,
                                                n_records_cap, rec_ptr, n_records, stop_reason);
@@ -372,11 +415,7 @@ extern "C" int gdm_des_run_batch_dist_host(const double* adj, int B, int dim, co
                                            int32_t* has_gauss, double* cached_gauss, double* value, int64_t* event_id,
                                            int32_t* node, int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr,
                                            int64_t* n_records, int32_t* stop_reason) {
-  GDM_REQUIRE(dist_kind, "gdm_des_run_batch_dist_host: null pointer");
-  GDM_REQUIRE(B >= 1 && dim >= 1, "gdm_des_run_batch_dist_host: B >= 1, dim >= 1");
-  const int rc = check_kinds("gdm_des_run_batch_dist_host", dist_kind, B, dim, GDM_DES_DIST_UNIFORM);
-  if (rc != GDM_OK) return rc;
-  return run_batch_host_entry<des::AnyDist, true>("gdm_des_run_batch_dist_host", adj, B, dim, loc, scale, dist_kind,
+  return run_batch_host_entry<des::AnyDist>("gdm_des_run_batch_dist_host", adj, B, dim, loc, scale, dist_kind,
                                             queue_cap, seed, number_of_customers, max_queue_cap, math, max_events,
                                             max_records, mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node,
                                             kind, n_records_cap, rec_ptr, n_records, stop_reason);
@@ -389,14 +428,10 @@ extern "C" int gdm_des_run_batch_net_host(const double* adj, int B, int dim, con
                                           int32_t* has_gauss, double* cached_gauss, double* value, int64_t* event_id,
                                           int32_t* node, int32_t* kind, int64_t n_records_cap, int64_t* rec_ptr,
                                           int64_t* n_records, int32_t* stop_reason) {
-  GDM_REQUIRE(node_kind, "gdm_des_run_batch_net_host: null pointer");
-  GDM_REQUIRE(B >= 1 && dim >= 1, "gdm_des_run_batch_net_host: B >= 1, dim >= 1");
-  const int rc = check_kinds("gdm_des_run_batch_net_host", node_kind, B, dim, GDM_DES_DIST_BRANCH);
-  if (rc != GDM_OK) return rc;
-  return run_batch_host_entry<des::AnyNode, true>("gdm_des_run_batch_net_host", adj, B, dim, loc, scale, node_kind,
-                                                  queue_cap, seed, number_of_customers, max_queue_cap, math, max_events,
-                                                  max_records, mt_key, mt_pos, has_gauss, cached_gauss, value, event_id,
-                                                  node, kind, n_records_cap, rec_ptr, n_records, stop_reason);
+  return run_batch_host_entry<des::AnyNode>("gdm_des_run_batch_net_host", adj, B, dim, loc, scale, node_kind,
+                                            queue_cap, seed, number_of_customers, max_queue_cap, math, max_events,
+                                            max_records, mt_key, mt_pos, has_gauss, cached_gauss, value, event_id, node,
+                                            kind, n_records_cap, rec_ptr, n_records, stop_reason);
 }
 
 extern "C" int gdm_des_math_probe_host(const double* x, int64_t n, double* log_out, double* factor_out) {
@@ -409,6 +444,15 @@ extern "C" int gdm_des_math_probe_host(const double* x, int64_t n, double* log_o
   return GDM_OK;
 }
 
+// the arguments the host statistics entries share, as stats_batch_host_entry takes them behind `who`
+#define DES_STATS_HOST_ARGS(kind)                                                                                      \
+  adj, B, dim, loc, scale, kind, queue_cap, seed, number_of_customers, max_queue_cap, math, max_events, mt_key, mt_pos, \
+      has_gauss, cached_gauss,                                                                                         \
+      StatsOut {                                                                                                       \
+    served, reneges, generated, max_queue, time_in_service, time_in_queue, queue_area, arrival_time, clock, end_time,  \
+        total_customers, events, n_records, stop_reason, queue_time                                                    \
+  }
+
 extern "C" int gdm_des_stats_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale,
                                         const int32_t* queue_cap, const int64_t* seed,
                                         const int64_t* number_of_customers, int max_queue_cap, int math,
@@ -418,20 +462,7 @@ extern "C" int gdm_des_stats_batch_host(const double* adj, int B, int dim, const
                                         double* queue_area, double* arrival_time, double* clock, double* end_time,
                                         int64_t* total_customers, int64_t* events, int64_t* n_records,
                                         int32_t* stop_reason, double* queue_time) {
-  const StatsOut o{served, reneges, generated, max_queue, time_in_service, time_in_queue, queue_area, arrival_time,
-                   clock, end_time, total_customers, events, n_records, stop_reason, queue_time};
-  const int rc = check_stats_host("gdm_des_stats_batch_host", adj, B, dim, loc, scale, queue_cap, seed,
-                                  number_of_customers, max_queue_cap, math, max_events, mt_key, mt_pos, has_gauss,
-                                  cached_gauss, o);
-  if (rc != GDM_OK) return rc;
-  if (math == 0)
-    stats_batch_host<MathLibm, des::NormalOnly>(adj, B, dim, loc, scale, nullptr, queue_cap, seed, number_of_customers,
-                                                max_queue_cap, max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
-  else
-    stats_batch_host<des::MathPortable, des::NormalOnly>(adj, B, dim, loc, scale, nullptr, queue_cap, seed,
-                                                         number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,
-                                                         has_gauss, cached_gauss, o);
-  return GDM_OK;
+  return stats_batch_host_entry<des::NormalOnly>("gdm_des_stats_batch_host", DES_STATS_HOST_ARGS(nullptr));
 }
 
 extern "C" int gdm_des_stats_batch_dist_host(const double* adj, int B, int dim, const double* loc, const double* scale,
@@ -444,23 +475,7 @@ extern "C" int gdm_des_stats_batch_dist_host(const double* adj, int B, int dim, 
                                              double* clock, double* end_time, int64_t* total_customers,
                                              int64_t* events, int64_t* n_records, int32_t* stop_reason,
                                              double* queue_time) {
-  const StatsOut o{served, reneges, generated, max_queue, time_in_service, time_in_queue, queue_area, arrival_time,
-                   clock, end_time, total_customers, events, n_records, stop_reason, queue_time};
-  GDM_REQUIRE(kind, "gdm_des_stats_batch_dist_host: null pointer");
-  int rc = check_stats_host("gdm_des_stats_batch_dist_host", adj, B, dim, loc, scale, queue_cap, seed,
-                            number_of_customers, max_queue_cap, math, max_events, mt_key, mt_pos, has_gauss,
-                            cached_gauss, o);
-  if (rc != GDM_OK) return rc;
-  rc = check_kinds("gdm_des_stats_batch_dist_host", kind, B, dim, GDM_DES_DIST_UNIFORM);
-  if (rc != GDM_OK) return rc;
-  if (math == 0)
-    stats_batch_host<MathLibm, des::AnyDist>(adj, B, dim, loc, scale, kind, queue_cap, seed, number_of_customers,
-                                             max_queue_cap, max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
-  else
-    stats_batch_host<des::MathPortable, des::AnyDist>(adj, B, dim, loc, scale, kind, queue_cap, seed,
-                                                      number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,
-                                                      has_gauss, cached_gauss, o);
-  return GDM_OK;
+  return stats_batch_host_entry<des::AnyDist>("gdm_des_stats_batch_dist_host", DES_STATS_HOST_ARGS(kind));
 }
 
 extern "C" int gdm_des_stats_batch_net_host(const double* adj, int B, int dim, const double* loc, const double* scale,
@@ -473,21 +488,5 @@ extern "C" int gdm_des_stats_batch_net_host(const double* adj, int B, int dim, c
                                             double* clock, double* end_time, int64_t* total_customers,
                                             int64_t* events, int64_t* n_records, int32_t* stop_reason,
                                             double* queue_time) {
-  const StatsOut o{served, reneges, generated, max_queue, time_in_service, time_in_queue, queue_area, arrival_time,
-                   clock, end_time, total_customers, events, n_records, stop_reason, queue_time};
-  GDM_REQUIRE(kind, "gdm_des_stats_batch_net_host: null pointer");
-  int rc = check_stats_host("gdm_des_stats_batch_net_host", adj, B, dim, loc, scale, queue_cap, seed,
-                            number_of_customers, max_queue_cap, math, max_events, mt_key, mt_pos, has_gauss,
-                            cached_gauss, o);
-  if (rc != GDM_OK) return rc;
-  rc = check_kinds("gdm_des_stats_batch_net_host", kind, B, dim, GDM_DES_DIST_BRANCH);
-  if (rc != GDM_OK) return rc;
-  if (math == 0)
-    stats_batch_host<MathLibm, des::AnyNode>(adj, B, dim, loc, scale, kind, queue_cap, seed, number_of_customers,
-                                             max_queue_cap, max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
-  else
-    stats_batch_host<des::MathPortable, des::AnyNode>(adj, B, dim, loc, scale, kind, queue_cap, seed,
-                                                      number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,
-                                                      has_gauss, cached_gauss, o);
-  return GDM_OK;
+  return stats_batch_host_entry<des::AnyNode>("gdm_des_stats_batch_net_host", DES_STATS_HOST_ARGS(kind));
 }

@@ -4,18 +4,20 @@
 // accumulators every Server / Source of the reference carries (SIMULATOR/simulation_v3.py:207-217, 280-281), from
 // which Sim.calculate_metrics (752-824) derives utilisation, waiting times, renege rates and L / LQ / W / WQ.
 //
-// Three kernels over one body (stats_sample): des_stats_kernel draws 'normal' only (des::NormalOnly, the bridges' nets);
-// des_stats_dist_kernel takes a kind per node (des::AnyDist: normal, exponential, uniform), its row staged into LDS;
-// des_stats_net_kernel takes the reference's 'queue' and 'branch' nodes as well (des::AnyNode), with the two per-node
-// arrays of that policy -- delayed departures, next departure time -- in LDS beside the kinds.
+// One kernel template over one body (stats_sample), instantiated for the three node policies of des_wave.h:
+// des_stats_kernel<NormalOnly> draws 'normal' only (the bridges' nets); des_stats_kernel<AnyDist> takes a kind per node
+// (normal, exponential, uniform), its row staged into LDS; des_stats_kernel<AnyNode> takes the reference's 'queue' and
+// 'branch' nodes as well, with the two per-node arrays of that policy -- delayed departures, next departure time -- in
+// LDS beside the kinds.  (Older texts call the three des_stats_kernel, des_stats_dist_kernel, des_stats_net_kernel.)
+// One launcher template (launch_stats) is behind the three entries.
 //
 // Mapping as in des_batch.hip, one WAVE per sample (des_wave.h is the shared prologue): all lanes stage the parameters,
 // build the routing tables and seed the node generators; lane 0 runs the chain; then ALL lanes write the (dim) rows
 // with ordinary vector stores.  No record arrays, no pack step.
 // LDS: the block of des_wave.h (16.2 KB) + eight 8-byte and one 4-byte accumulator per node (8.5 KB at the maximum of
 // 128 nodes) + the node generators when dim <= 15 (36.6 KB): 61.3 KB, below the 64 KB a workgroup may have; the kinds
-// of des_stats_dist_kernel add 512 B (61.8 KB), the kinds and node state of des_stats_net_kernel 2 KB (63.3 KB: the
-// static_assert below adds the blocks up).  Global memory holds what a sample cannot keep there: routing tables,
+// of des_stats_kernel<AnyDist> add 512 B (61.8 KB), the kinds and node state of des_stats_kernel<AnyNode> 2 KB (63.3 KB:
+// the static_assert below adds the blocks up).  Global memory holds what a sample cannot keep there: routing tables,
 // the FIFO ring of customer ids and, slot for slot beside it, the ring of their arrival times (workspace), and the
 // optional time-at-queue-length histogram (an output).
 // Bounds: every index the chain computes is checked in des_sim.h before it forms an address -- the arrival-time ring
@@ -31,9 +33,6 @@
 namespace {
 
 using des_wave::kMaxDim;
-typedef des::Sim<des::MathPortable, des::OutNone, des::NodeStats> StatSim;
-typedef des::Sim<des::MathPortable, des::OutNone, des::NodeStats, des::AnyDist> DistSim;
-typedef des::Sim<des::MathPortable, des::OutNone, des::NodeStats, des::AnyNode> NetSim;
 
 struct StatsLds {
   int64_t served[kMaxDim], reneges[kMaxDim], generated[kMaxDim];
@@ -43,14 +42,9 @@ struct StatsLds {
   int reason;
 };
 
-// the kinds of one sample (des_stats_dist_kernel only: des_wave::Lds is the layout of the kernels that have none)
-struct DistLds {
-  int32_t kind[kMaxDim];
-};
-
-static_assert(sizeof(des_wave::Lds) + sizeof(StatsLds) + sizeof(des_wave::NetLds) + 16 * 3 +
+static_assert(sizeof(des_wave::Lds) + sizeof(StatsLds) + des_wave::kMaxPolicyLds + 16 * 3 +
                       (size_t)des_wave::kLdsGenDim * DES_MT_N * 4 <= 64 * 1024,
-              "des_stats_net_kernel: static + dynamic LDS beyond a workgroup's 64 KB");
+              "des_stats_kernel<AnyNode>: static + dynamic LDS beyond a workgroup's 64 KB");
 
 // the (B, dim) and (B) outputs of the kernels, and the inputs they share
 struct StatsArgs {
@@ -141,7 +135,9 @@ __device__ __forceinline__ void stats_sample(SimT& s, des_wave::Lds& lds, StatsL
   }
 }
 
-// the parameter list both kernels share (kernel parameters stay plain __restrict__ pointers) and the StatsArgs of them
+// The kernels' parameter list and the StatsArgs of it, under the names the entries below use too.  Kernel parameters
+// stay plain __restrict__ pointers: with the struct as the parameter the compiler loses the no-alias facts and all
+// three kernels come out longer.
 #define DES_STATS_PARAMS                                                                                               \
   const double *__restrict__ adj, int dim, const double *__restrict__ loc, const double *__restrict__ scale,           \
       const int32_t *__restrict__ queue_cap, const int64_t *__restrict__ seed,                                         \
@@ -157,42 +153,25 @@ __device__ __forceinline__ void stats_sample(SimT& s, des_wave::Lds& lds, StatsL
   StatsArgs {                                                                                                          \
     adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,             \
         mt_has_gauss, mt_gauss, served, reneges, generated, max_queue, time_in_service, time_in_queue, queue_area,     \
-        arrival_time, clock, end_time, total_customers, events, n_records, stop_reason, queue_time, workspace          \
+        arrival_time, clock, end_time, total_customers, events, n_records, stop_reason, queue_time,                    \
+        (unsigned char*)workspace                                                                                      \
   }
 
-__global__ __launch_bounds__(GDM_WAVE) void des_stats_kernel(DES_STATS_PARAMS) {
+// One kernel per node policy (des_wave.h) over that body.  flatten: three kinds at three draw sites exceed the inliner's
+// budget, and a chain function left out of line takes the Sim by address -- 384 bytes of scratch per lane and a load
+// for every member; inlined whole there is no scratch.  The policy's block is staged before the prologue, whose first
+// barrier orders it before lane 0 reads it.  (With its kinds staged through AnyDist::stage and no longer in the kernel's
+// own body, des_stats_kernel<AnyDist> is scheduled differently from the kernel it replaces: 86 VGPRs for 104, 114
+// instructions more, and measured 0.7 to 1.5 % faster; DESIGN.md section 7, f19.  The other two are the same code.)
+template <class Policy>
+__global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_stats_kernel(
+    DES_STATS_PARAMS, const int32_t* __restrict__ kind) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];       // node generators when dim <= kLdsGenDim
   __shared__ des_wave::Lds lds;
   __shared__ StatsLds acc;
-  StatSim s;
-  stats_sample(s, lds, acc, s_dyn, DES_STATS_ARGS);
-}
-
-// flatten: three kinds at three draw sites exceed the inliner's budget, and a chain function left out of line takes the
-// Sim by address -- 384 bytes of scratch per lane and a load for every member; inlined whole there is no scratch
-__global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_stats_dist_kernel(
-    DES_STATS_PARAMS, const int32_t* __restrict__ kind) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-  __shared__ des_wave::Lds lds;
-  __shared__ StatsLds acc;
-  __shared__ DistLds dl;
-  for (int i = threadIdx.x; i < dim; i += GDM_WAVE) dl.kind[i] = kind[(int64_t)blockIdx.x * dim + i];
-  DistSim s;
-  s.dist.kind = dl.kind;
-  stats_sample(s, lds, acc, s_dyn, DES_STATS_ARGS);
-}
-
-// The statistics kernel with a kind per node that may be 'queue' or 'branch' (des::AnyNode).  flatten for the reason
-// des_stats_dist_kernel has it; the prologue's first barrier orders the staged kinds and the reset node state before
-// lane 0 reads them
-__global__ __launch_bounds__(GDM_WAVE) __attribute__((flatten)) void des_stats_net_kernel(
-    DES_STATS_PARAMS, const int32_t* __restrict__ kind) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-  __shared__ des_wave::Lds lds;
-  __shared__ StatsLds acc;
-  __shared__ des_wave::NetLds nl;
-  NetSim s;
-  des_wave::stage_net(s.dist, nl, kind, dim, blockIdx.x, threadIdx.x);
+  __shared__ typename Policy::Block pl;
+  des::Sim<des::MathPortable, des::OutNone, des::NodeStats, typename Policy::Dist> s;
+  Policy::stage(s.dist, pl, kind, dim, blockIdx.x, threadIdx.x);
   stats_sample(s, lds, acc, s_dyn, DES_STATS_ARGS);
 }
 
@@ -224,6 +203,22 @@ int check_stats_args(const char* who, const StatsArgs& a, int B, const int32_t* 
   return GDM_OK;
 }
 
+// what every entry does: the checks, then its policy's kernel (`kind` is nullptr where the policy has none)
+template <class Policy>
+int launch_stats(const char* who, const StatsArgs& a, int B, const int32_t* kind, size_t workspace_bytes,
+                 void* stream) {
+  const int rc = check_stats_args(who, a, B, kind, Policy::kHasKind, workspace_bytes);
+  if (rc != GDM_OK) return rc;
+  hipLaunchKernelGGL(des_stats_kernel<Policy>, dim3(B), dim3(GDM_WAVE), des_wave::lds_dyn_bytes(a.dim),
+                     (hipStream_t)stream, a.adj, a.dim, a.loc, a.scale, a.queue_cap, a.seed, a.number_of_customers,
+                     a.max_queue_cap, a.max_events, a.mt_key, a.mt_pos, a.mt_has_gauss, a.mt_gauss, a.served, a.reneges,
+                     a.generated, a.max_queue, a.time_in_service, a.time_in_queue, a.queue_area, a.arrival_time,
+                     a.clock, a.end_time, a.total_customers, a.events, a.n_records, a.stop_reason, a.queue_time,
+                     a.workspace, kind);
+  GDM_LAUNCH_OK(who);
+  return GDM_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t gdm_des_stats_workspace_bytes(int B, int dim, int max_queue_cap) {
@@ -236,73 +231,37 @@ extern "C" int64_t gdm_des_stats_workspace_bytes(int B, int dim, int max_queue_c
 extern "C" int gdm_des_stats_batch(const double* adj, int B, int dim, const double* loc, const double* scale,
                                    const int32_t* queue_cap, const int64_t* seed, const int64_t* number_of_customers,
                                    int max_queue_cap, int64_t max_events, uint32_t* mt_key, int32_t* mt_pos,
-                                   int32_t* has_gauss, double* cached_gauss, int64_t* served, int64_t* reneges,
+                                   int32_t* mt_has_gauss, double* mt_gauss, int64_t* served, int64_t* reneges,
                                    int64_t* generated, int32_t* max_queue, double* time_in_service,
                                    double* time_in_queue, double* queue_area, double* arrival_time, double* clock,
                                    double* end_time, int64_t* total_customers, int64_t* events, int64_t* n_records,
                                    int32_t* stop_reason, double* queue_time, void* workspace, size_t workspace_bytes,
                                    void* stream) {
-  const StatsArgs a{adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, mt_key,
-                    mt_pos, has_gauss, cached_gauss, served, reneges, generated, max_queue, time_in_service,
-                    time_in_queue, queue_area, arrival_time, clock, end_time, total_customers, events, n_records,
-                    stop_reason, queue_time, (unsigned char*)workspace};
-  const int rc = check_stats_args("gdm_des_stats_batch", a, B, nullptr, false, workspace_bytes);
-  if (rc != GDM_OK) return rc;
-  hipLaunchKernelGGL(des_stats_kernel, dim3(B), dim3(GDM_WAVE), des_wave::lds_dyn_bytes(dim), (hipStream_t)stream,
-                     adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,
-                     has_gauss, cached_gauss, served, reneges, generated, max_queue, time_in_service, time_in_queue,
-                     queue_area, arrival_time, clock, end_time, total_customers, events, n_records, stop_reason,
-                     queue_time, (unsigned char*)workspace);
-  GDM_LAUNCH_OK("gdm_des_stats_batch");
-  return GDM_OK;
+  return launch_stats<des_wave::NormalOnly>("gdm_des_stats_batch", DES_STATS_ARGS, B, nullptr, workspace_bytes, stream);
 }
 
 extern "C" int gdm_des_stats_batch_dist(const double* adj, int B, int dim, const double* loc, const double* scale,
                                         const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
                                         const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
-                                        uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
+                                        uint32_t* mt_key, int32_t* mt_pos, int32_t* mt_has_gauss, double* mt_gauss,
                                         int64_t* served, int64_t* reneges, int64_t* generated, int32_t* max_queue,
                                         double* time_in_service, double* time_in_queue, double* queue_area,
                                         double* arrival_time, double* clock, double* end_time,
                                         int64_t* total_customers, int64_t* events, int64_t* n_records,
                                         int32_t* stop_reason, double* queue_time, void* workspace,
                                         size_t workspace_bytes, void* stream) {
-  const StatsArgs a{adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, mt_key,
-                    mt_pos, has_gauss, cached_gauss, served, reneges, generated, max_queue, time_in_service,
-                    time_in_queue, queue_area, arrival_time, clock, end_time, total_customers, events, n_records,
-                    stop_reason, queue_time, (unsigned char*)workspace};
-  const int rc = check_stats_args("gdm_des_stats_batch_dist", a, B, kind, true, workspace_bytes);
-  if (rc != GDM_OK) return rc;
-  hipLaunchKernelGGL(des_stats_dist_kernel, dim3(B), dim3(GDM_WAVE), des_wave::lds_dyn_bytes(dim), (hipStream_t)stream,
-                     adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,
-                     has_gauss, cached_gauss, served, reneges, generated, max_queue, time_in_service, time_in_queue,
-                     queue_area, arrival_time, clock, end_time, total_customers, events, n_records, stop_reason,
-                     queue_time, (unsigned char*)workspace, kind);
-  GDM_LAUNCH_OK("gdm_des_stats_batch_dist");
-  return GDM_OK;
+  return launch_stats<des_wave::AnyDist>("gdm_des_stats_batch_dist", DES_STATS_ARGS, B, kind, workspace_bytes, stream);
 }
 
 extern "C" int gdm_des_stats_batch_net(const double* adj, int B, int dim, const double* loc, const double* scale,
                                        const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
                                        const int64_t* number_of_customers, int max_queue_cap, int64_t max_events,
-                                       uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
+                                       uint32_t* mt_key, int32_t* mt_pos, int32_t* mt_has_gauss, double* mt_gauss,
                                        int64_t* served, int64_t* reneges, int64_t* generated, int32_t* max_queue,
                                        double* time_in_service, double* time_in_queue, double* queue_area,
                                        double* arrival_time, double* clock, double* end_time,
                                        int64_t* total_customers, int64_t* events, int64_t* n_records,
                                        int32_t* stop_reason, double* queue_time, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-  const StatsArgs a{adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, mt_key,
-                    mt_pos, has_gauss, cached_gauss, served, reneges, generated, max_queue, time_in_service,
-                    time_in_queue, queue_area, arrival_time, clock, end_time, total_customers, events, n_records,
-                    stop_reason, queue_time, (unsigned char*)workspace};
-  const int rc = check_stats_args("gdm_des_stats_batch_net", a, B, kind, true, workspace_bytes);
-  if (rc != GDM_OK) return rc;
-  hipLaunchKernelGGL(des_stats_net_kernel, dim3(B), dim3(GDM_WAVE), des_wave::lds_dyn_bytes(dim), (hipStream_t)stream,
-                     adj, dim, loc, scale, queue_cap, seed, number_of_customers, max_queue_cap, max_events, mt_key, mt_pos,
-                     has_gauss, cached_gauss, served, reneges, generated, max_queue, time_in_service, time_in_queue,
-                     queue_area, arrival_time, clock, end_time, total_customers, events, n_records, stop_reason,
-                     queue_time, (unsigned char*)workspace, kind);
-  GDM_LAUNCH_OK("gdm_des_stats_batch_net");
-  return GDM_OK;
+  return launch_stats<des_wave::AnyNode>("gdm_des_stats_batch_net", DES_STATS_ARGS, B, kind, workspace_bytes, stream);
 }

@@ -2,7 +2,8 @@
 // the log-free statistics kernel): the workspace layout, the LDS block of one sample, and the prologue every lane takes
 // part in -- parameters to LDS, routing tables (one node per lane), the checks of the batch entries and the seeder's
 // draws (lane 0), init_genrand (one generator per lane) -- up to the point where lane 0 runs the chain, and the
-// write-back of the global generator behind it.  Device code only.
+// write-back of the global generator behind it; and the three node policies both files instantiate their kernel for
+// (NormalOnly, AnyDist, AnyNode: the Dist of des::Sim, the LDS block beside Lds, its staging).  Device code only.
 #pragma once
 #include "gdm_common.h"
 #include "des_sim.h"
@@ -46,9 +47,19 @@ struct Lds {
   int ok;
 };
 
+// the kinds of one sample for the kernels over des::AnyDist (512 B), staged by every lane of the wave.  Before the
+// prologue, whose first barrier orders it before any read.
+struct DistLds {
+  int32_t kind[kMaxDim];
+};
+__device__ inline void stage_dist(des::AnyDist& d, DistLds& n, const int32_t* __restrict__ kind, int dim, int b,
+                                  int lane) {
+  for (int i = lane; i < dim; i += GDM_WAVE) n.kind[i] = kind[(int64_t)b * dim + i];
+  d.kind = n.kind;
+}
+
 // the kinds and the node state of one sample for the kernels over des::AnyNode (2 KB), and their staging by every lane
-// of the wave: the kinds of sample b, no delayed departure, no departure scheduled yet.  Before the prologue, whose
-// first barrier orders it before any read.
+// of the wave: the kinds of sample b, no delayed departure, no departure scheduled yet.  Before the prologue, as above.
 struct NetLds {
   double next_departure[kMaxDim];
   int32_t kind[kMaxDim], delayed[kMaxDim];
@@ -61,6 +72,35 @@ __device__ inline void stage_net(des::AnyNode& d, NetLds& n, const int32_t* __re
   for (int i = lane; i < dim; i += GDM_WAVE) n.kind[i] = kind[(int64_t)b * dim + i];
   d.reset(dim, lane, GDM_WAVE);
 }
+
+// A node policy of the batch kernels, described once: the Dist it gives des::Sim, the LDS block it needs beside Lds,
+// how every lane stages that block before the prologue, and whether its entries take a (B, dim) `kind` array at all
+// (the kernels are instantiated per policy in des_batch.hip and des_stats.hip; NormalOnly ignores the pointer).
+struct NoLds {};
+struct NormalOnly {
+  typedef des::NormalOnly Dist;
+  typedef NoLds Block;
+  static constexpr bool kHasKind = false;
+  __device__ static void stage(Dist&, Block&, const int32_t*, int, int, int) {}
+};
+struct AnyDist {
+  typedef des::AnyDist Dist;
+  typedef DistLds Block;
+  static constexpr bool kHasKind = true;
+  __device__ static void stage(Dist& d, Block& n, const int32_t* __restrict__ kind, int dim, int b, int lane) {
+    stage_dist(d, n, kind, dim, b, lane);
+  }
+};
+struct AnyNode {
+  typedef des::AnyNode Dist;
+  typedef NetLds Block;
+  static constexpr bool kHasKind = true;
+  __device__ static void stage(Dist& d, Block& n, const int32_t* __restrict__ kind, int dim, int b, int lane) {
+    stage_net(d, n, kind, dim, b, lane);
+  }
+};
+constexpr size_t kMaxPolicyLds = sizeof(NetLds);        // the largest Block: what the kernels' LDS sums count
+static_assert(sizeof(DistLds) <= kMaxPolicyLds, "kMaxPolicyLds is not the largest policy block");
 
 // Every lane of the wave: binds the simulator's storage (dyn: the dynamic LDS, lds_dyn_bytes(dim); ws: the sample's
 // workspace), stages sample b and leaves the node generators seeded.  Returns whether the spec passed the checks of

@@ -1064,23 +1064,39 @@ def des_batch_workspace_bytes(b, dim, max_queue_cap):
     return n
 
 
-def _des_run_batch(who, kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, max_queue_cap,
-                   max_events, max_records, workspace_tensor, entry=None):
-    """``des_run_batch`` (kind None: gdm_des_run_batch), ``des_run_batch_dist`` (gdm_des_run_batch_dist) and
-    ``des_run_batch_net`` (``entry``: gdm_des_run_batch_net)."""
-    _need_gpu(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss,
-              *(() if kind is None else (kind,)))
+# (mode, policy) -> the C entry; the wrapper of a pair is des_run_<mode><policy>
+_DES_ENTRIES = {("batch", ""): "gdm_des_run_batch", ("batch", "_dist"): "gdm_des_run_batch_dist",
+                ("batch", "_net"): "gdm_des_run_batch_net", ("stats", ""): "gdm_des_stats_batch",
+                ("stats", "_dist"): "gdm_des_stats_batch_dist", ("stats", "_net"): "gdm_des_stats_batch_net"}
+
+
+def _des_inputs(mode, policy, kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss):
+    """What the six wrappers check alike: the device, (B, dim, dim) and the shape / dtype / contiguity of every input
+    (``kind`` is None where the policy has none).  Returns the wrapper's name for its messages, its C entry, B, dim and
+    the entry's arguments up to ``number_of_customers``."""
+    who = f"des_run_{mode}{policy}"
+    kinds = () if kind is None else (kind,)
+    _need_gpu(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *kinds)
     if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
         raise GdmError(f"{who}: adj must be (B, dim, dim)")
     b, dim = adj.shape[0], adj.shape[1]
     for t, shape, dt in ((adj, (b, dim, dim), torch.float64), (loc, (b, dim), torch.float64),
                          (scale, (b, dim), torch.float64), (queue_cap, (b, dim), torch.int32), (seed, (b,), torch.int64),
                          (customers, (b,), torch.int64), (mt_key, (b, 624), torch.int32), (mt_pos, (b,), torch.int32),
-                         (has_gauss, (b,), torch.int32), (gauss, (b,), torch.float64)) + \
-                        (() if kind is None else ((kind, (b, dim), torch.int32),)):
+                         (has_gauss, (b,), torch.int32), (gauss, (b,), torch.float64),
+                         *((k, (b, dim), torch.int32) for k in kinds)):
         if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
             raise GdmError(f"{who}: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
                            f"{tuple(t.shape)}")
+    head = (_p(adj), b, dim, _p(loc), _p(scale), *(_p(k) for k in kinds), _p(queue_cap), _p(seed), _p(customers))
+    return who, _DES_ENTRIES[mode, policy], b, dim, head
+
+
+def _des_run_batch(policy, kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss,
+                   max_queue_cap, max_events, max_records, workspace_tensor):
+    """``des_run_batch``, ``des_run_batch_dist`` and ``des_run_batch_net`` (policy "", "_dist", "_net")."""
+    who, entry, b, dim, head = _des_inputs("batch", policy, kind, adj, loc, scale, queue_cap, seed, customers, mt_key,
+                                           mt_pos, has_gauss, gauss)
     max_records = int(max_records)
     if max_records < 1:
         raise GdmError(f"{who}: the device simulator needs a record cap (max_records >= 1)")
@@ -1095,10 +1111,9 @@ def _des_run_batch(who, kind, adj, loc, scale, queue_cap, seed, customers, mt_ke
     stop = torch.empty(b, dtype=torch.int32, device=dev)
     need = des_batch_workspace_bytes(b, dim, max_queue_cap)
     ws = workspace(need, dev) if workspace_tensor is None else workspace_tensor
-    _call(entry or ("gdm_des_run_batch" if kind is None else "gdm_des_run_batch_dist"), _p(adj), b, dim, _p(loc), _p(scale),
-          *(() if kind is None else (_p(kind),)), _p(queue_cap), _p(seed), _p(customers),
-          int(max_queue_cap), int(max_events), max_records, _p(mt_key), _p(mt_pos), _p(has_gauss), _p(gauss), _p(value),
-          _p(event_id), _p(node), _p(rkind), n, _p(rec_ptr), _p(n_records), _p(stop), _p(ws), ws.numel(), _stream())
+    _call(entry, *head, int(max_queue_cap), int(max_events), max_records, _p(mt_key), _p(mt_pos), _p(has_gauss),
+          _p(gauss), _p(value), _p(event_id), _p(node), _p(rkind), n, _p(rec_ptr), _p(n_records), _p(stop), _p(ws),
+          ws.numel(), _stream())
     return value, event_id, node, rkind, rec_ptr, n_records, stop
 
 
@@ -1109,7 +1124,7 @@ def des_run_batch(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, h
     (uint32 bit patterns), mt_pos, has_gauss (B) i32, gauss (B) f64 are UPDATED IN PLACE.  Returns (value, event_id,
     node, kind, rec_ptr, n_records, stop_reason): the CSR record arrays hold B * max_records entries, of which
     rec_ptr[B] are records; nothing is read back."""
-    return _des_run_batch("des_run_batch", None, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss,
+    return _des_run_batch("", None, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss,
                           gauss, max_queue_cap, max_events, max_records, workspace_tensor)
 
 
@@ -1118,7 +1133,7 @@ def des_run_batch_dist(adj, loc, scale, kind, queue_cap, seed, customers, mt_key
     """``des_run_batch`` with a distribution kind per node (``kind`` (B,dim) int32 of DES_DIST_*; ``loc`` is not read
     where a node is exponential): ``gdm_des_run_batch_dist``, one launch + the pack step.  A kind outside 0..2 ends
     that sample with DES_STOP_ERROR; a sample that ends so keeps its generator state."""
-    return _des_run_batch("des_run_batch_dist", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
+    return _des_run_batch("_dist", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
                           has_gauss, gauss, max_queue_cap, max_events, max_records, workspace_tensor)
 
 
@@ -1138,23 +1153,11 @@ def des_stats_workspace_bytes(b, dim, max_queue_cap):
     return n
 
 
-def _des_run_stats(who, kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, max_queue_cap,
-                   max_events, histogram, workspace_tensor, entry=None):
-    """``des_run_stats`` (kind None: gdm_des_stats_batch), ``des_run_stats_dist`` (gdm_des_stats_batch_dist) and
-    ``des_run_stats_net`` (``entry``: gdm_des_stats_batch_net)."""
-    _need_gpu(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss,
-              *(() if kind is None else (kind,)))
-    if adj.dim() != 3 or adj.shape[1] != adj.shape[2]:
-        raise GdmError(f"{who}: adj must be (B, dim, dim)")
-    b, dim = adj.shape[0], adj.shape[1]
-    for t, shape, dt in ((adj, (b, dim, dim), torch.float64), (loc, (b, dim), torch.float64),
-                         (scale, (b, dim), torch.float64), (queue_cap, (b, dim), torch.int32), (seed, (b,), torch.int64),
-                         (customers, (b,), torch.int64), (mt_key, (b, 624), torch.int32), (mt_pos, (b,), torch.int32),
-                         (has_gauss, (b,), torch.int32), (gauss, (b,), torch.float64)) + \
-                        (() if kind is None else ((kind, (b, dim), torch.int32),)):
-        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
-            raise GdmError(f"{who}: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} "
-                           f"{tuple(t.shape)}")
+def _des_run_stats(policy, kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss,
+                   max_queue_cap, max_events, histogram, workspace_tensor):
+    """``des_run_stats``, ``des_run_stats_dist`` and ``des_run_stats_net`` (policy "", "_dist", "_net")."""
+    _who, entry, b, dim, head = _des_inputs("stats", policy, kind, adj, loc, scale, queue_cap, seed, customers, mt_key,
+                                            mt_pos, has_gauss, gauss)
     dev = adj.device
     out = {name: torch.empty((b, dim), dtype=dt, device=dev) for name, dt in DES_STATS_NODE_FIELDS}
     out.update({name: torch.empty(b, dtype=dt, device=dev) for name, dt in DES_STATS_SAMPLE_FIELDS})
@@ -1162,9 +1165,7 @@ def _des_run_stats(who, kind, adj, loc, scale, queue_cap, seed, customers, mt_ke
                          else None)
     need = des_stats_workspace_bytes(b, dim, max_queue_cap)
     ws = workspace(need, dev) if workspace_tensor is None else workspace_tensor
-    _call(entry or ("gdm_des_stats_batch" if kind is None else "gdm_des_stats_batch_dist"), _p(adj), b, dim, _p(loc), _p(scale),
-          *(() if kind is None else (_p(kind),)), _p(queue_cap), _p(seed), _p(customers),
-          int(max_queue_cap), int(max_events), _p(mt_key), _p(mt_pos), _p(has_gauss), _p(gauss),
+    _call(entry, *head, int(max_queue_cap), int(max_events), _p(mt_key), _p(mt_pos), _p(has_gauss), _p(gauss),
           *(_p(out[name]) for name, _dt in DES_STATS_NODE_FIELDS + DES_STATS_SAMPLE_FIELDS), _p(out["queue_time"]),
           _p(ws), ws.numel(), _stream())
     return out
@@ -1172,11 +1173,11 @@ def _des_run_stats(who, kind, adj, loc, scale, queue_cap, seed, customers, mt_ke
 
 def des_run_stats(adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *, max_queue_cap,
                   max_events=200000, histogram=False, workspace_tensor=None):
-    """B simulations in one launch, no records: the device tensors of ``des_run_batch`` in (generator states UPDATED
-    IN PLACE) -> dict of device tensors: DES_STATS_NODE_FIELDS (B,dim), DES_STATS_SAMPLE_FIELDS (B) and ``queue_time``
-    (B,dim,max_queue_cap+1) f64, the time spent at every queue length, or None without ``histogram``.  Nothing is read
-    back."""
-    return _des_run_stats("des_run_stats", None, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss,
+    """B simulations in one launch (``gdm_des_stats_batch``), no records: the device tensors of ``des_run_batch`` in
+    (generator states UPDATED IN PLACE) -> dict of device tensors: DES_STATS_NODE_FIELDS (B,dim),
+    DES_STATS_SAMPLE_FIELDS (B) and ``queue_time`` (B,dim,max_queue_cap+1) f64, the time spent at every queue length,
+    or None without ``histogram``.  Nothing is read back."""
+    return _des_run_stats("", None, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos, has_gauss,
                           gauss, max_queue_cap, max_events, histogram, workspace_tensor)
 
 
@@ -1188,7 +1189,7 @@ def des_run_stats_dist(adj, loc, scale, kind, queue_cap, seed, customers, mt_key
     """``des_run_stats`` with a distribution kind per node (``kind`` (B,dim) int32 of DES_DIST_*; ``loc`` is not read
     where a node is exponential): ``gdm_des_stats_batch_dist``, one launch.  A kind outside 0..2 ends that sample with
     DES_STOP_ERROR."""
-    return _des_run_stats("des_run_stats_dist", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
+    return _des_run_stats("_dist", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
                           has_gauss, gauss, max_queue_cap, max_events, histogram, workspace_tensor)
 
 
@@ -1200,9 +1201,8 @@ def des_run_stats_net(adj, loc, scale, kind, queue_cap, seed, customers, mt_key,
     """``des_run_stats_dist`` for nets with the reference's 'queue' and 'branch' nodes (``kind`` may be DES_DIST_QUEUE
     or DES_DIST_BRANCH; ``loc`` and ``scale`` are not read there): ``gdm_des_stats_batch_net``, one launch.  A kind
     outside 0..4 ends that sample with DES_STOP_ERROR.  The same workspace as ``des_run_stats``."""
-    return _des_run_stats("des_run_stats_net", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
-                          has_gauss, gauss, max_queue_cap, max_events, histogram, workspace_tensor,
-                          entry="gdm_des_stats_batch_net")
+    return _des_run_stats("_net", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
+                          has_gauss, gauss, max_queue_cap, max_events, histogram, workspace_tensor)
 
 
 def des_run_batch_net(adj, loc, scale, kind, queue_cap, seed, customers, mt_key, mt_pos, has_gauss, gauss, *,
@@ -1210,9 +1210,8 @@ def des_run_batch_net(adj, loc, scale, kind, queue_cap, seed, customers, mt_key,
     """``des_run_batch_dist`` for nets with 'queue' and 'branch' nodes (``des_run_stats_net``'s kinds):
     ``gdm_des_run_batch_net``, one launch + the pack step.  A kind outside 0..4 ends that sample with DES_STOP_ERROR; a
     sample that ends so keeps its generator state.  The same workspace as ``des_run_batch``."""
-    return _des_run_batch("des_run_batch_net", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
-                          has_gauss, gauss, max_queue_cap, max_events, max_records, workspace_tensor,
-                          entry="gdm_des_run_batch_net")
+    return _des_run_batch("_net", kind, adj, loc, scale, queue_cap, seed, customers, mt_key, mt_pos,
+                          has_gauss, gauss, max_queue_cap, max_events, max_records, workspace_tensor)
 
 
 def des_pack(n_records, rec_ptr, value, event_id, node, kind, max_records):

@@ -248,16 +248,16 @@ def sample_log(log, b):
     return out
 
 
-def run_batch_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, math=1, max_events=200000,
-                   max_records=5001, max_queue_cap=None, kind=None, net=False):
-    """``gdm_des_run_batch_host`` on numpy arrays: adj (B,dim,dim), loc, scale, queue_cap (B,dim), seed, customers (B).
-    math 0 = libm (the reference's bits), 1 = portable (the device's bits).  max_records 0 = no cap.  -> BatchLog of
-    numpy arrays; the record arrays are cut to rec_ptr[B].  ``kind`` (B,dim), the index into DIST_KINDS per node:
-    ``gdm_des_run_batch_dist_host``; None: every node is normal.  ``net=True`` (with ``kind``, the index into NODE_KINDS):
-    ``gdm_des_run_batch_net_host``, which also takes 'queue' and 'branch' nodes."""
+_HostInputs = collections.namedtuple("_HostInputs", "b dim adj state max_queue_cap policy head arrays")
+
+
+def _host_inputs(who, adj, loc, scale, queue_cap, seed, customers, states, max_queue_cap, math, max_events, kind, net):
+    """What both host runners do with their inputs: the arrays as the C entries read them, the generator states
+    ``state`` = (key, pos, has_gauss, gauss) as writable arrays, ``max_queue_cap`` (None: the largest capacity), the
+    entry's ``policy`` suffix ("", "_dist", "_net"), and ``head``, the entry's arguments up to ``max_events``, which
+    point into ``arrays``."""
     if net and kind is None:
-        raise ValueError("run_batch_host: net=True needs kind")
-    lib = _lib.load()
+        raise ValueError(f"{who}: net=True needs kind")
     adj = np.ascontiguousarray(adj, dtype=np.float64)
     b, dim = adj.shape[0], adj.shape[1]
     assert adj.shape == (b, dim, dim), adj.shape
@@ -266,16 +266,30 @@ def run_batch_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, 
     queue_cap = np.ascontiguousarray(queue_cap, dtype=np.int32).reshape(b, dim)
     seed = np.ascontiguousarray(seed, dtype=np.int64).reshape(b)
     customers = np.ascontiguousarray(customers, dtype=np.int64).reshape(b)
-    key, pos, has, gauss = (np.array(a) for a in pack_states(states, b))
-    max_events, max_records = int(max_events), int(max_records)
+    state = tuple(np.array(a) for a in pack_states(states, b))
     if max_queue_cap is None:
         max_queue_cap = max(1, int(queue_cap.max()))
-    if kind is None:
-        name, kinds = "gdm_des_run_batch_host", ()
-    else:
-        kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(b, dim)
-        name, kinds = "gdm_des_run_batch_net_host" if net else "gdm_des_run_batch_dist_host", (kind.ctypes.data,)
-    entry = getattr(lib, name)
+    kinds = () if kind is None else (np.ascontiguousarray(kind, dtype=np.int32).reshape(b, dim),)
+    arrays = (adj, loc, scale, *kinds, queue_cap, seed, customers)
+    head = (adj.ctypes.data, b, dim, *(a.ctypes.data for a in arrays[1:]), int(max_queue_cap), int(math),
+            int(max_events))
+    policy = "" if kind is None else "_net" if net else "_dist"
+    return _HostInputs(b, dim, adj, state, int(max_queue_cap), policy, head, arrays)
+
+
+def run_batch_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, math=1, max_events=200000,
+                   max_records=5001, max_queue_cap=None, kind=None, net=False):
+    """``gdm_des_run_batch_host`` on numpy arrays: adj (B,dim,dim), loc, scale, queue_cap (B,dim), seed, customers (B).
+    math 0 = libm (the reference's bits), 1 = portable (the device's bits).  max_records 0 = no cap.  -> BatchLog of
+    numpy arrays; the record arrays are cut to rec_ptr[B].  ``kind`` (B,dim), the index into DIST_KINDS per node:
+    ``gdm_des_run_batch_dist_host``; None: every node is normal.  ``net=True`` (with ``kind``, the index into NODE_KINDS):
+    ``gdm_des_run_batch_net_host``, which also takes 'queue' and 'branch' nodes."""
+    x = _host_inputs("run_batch_host", adj, loc, scale, queue_cap, seed, customers, states, max_queue_cap, math,
+                     max_events, kind, net)
+    b, dim, (key, pos, has, gauss) = x.b, x.dim, x.state
+    max_events, max_records = int(max_events), int(max_records)
+    name = f"gdm_des_run_batch{x.policy}_host"
+    entry = getattr(_lib.load(), name)
     per = 4 * max_events + 4 * dim + 64                    # at most four records per processed event
     cap = b * (min(per, max_records) if max_records > 0 else per)
     while True:
@@ -283,10 +297,9 @@ def run_batch_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, 
         node, rkind = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
         rec_ptr, n_rec, stop = np.zeros(b + 1, dtype=np.int64), np.zeros(b, dtype=np.int64), np.zeros(b, dtype=np.int32)
         k, p, h, g = key.copy(), pos.copy(), has.copy(), gauss.copy()
-        rc = entry(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data, *kinds, queue_cap.ctypes.data,
-                   seed.ctypes.data, customers.ctypes.data, int(max_queue_cap), int(math), max_events, max_records,
-                   k.ctypes.data, p.ctypes.data, h.ctypes.data, g.ctypes.data, value.ctypes.data, eid.ctypes.data,
-                   node.ctypes.data, rkind.ctypes.data, cap, rec_ptr.ctypes.data, n_rec.ctypes.data, stop.ctypes.data)
+        rc = entry(*x.head, max_records, k.ctypes.data, p.ctypes.data, h.ctypes.data, g.ctypes.data, value.ctypes.data,
+                   eid.ctypes.data, node.ctypes.data, rkind.ctypes.data, cap, rec_ptr.ctypes.data, n_rec.ctypes.data,
+                   stop.ctypes.data)
         if rc == -3 and int(rec_ptr[-1]) > cap:            # GDM_EWORKSPACE: again from the ORIGINAL generator states
             cap = int(rec_ptr[-1])
             continue
@@ -295,25 +308,23 @@ def run_batch_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, 
         return BatchLog(value[:n], eid[:n], node[:n], rkind[:n], rec_ptr, n_rec, stop, k, p, h, g)
 
 
+def _one_seed(sp, name):
+    if np.asarray(sp.seeds).size != 1:
+        raise ValueError(f"{name}: one seed (one run) per spec")
+
+
+def _normal_row(sp):
+    """``dist_row`` of a spec for the entries without kinds: every node 'normal'."""
+    if any(d[0] != "normal" for d in sp.distributions):
+        raise NotImplementedError("run_batch: the deterministic core implements 'normal' distributions only")
+    _one_seed(sp, "run_batch")
+    return dist_row(sp.distributions)
+
+
 def spec_arrays(specs):
     """[DesSpec] of one size -> (adj, loc, scale, queue_cap, seed, customers) numpy arrays with a leading B."""
-    if len(specs) == 0:
-        raise ValueError("run_batch: no specs")
-    dim = np.asarray(specs[0].sim_matrix).shape[0]
-    for sp in specs:
-        if np.asarray(sp.sim_matrix).shape != (dim, dim) or len(sp.distributions) != dim or len(sp.queue_list) != dim:
-            raise ValueError("run_batch: every spec of a batch must have the same number of nodes")
-        if any(d[0] != "normal" for d in sp.distributions):
-            raise NotImplementedError("run_batch: the deterministic core implements 'normal' distributions only")
-        if np.asarray(sp.seeds).size != 1:
-            raise ValueError("run_batch: one seed (one run) per spec")
-    adj = np.ascontiguousarray([np.asarray(sp.sim_matrix, dtype=np.float64) for sp in specs])
-    loc = np.ascontiguousarray([[float(d[1]) for d in sp.distributions] for sp in specs], dtype=np.float64)
-    scale = np.ascontiguousarray([[float(d[2]) for d in sp.distributions] for sp in specs], dtype=np.float64)
-    qcap = np.ascontiguousarray([list(sp.queue_list) for sp in specs], dtype=np.int32)
-    seed = np.ascontiguousarray([int(np.asarray(sp.seeds).reshape(-1)[0]) for sp in specs], dtype=np.int64)
-    customers = np.ascontiguousarray([int(sp.num_customers) for sp in specs], dtype=np.int64)
-    return adj, loc, scale, qcap, seed, customers
+    adj, _kind, *rest = _spec_arrays(specs, "run_batch", _normal_row)
+    return (adj, *rest)
 
 
 DIST_KINDS = ("normal", "exponential", "uniform")     # GDM_DES_DIST_*: the index is the kind
@@ -338,19 +349,17 @@ def dist_row(distributions, who="dist_arrays", kinds=DIST_KINDS):
     return kind, loc, scale
 
 
-def dist_arrays(specs, who="run_stats", kinds=DIST_KINDS):
-    """``spec_arrays`` for specs whose nodes may be any of DIST_KINDS -> (adj, kind, loc, scale, queue_cap, seed,
-    customers) numpy arrays with a leading B; kind (B,dim) int32, the index into DIST_KINDS."""
+def _spec_arrays(specs, name, row):
+    """The arrays of ``spec_arrays`` and ``dist_arrays``; ``name`` heads the messages, ``row`` checks a spec of the
+    right size and returns its ``dist_row``."""
     if len(specs) == 0:
-        raise ValueError("run_stats: no specs")
+        raise ValueError(f"{name}: no specs")
     dim = np.asarray(specs[0].sim_matrix).shape[0]
     rows = []
     for sp in specs:
         if np.asarray(sp.sim_matrix).shape != (dim, dim) or len(sp.distributions) != dim or len(sp.queue_list) != dim:
-            raise ValueError("run_stats: every spec of a batch must have the same number of nodes")
-        if np.asarray(sp.seeds).size != 1:
-            raise ValueError("run_stats: one seed (one run) per spec")
-        rows.append(dist_row(sp.distributions, who, kinds))
+            raise ValueError(f"{name}: every spec of a batch must have the same number of nodes")
+        rows.append(row(sp))
     adj = np.ascontiguousarray([np.asarray(sp.sim_matrix, dtype=np.float64) for sp in specs])
     kind = np.ascontiguousarray([r[0] for r in rows], dtype=np.int32)
     loc = np.ascontiguousarray([r[1] for r in rows], dtype=np.float64)
@@ -361,22 +370,30 @@ def dist_arrays(specs, who="run_stats", kinds=DIST_KINDS):
     return adj, kind, loc, scale, qcap, seed, customers
 
 
+def dist_arrays(specs, who="run_stats", kinds=DIST_KINDS):
+    """``spec_arrays`` for specs whose nodes may be any of DIST_KINDS -> (adj, kind, loc, scale, queue_cap, seed,
+    customers) numpy arrays with a leading B; kind (B,dim) int32, the index into DIST_KINDS."""
+    def row(sp):
+        _one_seed(sp, "run_stats")
+        return dist_row(sp.distributions, who, kinds)
+
+    return _spec_arrays(specs, "run_stats", row)
+
+
 def net_arrays(specs, who="net_arrays"):
     """``dist_arrays`` for specs whose nodes may be any of NODE_KINDS: ``['queue']`` and ``['branch']`` get kind 3 and 4,
     loc 0 and scale 0 (neither is read).  For the entries taken with ``net=True``."""
     return dist_arrays(specs, who, NODE_KINDS)
 
 
-def run_batch_device(adj, loc, scale, queue_cap, seed, customers, states=None, *, device, max_events=200000,
-                     max_records=5001, max_queue_cap=None, workspace_tensor=None, kind=None, net=False):
-    """``gdm_des_run_batch``: the arrays of ``run_batch_host`` (numpy, or device tensors that stay where they are --
-    ``adj`` straight from ``ops.des_routing``) -> BatchLog of device tensors.  Nothing is read back.  ``kind`` as in
-    ``run_batch_host``: ``gdm_des_run_batch_dist``, the kernel that draws normal, exponential and uniform nodes;
-    ``net=True``: ``gdm_des_run_batch_net``, the kernel that also takes 'queue' and 'branch' nodes."""
+def _device_inputs(who, adj, loc, scale, queue_cap, seed, customers, states, device, max_queue_cap, kind, net):
+    """The upload of both device runners: numpy arrays go to ``device``, device tensors stay where they are; generator
+    states as ``pack_states`` takes them, or the four tensors (mt_key (B,624) i32, mt_pos, has_gauss (B) i32, gauss (B)
+    f64) already on the device (``ops.des_draws``), updated in place like every state the kernel is given.  -> (the
+    tensors in the order the ops wrappers take them, the four state tensors among them, max_queue_cap)."""
     if net and kind is None:
-        raise ValueError("run_batch_device: net=True needs kind")
+        raise ValueError(f"{who}: net=True needs kind")
     import torch
-    from . import ops
     dev = torch.device(device)
 
     def up(a, dt):
@@ -387,26 +404,36 @@ def run_batch_device(adj, loc, scale, queue_cap, seed, customers, states=None, *
     b = adj.shape[0]
     if max_queue_cap is None:
         if torch.is_tensor(queue_cap):
-            raise ValueError("run_batch_device: pass max_queue_cap with a device queue_cap (it sizes the workspace)")
+            raise ValueError(f"{who}: pass max_queue_cap with a device queue_cap (it sizes the workspace)")
         max_queue_cap = max(1, int(np.asarray(queue_cap).max()))
     if isinstance(states, (tuple, list)) and len(states) == 4 and torch.is_tensor(states[0]):
-        # (mt_key (B,624) i32, mt_pos, has_gauss (B) i32, gauss (B) f64) already on the device (``ops.des_draws``):
-        # updated in place like every state the kernel is given
-        k, p, h, g = (up(t, dt) for t, dt in zip(states, (torch.int32, torch.int32, torch.int32, torch.float64)))
+        state = tuple(up(t, dt) for t, dt in zip(states, (torch.int32, torch.int32, torch.int32, torch.float64)))
     else:
         key, pos, has, gauss = pack_states(states, b)
-        k, p, h, g = (up(key.view(np.int32), torch.int32), up(pos, torch.int32), up(has, torch.int32),
-                      up(gauss, torch.float64))
-    tail = (up(queue_cap, torch.int32), up(seed, torch.int64), up(customers, torch.int64), k, p, h, g)
+        state = (up(key.view(np.int32), torch.int32), up(pos, torch.int32), up(has, torch.int32),
+                 up(gauss, torch.float64))
+    args = (up(adj, torch.float64), up(loc, torch.float64), up(scale, torch.float64),
+            *(() if kind is None else (up(kind, torch.int32),)), up(queue_cap, torch.int32), up(seed, torch.int64),
+            up(customers, torch.int64), *state)
+    return args, state, max_queue_cap
+
+
+def run_batch_device(adj, loc, scale, queue_cap, seed, customers, states=None, *, device, max_events=200000,
+                     max_records=5001, max_queue_cap=None, workspace_tensor=None, kind=None, net=False):
+    """``gdm_des_run_batch``: the arrays of ``run_batch_host`` (numpy, or device tensors that stay where they are --
+    ``adj`` straight from ``ops.des_routing``) -> BatchLog of device tensors.  Nothing is read back.  ``kind`` as in
+    ``run_batch_host``: ``gdm_des_run_batch_dist``, the kernel that draws normal, exponential and uniform nodes;
+    ``net=True``: ``gdm_des_run_batch_net``, the kernel that also takes 'queue' and 'branch' nodes."""
+    from . import ops
+    args, state, max_queue_cap = _device_inputs("run_batch_device", adj, loc, scale, queue_cap, seed, customers, states,
+                                                device, max_queue_cap, kind, net)
     kw = dict(max_queue_cap=max_queue_cap, max_events=max_events, max_records=max_records,
               workspace_tensor=workspace_tensor)
     if kind is None:
-        out = ops.des_run_batch(up(adj, torch.float64), up(loc, torch.float64), up(scale, torch.float64), *tail, **kw)
+        out = ops.des_run_batch(*args, **kw)
     else:
-        entry = ops.des_run_batch_net if net else ops.des_run_batch_dist
-        out = entry(up(adj, torch.float64), up(loc, torch.float64), up(scale, torch.float64), up(kind, torch.int32),
-                    *tail, **kw)
-    return BatchLog(*out, k, p, h, g)
+        out = (ops.des_run_batch_net if net else ops.des_run_batch_dist)(*args, **kw)
+    return BatchLog(*out, *state)
 
 
 def batch_log_to(log, device):
@@ -492,36 +519,18 @@ def run_stats_host(adj, loc, scale, queue_cap, seed, customers, states=None, *, 
     of numpy arrays.  math 0 = libm (the reference's bits), 1 = portable (the device's bits).  ``kind`` (B,dim), the
     index into DIST_KINDS per node: ``gdm_des_stats_batch_dist_host``; None: every node is normal.  ``net=True`` (with
     ``kind``, the index into NODE_KINDS): ``gdm_des_stats_batch_net_host``, which also takes 'queue' and 'branch' nodes."""
-    if net and kind is None:
-        raise ValueError("run_stats_host: net=True needs kind")
-    lib = _lib.load()
-    adj = np.ascontiguousarray(adj, dtype=np.float64)
-    b, dim = adj.shape[0], adj.shape[1]
-    assert adj.shape == (b, dim, dim), adj.shape
-    loc = np.ascontiguousarray(loc, dtype=np.float64).reshape(b, dim)
-    scale = np.ascontiguousarray(scale, dtype=np.float64).reshape(b, dim)
-    queue_cap = np.ascontiguousarray(queue_cap, dtype=np.int32).reshape(b, dim)
-    seed = np.ascontiguousarray(seed, dtype=np.int64).reshape(b)
-    customers = np.ascontiguousarray(customers, dtype=np.int64).reshape(b)
-    k, p, h, g = (np.array(a) for a in pack_states(states, b))
-    if max_queue_cap is None:
-        max_queue_cap = max(1, int(queue_cap.max()))
+    x = _host_inputs("run_stats_host", adj, loc, scale, queue_cap, seed, customers, states, max_queue_cap, math,
+                     max_events, kind, net)
+    b, dim, (k, p, h, g) = x.b, x.dim, x.state
     out = {n: np.zeros((b, dim), dtype=_STATS_DTYPES[n]) for n in STATS_NODE_FIELDS}
     out.update({n: np.zeros(b, dtype=_STATS_DTYPES[n]) for n in STATS_SAMPLE_FIELDS})
-    hist = np.zeros((b, dim, int(max_queue_cap) + 1), dtype=np.float64) if histogram else None
-    tail = (queue_cap.ctypes.data, seed.ctypes.data, customers.ctypes.data, int(max_queue_cap), int(math),
-            int(max_events), k.ctypes.data, p.ctypes.data, h.ctypes.data, g.ctypes.data,
-            *(out[n].ctypes.data for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS),
-            hist.ctypes.data if histogram else None)
-    if kind is None:
-        rc = lib.gdm_des_stats_batch_host(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data, *tail)
-        _lib.check(rc, "gdm_des_stats_batch_host")
-    else:
-        kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(b, dim)
-        name = "gdm_des_stats_batch_net_host" if net else "gdm_des_stats_batch_dist_host"
-        rc = getattr(lib, name)(adj.ctypes.data, b, dim, loc.ctypes.data, scale.ctypes.data, kind.ctypes.data, *tail)
-        _lib.check(rc, name)
-    is_source = np.diagonal(adj, axis1=1, axis2=2) > 0
+    hist = np.zeros((b, dim, x.max_queue_cap + 1), dtype=np.float64) if histogram else None
+    name = f"gdm_des_stats_batch{x.policy}_host"
+    rc = getattr(_lib.load(), name)(*x.head, k.ctypes.data, p.ctypes.data, h.ctypes.data, g.ctypes.data,
+                                    *(out[n].ctypes.data for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS),
+                                    hist.ctypes.data if histogram else None)
+    _lib.check(rc, name)
+    is_source = np.diagonal(x.adj, axis1=1, axis2=2) > 0
     return BatchStats(*(out[n] for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS), hist, is_source, k, p, h, g)
 
 
@@ -532,39 +541,17 @@ def run_stats_device(adj, loc, scale, queue_cap, seed, customers, states=None, *
     ``run_stats_host(math=1)``.  Nothing is read back.  ``kind`` as in ``run_stats_host``: ``gdm_des_stats_batch_dist``,
     the kernel that draws normal, exponential and uniform nodes; ``net=True``: ``gdm_des_stats_batch_net``, the kernel
     that also takes 'queue' and 'branch' nodes."""
-    if net and kind is None:
-        raise ValueError("run_stats_device: net=True needs kind")
     import torch
     from . import ops
-    dev = torch.device(device)
-
-    def up(a, dt):
-        if torch.is_tensor(a):
-            return a.to(device=dev, dtype=dt).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(dt).contiguous()
-
-    b = adj.shape[0]
-    if max_queue_cap is None:
-        if torch.is_tensor(queue_cap):
-            raise ValueError("run_stats_device: pass max_queue_cap with a device queue_cap (it sizes the workspace)")
-        max_queue_cap = max(1, int(np.asarray(queue_cap).max()))
-    if isinstance(states, (tuple, list)) and len(states) == 4 and torch.is_tensor(states[0]):
-        k, p, h, g = (up(t, dt) for t, dt in zip(states, (torch.int32, torch.int32, torch.int32, torch.float64)))
-    else:
-        key, pos, has, gauss = pack_states(states, b)
-        k, p, h, g = (up(key.view(np.int32), torch.int32), up(pos, torch.int32), up(has, torch.int32),
-                      up(gauss, torch.float64))
-    adj = up(adj, torch.float64)
-    tail = (up(queue_cap, torch.int32), up(seed, torch.int64), up(customers, torch.int64), k, p, h, g)
+    args, state, max_queue_cap = _device_inputs("run_stats_device", adj, loc, scale, queue_cap, seed, customers, states,
+                                                device, max_queue_cap, kind, net)
     kw = dict(max_queue_cap=max_queue_cap, max_events=max_events, histogram=histogram, workspace_tensor=workspace_tensor)
     if kind is None:
-        out = ops.des_run_stats(adj, up(loc, torch.float64), up(scale, torch.float64), *tail, **kw)
+        out = ops.des_run_stats(*args, **kw)
     else:
-        entry = ops.des_run_stats_net if net else ops.des_run_stats_dist
-        out = entry(adj, up(loc, torch.float64), up(scale, torch.float64), up(kind, torch.int32), *tail, **kw)
-    is_source = torch.diagonal(adj, dim1=1, dim2=2) > 0
-    return BatchStats(*(out[n] for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS), out["queue_time"], is_source, k, p, h,
-                      g)
+        out = (ops.des_run_stats_net if net else ops.des_run_stats_dist)(*args, **kw)
+    is_source = torch.diagonal(args[0], dim1=1, dim2=2) > 0
+    return BatchStats(*(out[n] for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS), out["queue_time"], is_source, *state)
 
 
 def run_stats(specs, *, device=None, max_events=200000, states=None, histogram=False):

@@ -8,10 +8,11 @@ B = 256 and B = 48).  Per B, after one warm-up pass, seven passes that alternate
 the same generator states, timed with HIP events on the stream.  Every entry is called through ctypes on preallocated
 outputs, the parent's library and this tree's alike:
 
-    parent/<entry>, parent_again/<entry>   the four existing entries -- gdm_des_stats_batch, gdm_des_stats_batch_dist
-                      (kinds 0), gdm_des_run_batch, gdm_des_run_batch_dist (kinds 0) -- of the library at PATH (a
-                      build of the parent commit), when given, measured twice in the same passes: the difference of
-                      the two medians is the spread a difference to this tree is read against
+    parent/<entry>, parent_again/<entry>   the six device entries -- gdm_des_stats_batch, gdm_des_stats_batch_dist and
+                      gdm_des_stats_batch_net (kinds 0), gdm_des_run_batch, gdm_des_run_batch_dist and
+                      gdm_des_run_batch_net (kinds 0) -- of the library at PATH (a build of the parent commit), when
+                      given, measured twice in the same passes: the difference of the two medians is the spread a
+                      difference to this tree is read against
     tree/<entry>      the same entries of this tree
     tree/gdm_des_stats_batch_dist_expon, tree/gdm_des_stats_batch_net_expon, ..._run_batch_...   the _net kernels on
                       all-exponential kinds (scale = the node's mean) beside the _dist kernels on the same inputs,
@@ -36,7 +37,8 @@ dev = torch.device("cuda")
 d = np.load(os.path.join(ROOT, "tests/golden/des_prologue_rng.npz"))
 PASSES = 7
 MAX_RECORDS = 5001
-EXISTING = ("gdm_des_stats_batch", "gdm_des_stats_batch_dist", "gdm_des_run_batch", "gdm_des_run_batch_dist")
+EXISTING = ("gdm_des_stats_batch", "gdm_des_stats_batch_dist", "gdm_des_stats_batch_net",
+            "gdm_des_run_batch", "gdm_des_run_batch_dist", "gdm_des_run_batch_net")
 STAT_FIELDS = tuple(n for n, _dt in ops.DES_STATS_NODE_FIELDS + ops.DES_STATS_SAMPLE_FIELDS)
 LOG_FIELDS = ("value", "event_id", "node", "kind", "rec_ptr", "n_records", "stop_reason")
 args = sys.argv[1:]
@@ -141,7 +143,7 @@ def measure(b):
     zeros = torch.zeros((b, x.dim), dtype=torch.int32, device=dev)
     ones = torch.ones((b, x.dim), dtype=torch.int32, device=dev)
     expon = (x.head[0], x.head[1], x.head[1])                                     # scale = the mean; loc is not read
-    kinds = {name: zeros if name.endswith("_dist") else None for name in EXISTING}
+    kinds = {name: zeros if name.endswith(("_dist", "_net")) else None for name in EXISTING}
 
     # what is timed against what computes the same bytes
     want = {}
