@@ -167,6 +167,11 @@ for _mode in ("run", "stats"):
                 _I, _DES_NET + (_DES_KIND if _policy else []) + _DES_SPEC + (_DES_MATH if _host else []) +
                 _DES_CAPS[_mode] + _DES_STATE + _DES_OUT[_mode] + ([] if _host else _DES_DEVICE))
 
+# the host snapshot entry (des::SnapStats): the _net statistics list with snap_customers (B, S) and S in the place of
+# number_of_customers
+SIGNATURES["gdm_des_stats_batch_snap_host"] = (
+    _I, _DES_NET + _DES_KIND + [_P, _P, _P, _I, _I] + _DES_MATH + _DES_CAPS["stats"] + _DES_STATE + _DES_OUT["stats"])
+
 _lock = threading.Lock()
 _lib = None
 

@@ -8,7 +8,8 @@
 // instantiations: gdm_des_run (libm math, numpy's bits), gdm_des_run_batch_host (the batch mirror),
 // gdm_des_run_batch_dist_host (the batch mirror with a distribution kind per node, des::AnyDist) and
 // gdm_des_run_batch_net_host (with the reference's 'queue' and 'branch' nodes as well, des::AnyNode); the statistics
-// entries gdm_des_stats_batch[_dist|_net]_host likewise.
+// entries gdm_des_stats_batch[_dist|_net]_host likewise, and gdm_des_stats_batch_snap_host, the statistics at several
+// customer counts of one run (des::SnapStats).
 //
 // HOST code ("a deterministic, event-count-capped C++ DES core"): the simulation is one
 // dependent event chain per sample (des_batch.hip runs a batch of them, one wave each).  What makes it a drop-in is that it reproduces the reference's
@@ -313,6 +314,73 @@ int stats_batch_host_entry(const char* who, const double* adj, int B, int dim, c
   return GDM_OK;
 }
 
+// The statistics mode with snapshots at customer counts (des::SnapStats over des::AnyNode, the superset of the node
+// policies), one sample after the other.  The accumulators are scratch; `o` holds the
+// (B, S, dim), (B, S) and (B, S, dim, max_queue_cap + 1) snapshot arrays, o.stop_reason the (B, S) stop reasons.
+template <class Math>
+void stats_snap_batch_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                           const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
+                           const int64_t* snap_customers, int S, int max_queue_cap, int64_t max_events, uint32_t* mt_key,
+                           int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss, const StatsOut& o) {
+  HostSim<Math, des::OutNone, des::SnapStats, des::AnyNode> h(dim, max_queue_cap);
+  NodeState<des::AnyNode> nodes(dim);
+  std::vector<double> atime((size_t)dim * max_queue_cap), f64((size_t)5 * dim);
+  std::vector<int64_t> i64((size_t)3 * dim);
+  std::vector<int32_t> max_queue(dim);
+  const int64_t hist_stride = (int64_t)max_queue_cap + 1;
+  for (int b = 0; b < B; ++b) {
+    des::Sim<Math, des::OutNone, des::SnapStats, des::AnyNode>& s = h.s;
+    const size_t row = (size_t)b * dim, srow = (size_t)b * S, rows = srow * dim;
+    bind_kind(s.dist, kind, row);
+    nodes.bind(s.dist, dim);
+    s.out_cap = INT64_MAX;
+    s.max_records = 0;
+    s.draws_left = (int64_t)DES_DRAW_FACTOR * (max_events + dim + 1);
+    s.loc = loc + row;
+    s.scale = scale + row;
+    s.qcap = queue_cap + row;
+    des::SnapStats& st = s.stats;
+    st.served = i64.data();
+    st.reneges = i64.data() + dim;
+    st.generated = i64.data() + 2 * (size_t)dim;
+    st.max_queue = max_queue.data();
+    st.time_in_service = f64.data();
+    st.time_in_queue = f64.data() + dim;
+    st.queue_area = f64.data() + 2 * (size_t)dim;
+    st.arrival_time = f64.data() + 3 * (size_t)dim;
+    st.last_change = f64.data() + 4 * (size_t)dim;
+    st.atime = atime.data();
+    st.ring_stride = max_queue_cap;
+    st.hist_stride = hist_stride;
+    st.snap_customers = snap_customers + srow;
+    st.n_snap = S;
+    st.dim = dim;
+    st.is_source = s.is_source;
+    st.next = 0;
+    st.o = des::SnapOut{o.served + rows, o.reneges + rows, o.generated + rows, o.max_queue + rows,
+                        o.time_in_service + rows, o.time_in_queue + rows, o.queue_area + rows, o.arrival_time + rows,
+                        o.clock + srow, o.end_time + srow, o.total_customers + srow, o.events + srow, o.n_records + srow,
+                        o.stop_reason + srow, o.queue_time ? o.queue_time + rows * hist_stride : nullptr};
+    st.queue_time = o.queue_time ? st.o.queue_time + (size_t)(S - 1) * dim * hist_stride : nullptr;
+    st.reset(dim, 0, 1);
+    if (st.queue_time) std::memset(st.queue_time, 0, sizeof(double) * (size_t)dim * hist_stride);
+    int reason = DES_STOP_ERROR;
+    if (s.spec_ok(seed[b], mt_pos[b])) {                  // (the rows were checked before anything ran)
+      h.prepare(adj + row * dim, s.loc, s.scale, s.qcap, (uint32_t)seed[b], mt_key + (size_t)b * DES_MT_N, mt_pos[b],
+                has_gauss[b], cached_gauss[b]);
+      reason = s.run(snap_customers[srow + S - 1], max_events);
+    }
+    const bool keep = reason != DES_STOP_ERROR;           // a sample that errors keeps its generator as it came
+    if (keep) {
+      std::memcpy(mt_key + (size_t)b * DES_MT_N, s.global_key, DES_MT_N * sizeof(uint32_t));
+      mt_pos[b] = s.pos[dim];
+      has_gauss[b] = s.has_gauss[dim];
+      cached_gauss[b] = s.gauss[dim];
+    }
+    st.flush(reason, s.total_customers, s.clock, s.n_out);
+  }
+}
+
 }  // namespace
 
 extern "C" int gdm_des_run(const double* adj, int dim, const double* loc, const double* scale, const int32_t* queue_cap,
@@ -489,4 +557,35 @@ extern "C" int gdm_des_stats_batch_net_host(const double* adj, int B, int dim, c
                                             int64_t* events, int64_t* n_records, int32_t* stop_reason,
                                             double* queue_time) {
   return stats_batch_host_entry<des::AnyNode>("gdm_des_stats_batch_net_host", DES_STATS_HOST_ARGS(kind));
+}
+
+extern "C" int gdm_des_stats_batch_snap_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                             const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
+                                             const int64_t* snap_customers, int S, int max_queue_cap, int math,
+                                             int64_t max_events, uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss,
+                                             double* cached_gauss, int64_t* served, int64_t* reneges,
+                                             int64_t* generated, int32_t* max_queue, double* time_in_service,
+                                             double* time_in_queue, double* queue_area, double* arrival_time,
+                                             double* clock, double* end_time, int64_t* total_customers,
+                                             int64_t* events, int64_t* n_records, int32_t* snap_stop,
+                                             double* queue_time) {
+  const char* who = "gdm_des_stats_batch_snap_host";
+  const StatsOut o{served,    reneges,  generated,       max_queue, time_in_service, time_in_queue, queue_area, arrival_time,
+                   clock,     end_time, total_customers, events,    n_records,       snap_stop,     queue_time};
+  GDM_REQUIRE(kind, "%s: null pointer", who);
+  GDM_REQUIRE(S >= 1 && S <= GDM_DES_SNAP_MAX, "%s: 1 <= S <= %d", who, GDM_DES_SNAP_MAX);
+  int rc = check_stats_host(who, adj, B, dim, loc, scale, queue_cap, seed, snap_customers, max_queue_cap, math,
+                            max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
+  if (rc == GDM_OK) rc = check_kinds(who, kind, B, dim, kLastKind<des::AnyNode>);
+  if (rc != GDM_OK) return rc;
+  for (int b = 0; b < B; ++b)
+    for (int s = 0; s < S; ++s)
+      GDM_REQUIRE(snap_customers[(size_t)b * S + s] > (s ? snap_customers[(size_t)b * S + s - 1] : 0),
+                  "%s: snap_customers of sample %d must be strictly ascending with values >= 1 (entry %d)", who, b, s);
+  with_math(math, [&](auto m) {
+    stats_snap_batch_host<decltype(m)>(adj, B, dim, loc, scale, kind, queue_cap, seed, snap_customers, S,
+                                       max_queue_cap, max_events, mt_key, mt_pos, has_gauss, cached_gauss, o);
+    return 0;
+  });
+  return GDM_OK;
 }

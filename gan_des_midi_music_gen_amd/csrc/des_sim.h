@@ -28,7 +28,8 @@
 //
 // What a run leaves behind is two more policies.  Out is the record sink: the 'Music' log as an array of structs, as four
 // field arrays, or nothing at all (OutNone).  Stats is the accumulator set: NoStats (empty, every hook a no-op: the logging
-// builds) or NodeStats, the per-node queueing statistics of the reference's Server / Source objects.
+// builds) or NodeStats, the per-node queueing statistics of the reference's Server / Source objects, or SnapStats,
+// NodeStats with snapshots of them at customer counts of the same run.
 //
 // Dist is the distribution policy: NormalOnly (empty: every draw is norm_rvs, the bridges' nets) or AnyDist, a kind per
 // node -- normal, exponential or uniform -- or AnyNode, which adds the reference's two node kinds without a distribution:
@@ -227,6 +228,8 @@ struct NoStats {
   DES_HD void held(int, double, int64_t) const {}
   DES_HD void delay(int, double) const {}
   template <class D>
+  DES_HD void checkpoint(int64_t, double, const int32_t*, const D&, int64_t, int64_t) const {}
+  template <class D>
   DES_HD void finish(const uint8_t*, const int32_t*, int, const D&) const {}
 };
 
@@ -291,10 +294,115 @@ struct NodeStats {
   // the number of delayed departures of a node is about to change; len: queue length + delayed departures before it
   DES_HD void held(int node, double t, int64_t len) { integrate(node, t, len); }
   DES_HD void delay(int node, double dt) { time_in_queue[node] += dt; }                // 697
+  // after every pop, before the customers test: SnapStats' (below); nothing here
+  template <class D>
+  DES_HD void checkpoint(int64_t, double, const int32_t*, const D&, int64_t, int64_t) const {}
   template <class D>
   DES_HD void finish(const uint8_t* is_source, const int32_t* qlen, int dim, const D& dist) {
     for (int i = 0; i < dim; ++i)
       if (!is_source[i]) integrate(i, end_time, qlen[i] + dist.held(i));
+  }
+};
+
+// ---- NodeStats with snapshots at customer counts.  number_of_customers enters the run in its stop test alone, so the
+// run of n1 customers is a prefix of the run of n2 > n1: the state at the pop where the test for n1 WOULD fire, closed
+// the way finish() closes it, is what the run of n1 customers returns -- field for field and bit for bit.
+// snap_customers: the sample's n_snap checkpoints, strictly ascending, the last one the run's number_of_customers (the
+// caller checks the row, sets next = 0 and passes the last entry to run()).  The accumulators of NodeStats are scratch here; `o` are the sample's
+// snapshot rows, (n_snap, dim), (n_snap) and (n_snap, dim, hist_stride).  The RUNNING histogram (NodeStats::queue_time)
+// is the last snapshot's slot: the last checkpoint is the run's own stop test, so that snapshot is the final state and
+// finish() closes it in place.
+// A snapshot's time-at-queue-length terms are closed on a COPY: queue_area, queue_time and last_change keep running
+// untouched (an interval split in two rounds differently from then on, and the run would no longer be the run without
+// snapshots).  With a histogram one snapshot costs the thread that runs the chain dim * hist_stride doubles.
+// Host instantiations only so far (des_core.hip: gdm_des_stats_batch_snap_host; tools/des_snap_host.cpp): a
+// one-wave-per-sample kernel over this policy is not part of the library.
+struct SnapOut {
+  int64_t *served, *reneges, *generated;
+  int32_t* max_queue;
+  double *time_in_service, *time_in_queue, *queue_area, *arrival_time, *clock, *end_time;
+  int64_t *total_customers, *events, *n_records;
+  int32_t* stop;
+  double* queue_time;
+};
+struct SnapStats : NodeStats {
+  const int64_t* snap_customers;
+  int32_t n_snap, next;       // next: the first checkpoint not written yet (the caller sets it to 0)
+  int32_t dim;
+  const uint8_t* is_source;
+  SnapOut o;
+
+  // snapshot s: the state at this pop, its time at queue length closed up to end_time on a copy
+  template <class D>
+  DES_HD void write(int s, int64_t total_customers, double clock, const int32_t* qlen, const D& dist, int64_t n_out,
+                    int64_t processed) {
+    if (s < 0 || s >= n_snap) return;
+    const int64_t row = (int64_t)s * dim, hs = hist_stride;
+    double* h = queue_time ? o.queue_time + row * hs : nullptr;
+    for (int i = 0; i < dim; ++i) {
+      o.served[row + i] = served[i];
+      o.reneges[row + i] = reneges[i];
+      o.generated[row + i] = generated[i];
+      o.max_queue[row + i] = max_queue[i];
+      o.time_in_service[row + i] = time_in_service[i];
+      o.time_in_queue[row + i] = time_in_queue[i];
+      o.arrival_time[row + i] = arrival_time[i];
+      double area = queue_area[i];
+      if (h)
+        for (int64_t k = 0; k < hs; ++k) h[i * hs + k] = queue_time[i * hs + k];
+      if (!is_source[i]) {                                 // finish()'s integrate(), on the copy
+        const int64_t len = qlen[i] + dist.held(i);
+        const double d = end_time - last_change[i];
+        area += d * (double)len;
+        if (h && len >= 0 && len < hs) h[i * hs + len] += d;
+      }
+      o.queue_area[row + i] = area;
+    }
+    o.clock[s] = clock;
+    o.end_time[s] = end_time;
+    o.total_customers[s] = total_customers;
+    o.events[s] = processed;
+    o.n_records[s] = n_out;
+    o.stop[s] = DES_STOP_CUSTOMERS;
+  }
+  // every checkpoint but the last whose stop test fires at this pop (several may: all at or below the number of
+  // sources fire at the first); the last one is run()'s own test
+  template <class D>
+  DES_HD void checkpoint(int64_t total_customers, double clock, const int32_t* qlen, const D& dist, int64_t n_out,
+                         int64_t processed) {
+    while (next < n_snap - 1 && total_customers > snap_customers[next] - 1) {
+      write(next, total_customers, clock, qlen, dist, n_out, processed);
+      ++next;
+    }
+  }
+  // After run(): every checkpoint not written yet receives the final state and the run's stop reason -- zeros after
+  // an error (the checkpoints written before it are the shorter runs', which ended well).
+  DES_HD void flush(int reason, int64_t total_customers, double clock, int64_t n_out) {
+    const bool keep = reason != DES_STOP_ERROR;
+    const int64_t hs = hist_stride;
+    for (int s = next; s < n_snap; ++s) {
+      const int64_t row = (int64_t)s * dim;
+      for (int i = 0; i < dim; ++i) {
+        o.served[row + i] = keep ? served[i] : 0;
+        o.reneges[row + i] = keep ? reneges[i] : 0;
+        o.generated[row + i] = keep ? generated[i] : 0;
+        o.max_queue[row + i] = keep ? max_queue[i] : 0;
+        o.time_in_service[row + i] = keep ? time_in_service[i] : 0.0;
+        o.time_in_queue[row + i] = keep ? time_in_queue[i] : 0.0;
+        o.queue_area[row + i] = keep ? queue_area[i] : 0.0;
+        o.arrival_time[row + i] = keep ? arrival_time[i] : 0.0;
+        if (!queue_time || (keep && s == n_snap - 1)) continue;           // (the running histogram is the last slot)
+        double* h = o.queue_time + (row + i) * hs;
+        for (int64_t k = 0; k < hs; ++k) h[k] = keep ? queue_time[i * hs + k] : 0.0;
+      }
+      o.clock[s] = keep ? clock : 0.0;
+      o.end_time[s] = keep ? end_time : 0.0;
+      o.total_customers[s] = keep ? total_customers : 0;
+      o.events[s] = keep ? events : 0;
+      o.n_records[s] = keep ? n_out : 0;
+      o.stop[s] = reason;
+    }
+    next = n_snap;
   }
 };
 
@@ -749,6 +857,7 @@ struct Sim {
     while (!stop && heap_n > 0) {
       const Ev evt = pop();
       stats.pop(evt.time);                             // counted in the time integration before the break (472-486)
+      stats.checkpoint(total_customers, clock, qlen, dist, n_out, processed);
       if (total_customers > number_of_customers - 1) { reason = DES_STOP_CUSTOMERS; break; }
       clock = evt.time;
       stats.event();

@@ -81,6 +81,15 @@ Differences, on purpose:
         a queue node must wait and every child is a     the departure is scheduled at +inf: the     stop 3
         source (none ever schedules a departure)        run is not defined by its inputs alone
 
+  * the statistics at S customer counts of ONE run: ``number_of_customers`` enters the reference only in its stop test
+    (486), so its run of n1 customers is a prefix of its run of n2 > n1, and ``run_stats_snapshots`` /
+    ``run_stats_snapshots_host`` (``gdm_des_stats_batch_snap_host``, des::SnapStats in csrc/des_sim.h) leave at every
+    checkpoint what ``run_stats_host`` returns for that many customers, bit for bit (tests/golden/des_snap.npz holds the
+    reference's own shorter runs).  ``snapshot`` and ``window`` cut BatchStats out of them, ``convergence`` is
+    ``replicate`` at every checkpoint from one batch, ``batch_means`` a confidence interval from one long run, and
+    ``warmup=`` on ``replicate`` / ``mm1k_sweep`` / ``mmck_sweep`` leaves the empty-system start out.  These run on the
+    host mirror; there is no kernel for them, and a device is refused by name.
+
   * shortest-queue routing is not built: ``FlowBranchOperator.shortest_queue`` (49-52) is set from the probabilities
     AFTER they were normalised, so it can be true only for a node without children, which the table above covers;
     ``use_next_available_server`` (731-736) is read on that path only.  ``Sim.run`` accepts and ignores the argument.
@@ -567,6 +576,125 @@ def run_stats(specs, *, device=None, max_events=200000, states=None, histogram=F
     return run_stats_device(adj, *rest, states, device=device, **kw)
 
 
+# ---- snapshots: the statistics at S customer counts of ONE run -------------------------------------------------------------
+StatsSnapshots = collections.namedtuple("StatsSnapshots", "snaps stop checkpoints mt_key mt_pos has_gauss gauss")
+StatsSnapshots.__doc__ = """The statistics of B runs at S customer counts each (``gdm_des_stats_batch_snap_host``):
+``snaps``, a BatchStats whose per-node arrays are (B,S,dim), per-sample arrays (B,S) and ``queue_time``
+(B,S,dim,max_queue_cap+1) or None (``is_source`` (B,dim) and the generator states, (B), are the run's); ``stop`` (B,S)
+int32, the stop reason of every snapshot (``snaps.stop_reason``); ``checkpoints`` (B,S) int64; and the generator states
+after the whole run as in BatchStats.  Snapshot s of sample b is what the statistics run returns for that sample with
+``checkpoints[b, s]`` customers -- bit for bit; the run to the last checkpoint is made once.  ``snapshot`` and ``window``
+cut BatchStats out of it."""
+_ADDITIVE = ("served", "reneges", "generated", "time_in_service", "time_in_queue", "queue_area", "arrival_time",
+             "clock", "end_time", "events", "n_records", "queue_time")
+
+
+def _checkpoints(who, checkpoints, b):
+    """(S,) or (B,S) customer counts -> a contiguous (B,S) int64 array.  Only the shape is checked here: the entry
+    refuses a row that is not strictly ascending from >= 1 by message."""
+    cp = np.asarray(checkpoints)
+    if cp.ndim == 1:
+        cp = np.broadcast_to(cp, (b, cp.shape[0]))
+    if cp.ndim != 2 or cp.shape[0] != b or cp.shape[1] < 1 or cp.dtype.kind not in "iu":
+        raise ValueError(f"{who}: checkpoints must be (S,) or (B, S) integers, S >= 1")
+    return np.ascontiguousarray(cp, dtype=np.int64)
+
+
+def run_stats_snapshots_host(adj, loc, scale, queue_cap, seed, checkpoints, states=None, *, math=1, max_events=200000,
+                             max_queue_cap=None, histogram=False, kind=None):
+    """``gdm_des_stats_batch_snap_host`` on the numpy arrays of ``run_stats_host`` with ``checkpoints`` ((S,) or (B,S),
+    every row strictly ascending from >= 1) in the place of ``customers``: every sample runs ONCE, to its last
+    checkpoint -> StatsSnapshots of numpy arrays.  ``kind`` (B,dim) is the index into NODE_KINDS (the entry runs the
+    policy with 'queue' and 'branch' nodes, the superset); None: every node is normal."""
+    adj = np.ascontiguousarray(adj, dtype=np.float64)
+    b, dim = adj.shape[0], adj.shape[1]
+    cp = _checkpoints("run_stats_snapshots_host", checkpoints, b)
+    s = cp.shape[1]
+    if kind is None:
+        kind = np.zeros((b, dim), dtype=np.int32)
+    x = _host_inputs("run_stats_snapshots_host", adj, loc, scale, queue_cap, seed, cp[:, -1], states, max_queue_cap,
+                     math, max_events, kind, True)
+    k, p, h, g = x.state
+    out = {n: np.zeros((b, s, dim), dtype=_STATS_DTYPES[n]) for n in STATS_NODE_FIELDS}
+    out.update({n: np.zeros((b, s), dtype=_STATS_DTYPES[n]) for n in STATS_SAMPLE_FIELDS})
+    hist = np.zeros((b, s, dim, x.max_queue_cap + 1), dtype=np.float64) if histogram else None
+    name = "gdm_des_stats_batch_snap_host"
+    # x.head ends in (customers, max_queue_cap, math, max_events): snap_customers and S take the place of the first
+    rc = getattr(_lib.load(), name)(*x.head[:-4], cp.ctypes.data, s, *x.head[-3:], k.ctypes.data, p.ctypes.data,
+                                    h.ctypes.data, g.ctypes.data,
+                                    *(out[n].ctypes.data for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS),
+                                    hist.ctypes.data if histogram else None)
+    _lib.check(rc, name)
+    is_source = np.diagonal(x.adj, axis1=1, axis2=2) > 0
+    snaps = BatchStats(*(out[n] for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS), hist, is_source, k, p, h, g)
+    return StatsSnapshots(snaps, out["stop_reason"], cp, k, p, h, g)
+
+
+def _no_snapshot_kernel(who, device):
+    """The snapshot run has a host entry only: a device is refused by name, nothing falls back quietly."""
+    if device is not None:
+        raise NotImplementedError(f"{who}: snapshots, and warmup=, run on the host mirror only (device=None): there is "
+                                  "no snapshot kernel in the library")
+
+
+def _checked_rows(who, checkpoints):
+    """The value check of the spec-level functions (the array-level ones leave it to the entries)."""
+    cp = np.asarray(checkpoints, dtype=np.int64)
+    if cp.ndim not in (1, 2) or cp.shape[-1] < 1 or (cp[..., 0] < 1).any() or (np.diff(cp, axis=-1) <= 0).any():
+        raise ValueError(f"{who}: checkpoints must be strictly ascending customer counts >= 1")
+    return cp
+
+
+def run_stats_snapshots(specs, checkpoints, *, device=None, max_events=200000, states=None, histogram=False):
+    """``run_stats`` at S customer counts of the same runs: B ``DesSpec`` of one size (their own ``num_customers`` is not
+    used: a run ends at its last checkpoint), ``checkpoints`` (S,) for all or (B,S) -> StatsSnapshots of numpy arrays
+    from the host mirror with portable math.  Nodes may be any of NODE_KINDS.  ``device`` must be None: there is no
+    snapshot kernel, and a device raises NotImplementedError instead of falling back."""
+    _no_snapshot_kernel("run_stats_snapshots", device)
+    adj, kind, loc, scale, qcap, seed, _customers = net_arrays(specs, "run_stats_snapshots")
+    cp = _checked_rows("run_stats_snapshots", checkpoints)
+    return run_stats_snapshots_host(adj, loc, scale, qcap, seed, cp, states, math=1, max_events=max_events,
+                                    histogram=histogram, kind=kind)
+
+
+def snapshot(snaps, s):
+    """Snapshot ``s`` of a StatsSnapshots as a BatchStats -- the statistics run of ``checkpoints[:, s]`` customers --, so
+    ``metrics`` takes it as it is."""
+    st = snaps.snaps
+    return BatchStats(*(getattr(st, n)[:, s] for n in STATS_NODE_FIELDS + STATS_SAMPLE_FIELDS),
+                      None if st.queue_time is None else st.queue_time[:, s], st.is_source, *st[-4:])
+
+
+def window(snaps, s0, s1):
+    """The statistics of the interval between snapshots ``s0`` and ``s1`` (s0 None: from the empty start) as a
+    BatchStats: the additive fields -- served, reneges, generated, n_records, events, the sums time_in_service,
+    time_in_queue, arrival_time, queue_area and queue_time, clock and end_time -- are the differences; ``max_queue``,
+    ``total_customers`` and ``stop_reason`` are those of ``s1`` (max_queue is the largest since the start of the run).
+    ``metrics`` of a window divides by the window's length of ``clock``.  Edge effect: ``time_in_service`` is credited
+    when a service STARTS (the reference's ScheduleDeparture, simulation_v3.py:606), so a window gains the whole service
+    that starts in it and none of the one running at its start: its utilisation is off by at most one service time per
+    node, relative to the window's length."""
+    hi = snapshot(snaps, s1)
+    if s0 is None:
+        return hi
+    lo = snapshot(snaps, s0)
+    return hi._replace(**{n: getattr(hi, n) - getattr(lo, n) for n in _ADDITIVE if getattr(hi, n) is not None})
+
+
+def _window_run(adj, loc, scale, queue_cap, seed, customers, states, *, warmup, device, math, max_events,
+                histogram=False, kind=None, max_queue_cap=None):
+    """What ``warmup=`` does in ``replicate`` and the sweeps: one run per sample with the checkpoints (warmup, customers),
+    the window between them."""
+    _no_snapshot_kernel("warmup=", device)
+    warmup, customers = int(warmup), np.asarray(customers, dtype=np.int64).reshape(-1)
+    if not 1 <= warmup < customers.min():
+        raise ValueError(f"warmup must be in 1 .. customers - 1, got {warmup}")
+    cp = np.stack([np.full_like(customers, warmup), customers], axis=1)
+    snaps = run_stats_snapshots_host(adj, loc, scale, queue_cap, seed, cp, states, math=math, max_events=max_events,
+                                     histogram=histogram, kind=kind, max_queue_cap=max_queue_cap)
+    return window(snaps, 0, 1)
+
+
 METRIC_NAMES = ("avg_time_at_server", "avg_queue_time", "server_utilizations", "max_queue_lengths", "renege_rate",
                 "service_times", "arrival_times", "customers_served_per_server", "avg_queue_length",
                 "avg_server_length")
@@ -633,17 +761,13 @@ def replication_states(seeds):
     return [np.random.RandomState([int(s), 1]).get_state() for s in seeds]
 
 
-def replicate(spec, seeds, *, device=None, max_events=200000, states=None):
-    """R = len(seeds) seeded runs of ONE net (a ``DesSpec``; its own ``seeds`` are not used) in one batch, then
-    ``metrics`` and their mean / std (ddof 1) / sem / n over the replications -> Replications.  Nodes may be any of
-    NODE_KINDS.  ``states``: the R global
-    generator states (default ``replication_states(seeds)``).  No interval is formed: sem and n are what one needs."""
-    from . import ops
+def _replication_inputs(who, spec, seeds, states):
+    """R seeded runs of ONE net as a batch: ((adj, loc, scale, queue_cap, seed, customers, states), kind or None, net)."""
     seeds = [int(s) for s in np.asarray(seeds).reshape(-1)]
     r = len(seeds)
     if r == 0:
-        raise ValueError("replicate: no seeds")
-    kinds, locs, scales = dist_row(spec.distributions, "replicate", NODE_KINDS)
+        raise ValueError(f"{who}: no seeds")
+    kinds, locs, scales = dist_row(spec.distributions, who, NODE_KINDS)
     net = any(k >= len(DIST_KINDS) for k in kinds)
     one = np.asarray(spec.sim_matrix, dtype=np.float64)
     dim = one.shape[0]
@@ -655,14 +779,17 @@ def replicate(spec, seeds, *, device=None, max_events=200000, states=None):
     customers = np.full(r, int(spec.num_customers), dtype=np.int64)
     if states is None:
         states = replication_states(seeds)
-    arrays = (adj, loc, scale, qcap, np.asarray(seeds, dtype=np.int64), customers, states)
-    if device is None:
-        stats = run_stats_host(*arrays, math=1, max_events=max_events, kind=kind, net=net)
-    else:
-        stats = run_stats_device(*arrays, device=device, max_events=max_events, kind=kind, net=net)
-    m = metrics(stats)
-    stop = np.asarray(stats.stop_reason.cpu() if hasattr(stats.stop_reason, "cpu") else stats.stop_reason)
-    valid = (stop != ops.DES_STOP_ERROR) & (stop != ops.DES_STOP_BUDGET)
+    return (adj, loc, scale, qcap, np.asarray(seeds, dtype=np.int64), customers, states), kind, net
+
+
+def _valid_runs(stop_reason):
+    from . import ops
+    stop = np.asarray(stop_reason.cpu() if hasattr(stop_reason, "cpu") else stop_reason)
+    return (stop != ops.DES_STOP_ERROR) & (stop != ops.DES_STOP_BUDGET)
+
+
+def _over_runs(m, valid):
+    """Per metric name: mean, std (ddof 1), sem and n over the runs of ``valid`` that have a value."""
     mean, std, sem, n = {}, {}, {}, {}
     for name, a in m.items():
         a = a[valid]
@@ -674,7 +801,89 @@ def replicate(spec, seeds, *, device=None, max_events=200000, states=None):
             dev2 = np.where(have, (a - mean[name]) ** 2, 0.0).sum(axis=0)
             std[name] = np.where(n[name] > 1, np.sqrt(dev2 / (n[name] - 1)), np.nan)
             sem[name] = std[name] / np.sqrt(n[name])
+    return mean, std, sem, n
+
+
+def replicate(spec, seeds, *, device=None, max_events=200000, states=None, warmup=0):
+    """R = len(seeds) seeded runs of ONE net (a ``DesSpec``; its own ``seeds`` are not used) in one batch, then
+    ``metrics`` and their mean / std (ddof 1) / sem / n over the replications -> Replications.  Nodes may be any of
+    NODE_KINDS.  ``states``: the R global
+    generator states (default ``replication_states(seeds)``).  No interval is formed: sem and n are what one needs.
+    ``warmup`` (customers, default 0: the whole run from the empty system): the statistics of the ``window`` between
+    ``warmup`` and ``num_customers`` customers of the same runs (``run_stats_snapshots_host``; host mirror only: with a
+    ``device`` it raises NotImplementedError)."""
+    arrays, kind, net = _replication_inputs("replicate", spec, seeds, states)
+    if warmup:
+        stats = _window_run(*arrays, warmup=warmup, device=device, math=1, max_events=max_events, kind=kind)
+    elif device is None:
+        stats = run_stats_host(*arrays, math=1, max_events=max_events, kind=kind, net=net)
+    else:
+        stats = run_stats_device(*arrays, device=device, max_events=max_events, kind=kind, net=net)
+    m = metrics(stats)
+    valid = _valid_runs(stats.stop_reason)
+    mean, std, sem, n = _over_runs(m, valid)
     return Replications(stats, m, mean, std, sem, n, valid)
+
+
+Convergence = collections.namedtuple("Convergence", "snaps checkpoints mean sem n valid")
+Convergence.__doc__ = """``convergence``'s result: the StatsSnapshots of the R runs, ``checkpoints`` (S,), and per metric name
+``mean``, ``sem`` (std with ddof 1 / sqrt(n)) and ``n`` over the runs of ``valid`` (R,S) that have a value, stacked over the
+checkpoints: (S,dim) for METRIC_NAMES, (S,) for TOTAL_NAMES -- a metric against run length with its error band."""
+
+
+def convergence(spec, seeds, checkpoints, *, device=None, max_events=200000, states=None):
+    """How the metrics of ONE net converge with run length: R = len(seeds) replications as in ``replicate``, ONE batch
+    on the host mirror (portable math) that runs to ``checkpoints[-1]`` customers (``spec.num_customers`` is not used) and leaves
+    a snapshot at every entry of ``checkpoints`` (S,) -> Convergence.  Row s is what ``replicate`` returns for
+    ``num_customers = checkpoints[s]``, without the S - 1 shorter runs.  ``device`` must be None, as in ``run_stats_snapshots``."""
+    _no_snapshot_kernel("convergence", device)
+    cp = _checked_rows("convergence", checkpoints)
+    if cp.ndim != 1:
+        raise ValueError("convergence: checkpoints must be (S,)")
+    (adj, loc, scale, qcap, seed, _customers, states), kind, _net = _replication_inputs("convergence", spec, seeds, states)
+    snaps = run_stats_snapshots_host(adj, loc, scale, qcap, seed, cp, states, math=1, max_events=max_events, kind=kind)
+    valid = _valid_runs(snaps.stop)
+    rows = [_over_runs(metrics(snapshot(snaps, s)), valid[:, s]) for s in range(len(cp))]
+    mean, sem, n = ({name: np.stack([row[i][name] for row in rows]) for name in rows[0][0]} for i in (0, 2, 3))
+    return Convergence(snaps, cp, mean, sem, n, valid)
+
+
+BatchMeans = collections.namedtuple("BatchMeans", "snaps checkpoints values mean sem n lag1")
+BatchMeans.__doc__ = """``batch_means``'s result: the StatsSnapshots of the one run, its ``checkpoints``, and per metric name
+``values`` (n_batches,dim) -- (n_batches,) for TOTAL_NAMES --, the metric in every batch; ``mean``, ``sem`` (std with ddof
+1 / sqrt(n)) and ``n`` over the batches that have a value; and ``lag1``, the lag-1 autocorrelation of the batch values
+(sum of (v[j] - mean)(v[j+1] - mean) over sum of (v[j] - mean)^2; NaN where a batch has no value or the values do not
+vary): near 0 when the batches are long enough for the sem to mean what it says."""
+
+
+def batch_means(spec, seed, *, n_batches, batch_customers, warmup=0, device=None, max_events=200000, state=None):
+    """A confidence interval from ONE long run: ``warmup`` customers are left out, then ``n_batches`` consecutive
+    windows of ``batch_customers`` customers each, the checkpoints warmup + j * batch_customers, j = 0 .. n_batches (with
+    warmup 0 the first window starts at the empty system and j = 0 is no checkpoint) -> BatchMeans.  ``spec.num_customers``
+    is not used; ``state``: the global generator state (default ``replication_states([seed])[0]``).  ValueError when the
+    run ends before its last checkpoint (raise ``max_events``).  ``device`` must be None, as in ``run_stats_snapshots``."""
+    from . import ops
+    _no_snapshot_kernel("batch_means", device)
+    n_batches, batch_customers, warmup = int(n_batches), int(batch_customers), int(warmup)
+    if n_batches < 2 or batch_customers < 1 or warmup < 0:
+        raise ValueError("batch_means: n_batches >= 2, batch_customers >= 1, warmup >= 0")
+    cp = np.array([warmup + j * batch_customers for j in range(0 if warmup else 1, n_batches + 1)], dtype=np.int64)
+    (adj, loc, scale, qcap, sd, _customers, states), kind, _net = _replication_inputs(
+        "batch_means", spec, [seed], None if state is None else [state])
+    snaps = run_stats_snapshots_host(adj, loc, scale, qcap, sd, cp, states, math=1, max_events=max_events, kind=kind)
+    stop = snaps.stop
+    if (stop != ops.DES_STOP_CUSTOMERS).any():
+        raise ValueError(f"batch_means: the run ended with {STOP_REASONS[int(stop[0, -1])]!r} before its last checkpoint")
+    first = 0 if warmup else -1                           # the snapshot a batch starts at, for batch 0
+    per = [metrics(window(snaps, first + j if first + j >= 0 else None, first + j + 1)) for j in range(n_batches)]
+    values = {name: np.concatenate([m[name] for m in per]) for name in per[0]}
+    mean, _std, sem, n = _over_runs(values, np.ones(n_batches, dtype=bool))
+    lag1 = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for name, v in values.items():
+            d = v - v.mean(axis=0)
+            lag1[name] = (d[:-1] * d[1:]).sum(axis=0) / (d * d).sum(axis=0)
+    return BatchMeans(snaps, cp, values, mean, sem, n, lag1)
 
 
 # ---- simulation beside theory: M/M/1/K -------------------------------------------------------------------------------
@@ -696,7 +905,7 @@ def mm1k_spec(lam, mu, queue_cap, customers, seed=0):
                    [int(queue_cap), int(queue_cap)], np.array([int(seed)]), int(customers), 1.0, np.zeros(2), np.zeros(2))
 
 
-def mm1k_sweep(lams, mus, queue_caps, seeds, *, customers, device=None, max_events=None, math=1):
+def mm1k_sweep(lams, mus, queue_caps, seeds, *, customers, device=None, max_events=None, math=1, warmup=0):
     """Simulated M/M/1/K beside ``queueing_theory.mm1k``: configuration c = (lams[c], mus[c], queue_caps[c]), every
     configuration with every seed, ALL of them one batch (one launch on a device; ``math`` is the host mirror's).
     Replication r of every configuration starts from the global stream ``replication_states(seeds)[r]``.  Compared
@@ -707,7 +916,10 @@ def mm1k_sweep(lams, mus, queue_caps, seeds, *, customers, device=None, max_even
       avg_queue_length            queue_area / clock                                                     ~ LQ
       avg_queue_time              time_in_queue / served                                                 ~ WQ
       queue_length_probabilities  queue_time / clock                                                     ~ (p0 + p1, p2, ..)
-    -> Mm1kSweep.  max_events None: 4 * customers + 64, which no run reaches (an arrival and a departure per customer)."""
+    -> Mm1kSweep.  max_events None: 4 * customers + 64, which no run reaches (an arrival and a departure per customer).
+    ``warmup`` (customers, default 0): every quantity, and ``stats``, is that of the ``window`` between ``warmup`` and
+    ``customers`` customers of the same runs, the empty-system start left out (host mirror only: with a ``device`` it
+    raises NotImplementedError)."""
     from . import ops, queueing_theory as qt
     lams, mus = np.asarray(lams, dtype=np.float64).reshape(-1), np.asarray(mus, dtype=np.float64).reshape(-1)
     caps = np.asarray(queue_caps, dtype=np.int64).reshape(-1)
@@ -722,7 +934,10 @@ def mm1k_sweep(lams, mus, queue_caps, seeds, *, customers, device=None, max_even
     specs = [mm1k_spec(lams[i], mus[i], caps[i], customers, s) for i in range(c) for s in seeds]
     states = replication_states(seeds) * c
     adj, kind, *rest = dist_arrays(specs)
-    if device is None:
+    if warmup:
+        stats = _window_run(adj, *rest, states, warmup=warmup, device=device, math=math, max_events=max_events,
+                            histogram=True, kind=kind)
+    elif device is None:
         stats = run_stats_host(adj, *rest, states, math=math, max_events=max_events, histogram=True, kind=kind)
     else:
         stats = run_stats_device(adj, *rest, states, device=device, max_events=max_events, histogram=True, kind=kind)
@@ -792,7 +1007,7 @@ def mmck_spec(c, lam, mu, queue_cap, customers, seed=0):
                    np.zeros(dim))
 
 
-def mmck_sweep(cs, lams, mus, queue_caps, seeds, *, customers, device=None, max_events=None, math=1):
+def mmck_sweep(cs, lams, mus, queue_caps, seeds, *, customers, device=None, max_events=None, math=1, warmup=0):
     """Simulated M/M/c/N beside ``queueing_theory.mmck``, shaped like ``mm1k_sweep``: configuration i = (cs[i], lams[i],
     mus[i], queue_caps[i]) on the net of ``mmck_spec``, every configuration with every seed from the global stream
     ``replication_states(seeds)[r]``.  Configurations of one c are one batch (one launch on a device: a batch has one
@@ -803,7 +1018,7 @@ def mmck_sweep(cs, lams, mus, queue_caps, seeds, *, customers, device=None, max_
       avg_queue_time              time_in_queue / served at the queue node (waits and delays)             ~ WQ
       queue_length_probabilities  queue_time / clock at the queue node                                    ~ (p[0] + .. + p[c], p[c + 1], ..)
     -> MmckSweep.  max_events None: 16 * customers + 64 (an arrival and two departures per customer, and a re-pop for
-    every delayed departure that loses its tie)."""
+    every delayed departure that loses its tie).  ``warmup`` as in ``mm1k_sweep``."""
     from . import ops, queueing_theory as qt
     cs = np.asarray(cs, dtype=np.int64).reshape(-1)
     lams, mus = np.asarray(lams, dtype=np.float64).reshape(-1), np.asarray(mus, dtype=np.float64).reshape(-1)
@@ -824,7 +1039,10 @@ def mmck_sweep(cs, lams, mus, queue_caps, seeds, *, customers, device=None, max_
         specs = [mmck_spec(servers, lams[i], mus[i], caps[i], customers, s) for i in idx for s in seeds]
         adj, kind, *rest = net_arrays(specs, "mmck_sweep")
         kw = dict(max_events=max_events, histogram=True, kind=kind, net=True, max_queue_cap=k)
-        if device is None:
+        if warmup:
+            stats = _window_run(adj, *rest, replication_states(seeds) * len(idx), warmup=warmup, device=device,
+                                math=math, **{k_: v for k_, v in kw.items() if k_ != "net"})
+        elif device is None:
             stats = run_stats_host(adj, *rest, replication_states(seeds) * len(idx), math=math, **kw)
         else:
             stats = run_stats_device(adj, *rest, replication_states(seeds) * len(idx), device=device, **kw)

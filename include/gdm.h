@@ -627,6 +627,36 @@ int gdm_des_run_batch_net(const double* adj, int B, int dim, const double* loc, 
                           int64_t n_records_cap, int64_t* rec_ptr, int64_t* n_records, int32_t* stop_reason,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the statistics at S customer counts of ONE run: snapshots (csrc/des_sim.h: des::SnapStats) -- HOST entry only ------
+ * number_of_customers enters a run only in its stop test, so the run of n1 customers is a prefix of the run of n2 > n1
+ * under the same seeds.  This entry runs gdm_des_stats_batch_net_host (des::AnyNode, the superset of the node kinds; an
+ * all-normal net passes kind = 0 everywhere) ONCE per sample, to the sample's last checkpoint, and writes at every
+ * checkpoint what the run of that many customers returns:
+ *   snap_customers (B, S) i64, 1 <= S <= GDM_DES_SNAP_MAX, every row strictly ascending with values >= 1; the run's
+ *   number_of_customers is the row's last entry (there is no other customers array).
+ * Outputs: the arrays of gdm_des_stats_batch_net_host with S between B and the rest -- (B, S, dim), (B, S), snap_stop
+ * (B, S) i32 and the optional queue_time (B, S, dim, max_queue_cap + 1) -- and the generator state after the run, (B).
+ * INVARIANT: snapshot s of sample b is, field for field and bit for bit, what gdm_des_stats_batch_net_host returns for
+ * that sample with number_of_customers = snap_customers[b, s] and the same max_events and math; the generator state is
+ * that of the run to the last checkpoint.  A checkpoint's stop test fires at a pop (several at one pop: all at or below
+ * the number of sources fire at the first); such a snapshot has GDM_DES_STOP_CUSTOMERS and its time-at-queue-length
+ * terms closed up to that pop on a copy, the running sums untouched.  When the run ends for another reason (event list
+ * empty, max_events, draw budget) every checkpoint not reached receives the final state and that reason.  A sample
+ * that ends in GDM_DES_STOP_ERROR keeps the generator state it came with and returns zeros and reason 3 in every
+ * checkpoint it had not reached (the ones before are the shorter runs', which ended well; a spec refused before anything
+ * runs has reached none).  A bad snap_customers row refuses the call by message (GDM_EINVAL, nothing runs).
+ * There is NO device entry: the one-wave-per-sample kernel over this policy is not part of the library (DESIGN.md
+ * section 7, f20).                                                                                                     */
+#define GDM_DES_SNAP_MAX 256
+int gdm_des_stats_batch_snap_host(const double* adj, int B, int dim, const double* loc, const double* scale,
+                                  const int32_t* kind, const int32_t* queue_cap, const int64_t* seed,
+                                  const int64_t* snap_customers, int S, int max_queue_cap, int math, int64_t max_events,
+                                  uint32_t* mt_key, int32_t* mt_pos, int32_t* has_gauss, double* cached_gauss,
+                                  int64_t* served, int64_t* reneges, int64_t* generated, int32_t* max_queue,
+                                  double* time_in_service, double* time_in_queue, double* queue_area,
+                                  double* arrival_time, double* clock, double* end_time, int64_t* total_customers,
+                                  int64_t* events, int64_t* n_records, int32_t* snap_stop, double* queue_time);
+
 /* ---- log -> queue tracks (csrc/des_tracks.hip; the reference's MMGAN_MIDI_DES/simlog_to_vid.ipynb, first cell) --------
  * Per sample b, over the first max_lines records of its log [rec_ptr[b], rec_ptr[b + 1]) ('processing' records count
  * towards max_lines and change nothing): an arrival (kind 0) at node n adds 1 to n's counter, a departure (kind 1)

@@ -1,13 +1,15 @@
 """Simulated M/M/1/K and M/M/c/N beside queueing theory (simulation_v3.mm1k_sweep / mmck_sweep, queueing_theory.mm1k /
 mmck): the counterpart of the validation harness the reference's simulator ends in.
 
-    python tools/des_validate.py [--device cuda] [--seeds 64] [--customers 4000]
+    python tools/des_validate.py [--device cuda] [--seeds 64] [--customers 4000] [--warmup N]
 
 For every configuration of the default grid (rho 0.5 .. 1.5, 1 .. 5 waiting places) the source -> server net is run once
 per seed -- all configurations and seeds in ONE batch: the host mirror without --device, one kernel launch with it -- and
 each compared quantity is printed as mean +- standard error over the seeds, the closed form, and z = (mean - theory) /
 sem.  Then the same table for the multi-server grid: source -> queue node -> c servers (simulation_v3.mmck_spec), one
-batch per c, beside M/M/c/N with N = c + max(cap, 1).  Reads nothing outside the repository."""
+batch per c, beside M/M/c/N with N = c + max(cap, 1).  With --warmup N both tables are printed twice: for the whole runs,
+which start from an empty system, and for the window between N and --customers customers of the same runs
+(simulation_v3.window; the host mirror only).  Reads nothing outside the repository."""
 import argparse
 import os
 import sys
@@ -44,18 +46,24 @@ def main():
     ap.add_argument("--device", default=None, help="a HIP device, e.g. cuda (default: the host mirror)")
     ap.add_argument("--seeds", type=int, default=64)
     ap.add_argument("--customers", type=int, default=4000)
+    ap.add_argument("--warmup", type=int, default=0, help="customers left out at the start (0: the whole runs only)")
     a = ap.parse_args()
+    if a.warmup and a.device is not None:
+        ap.error("--warmup runs on the host mirror only: leave --device out (there is no snapshot kernel)")
     seeds = np.arange(a.seeds) * 11 + 5
-    lam, mu, cap = (np.array(c) for c in zip(*GRID))
-    sw = sv.mm1k_sweep(lam, mu, cap, seeds, customers=a.customers, device=a.device)
-    print(f"{'lam':>5} {'mu':>5} {'cap':>3}  {'quantity':<30} {'simulated':>10} {'sem':>9} {'theory':>10} {'z':>6}  n")
-    table(sw, [f"{lam[c]:5.2f} {mu[c]:5.2f} {cap[c]:3d}" for c in range(len(GRID))], [int(k) + 1 for k in cap], a.seeds)
-    cs, lam, mu, cap = (np.array(c) for c in zip(*MMC_GRID))
-    sw = sv.mmck_sweep(cs, lam, mu, cap, seeds, customers=a.customers, device=a.device)
-    print(f"\n{'c':>2} {'lam':>5} {'mu':>5} {'cap':>3}  {'quantity':<30} {'simulated':>10} {'sem':>9} {'theory':>10} "
-          f"{'z':>6}  n")
-    table(sw, [f"{cs[c]:2d} {lam[c]:5.2f} {mu[c]:5.2f} {cap[c]:3d}" for c in range(len(MMC_GRID))],
-          [max(int(k), 1) + 1 for k in cap], a.seeds)
+    for warmup in ((0, a.warmup) if a.warmup else (0,)):
+        print(f"---- customers {warmup} .. {a.customers}" + (" (the whole runs)" if not warmup else " (the window)"))
+        lam, mu, cap = (np.array(c) for c in zip(*GRID))
+        sw = sv.mm1k_sweep(lam, mu, cap, seeds, customers=a.customers, device=a.device, warmup=warmup)
+        print(f"{'lam':>5} {'mu':>5} {'cap':>3}  {'quantity':<30} {'simulated':>10} {'sem':>9} {'theory':>10} {'z':>6}  n")
+        table(sw, [f"{lam[c]:5.2f} {mu[c]:5.2f} {cap[c]:3d}" for c in range(len(GRID))], [int(k) + 1 for k in cap],
+              a.seeds)
+        cs, lam, mu, cap = (np.array(c) for c in zip(*MMC_GRID))
+        sw = sv.mmck_sweep(cs, lam, mu, cap, seeds, customers=a.customers, device=a.device, warmup=warmup)
+        print(f"\n{'c':>2} {'lam':>5} {'mu':>5} {'cap':>3}  {'quantity':<30} {'simulated':>10} {'sem':>9} {'theory':>10} "
+              f"{'z':>6}  n")
+        table(sw, [f"{cs[c]:2d} {lam[c]:5.2f} {mu[c]:5.2f} {cap[c]:3d}" for c in range(len(MMC_GRID))],
+              [max(int(k), 1) + 1 for k in cap], a.seeds)
 
 
 if __name__ == "__main__":
