@@ -18,6 +18,11 @@
 // Sums follow numpy's summation order exactly (pairwise_sum with 8 partial sums for 8 <= n <= 128, sequential below;
 // Python's built-in sum() for the two float32 rows), divisions are IEEE, nothing is contracted into FMAs: the float64
 // matrix is bit-identical to the reference's on the fixtures.
+//
+// One deviation from upstream: Python's int() has no upper limit, an int32 has.  An instrument or note-level entry
+// whose float32 product with 126 is not below 2^31 (|m| from about 1.7044e7 on) raises the sample's flag, like a
+// non-finite entry, and the package refuses the batch with the same ValueError; upstream would carry the Python big
+// integer further (into the MIDI program / note number) before failing.  Below that the integers are upstream's.
 #pragma clang fp contract(off)
 #include "gdm_common.h"
 
@@ -26,7 +31,20 @@ namespace {
 constexpr int DES_MAX_S = 64;
 
 __device__ __forceinline__ bool nonfinite_bits(float v) {
-  return (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) == 0x7f800000u;   // no isnan/isinf: built with -fno-honor-nans
+  // No isnan/isinf: the build assumes there are no NaNs (-fno-honor-nans).  Not the exponent-mask test
+  // `(bits & 0x7f800000) == 0x7f800000` either: the compiler recognises it as a class test and, NaNs assumed away,
+  // emits |v| == inf (v_cmp_eq_f32), which a NaN fails.  An unsigned magnitude compare stays an integer compare.
+  return (__builtin_bit_cast(uint32_t, v) & 0x7fffffffu) >= 0x7f800000u;
+}
+
+// (int)p for a product p of |m| and 126 below 2^31; anything else -- larger, infinite, NaN: read off the bits, the
+// build assumes there are no NaNs -- sets *over and gives INT32_MAX (the conversion itself would be undefined)
+__device__ __forceinline__ int to_int_or_flag(float p, int* over) {
+  if ((__builtin_bit_cast(uint32_t, p) & 0x7fffffffu) >= 0x4f000000u) {                     // 0x4f000000 = 2^31
+    *over = 1;
+    return 0x7fffffff;
+  }
+  return (int)p;
 }
 
 // sample b -> LDS tile[S][S+1] of |m| (fp32), coalesced
@@ -57,9 +75,11 @@ __global__ __launch_bounds__(256) void des_scan_kernel(const float* __restrict__
   __syncthreads();
   if (t < S && thr_mask) thr_mask[(int64_t)b * S + t] = tile[dim][t] > thr ? 1 : 0;       // np.where(matrix[dim] > thr)
   if (t < dim) {
-    // int(matrix[dim + 1, i] * 126): float32 product, truncation
-    instruments[(int64_t)b * dim + t] = (int)(tile[dim + 1][t] * 126.0f);
-    const int nl = (int)(tile[dim + 2][t] * 126.0f);
+    // int(matrix[dim + 1, i] * 126): float32 product, truncation; from 2^31 on the sample is flagged (header comment)
+    int over = 0;
+    instruments[(int64_t)b * dim + t] = to_int_or_flag(tile[dim + 1][t] * 126.0f, &over);
+    const int nl = to_int_or_flag(tile[dim + 2][t] * 126.0f, &over);
+    if (over) atomicOr(&bad, 1);
     note_levels[(int64_t)b * dim + t] = note_mod ? max(0, nl % 128) : nl;
     uint64_t z = 0;
     for (int x = 0; x < dim; ++x) z |= (uint64_t)(tile[t][x] == 0.0f ? 1 : 0) << x;

@@ -45,7 +45,11 @@ return ALL specs before any simulation runs (one batched routing launch): equal 
 that leaves numpy's global stream alone.  Reference quirks kept: matrix_to_midi ALWAYS draws random
 sources (its emptiness test at line 42 is always true); matrix_to_wav raises ValueError for more than one thresholded
 source (line 30) and IndexError for a thresholded column >= dim (line 67); an all-zero row raises ValueError from
-``np.random.choice([])``.
+``np.random.choice([])``.  One deviation: upstream's ``int(matrix[dim + 1, i] * 126)`` is a Python integer without an
+upper limit, the scan's is an int32.  A sample with an instrument or note-level entry whose float32 product with 126 is
+not below 2^31 (|m| from about 1.7044e7 on; a generator's sigmoid output stays below 1) is flagged by the scan and
+raises the ValueError a non-finite matrix raises, where that one is raised; upstream would carry the big integer
+further, into the MIDI program or note number, before failing there.
 
 simulate="des_batch" (opt-in; "des" is unchanged) batches the one stage "des" leaves per sample and on the host: the
 batched prologue (``batched_prologue_midi`` / ``batched_prologue_wav``: one scan launch, ALL host draws in the
@@ -135,7 +139,8 @@ def _reseed():
 
 def _check_finite(flags):
     if int(flags.max()) != 0:
-        raise ValueError("generated matrix holds non-finite values: the DES prologue is defined for finite inputs only")
+        raise ValueError("generated matrix holds non-finite values or an instrument / note-level entry whose product "
+                         "with 126 does not fit an int32: the DES prologue is defined for finite inputs below that only")
 
 
 def _midi_draws(h, i):

@@ -723,7 +723,9 @@ int gdm_maxpool2_bwd(const void* dout, int dtype, const uint8_t* idx, int B, int
  *                 int(|m[dim+1][i]| * 126); note_levels (B,dim) i32 = int(|m[dim+2][i]| * 126), with note_mod:
  *                 max(0, . % 128); zero_mask (B,dim) u64, bit x of row i set iff |m[i][x]| == 0 (x < dim);
  *                 norm_aux: aux (B,2,dim) fp32 = rows dim+3, dim+4 divided by their sequential float32 sum over all S
- *                 entries (model 1's distribution rows); flags (B) i32, bit 0 = the sample holds a non-finite value.
+ *                 entries (model 1's distribution rows); flags (B) i32, bit 0 = the sample holds a non-finite value or
+ *                 an instrument / note-level product |m| * 126 that is not below 2^31 (stored as INT32_MAX; Python's
+ *                 int() upstream has no such limit).
  * gdm_des_routing src_mask (B,dim) u8 (1 = source node), residue_col (B,dim) i32 (column that absorbs 1 - sum(row);
  *                 < 0: none) -> out (B,dim,dim) fp64: source columns and diagonal zeroed, rows divided by their
  *                 float64 sum in numpy's pairwise order (0/0 -> 0), residue added, diagonal +1 (source) / -1 (server).
