@@ -133,6 +133,7 @@ SIGNATURES = {
     "gdm_des_log_tracks_count": (_I, [_P, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P, _P]),
     "gdm_des_log_tracks": (_I, [_P, _P, _P, _L, _I, _I, _P, _I, _L, _P, _L, _P, _P]),
     "gdm_des_log_tracks_host": (_I, [_P, _P, _P, _L, _I, _I, _P, _I, _L, _P, _P, _P, _P, _L]),
+    "gdm_des_log_visits_host": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _L]),
     "gdm_piano_roll_raster": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     "gdm_piano_roll_windows": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "gdm_des_log_to_roll": (_I, [_P, _P, _P, _P, _P, _L, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P,

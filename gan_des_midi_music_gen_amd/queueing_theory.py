@@ -34,6 +34,40 @@ def mm1k(lam, mu, queue_cap):
             "queue_length_probabilities": np.concatenate([[p[0] + p[1]], p[2:]])}
 
 
+def _mm1k_erlang_mixture(lam, mu, queue_cap, t, more):
+    """sum over n = 0 .. K - 1 of q[n] * P(Erlang(n + more, mu) > t), q[n] = p[n] / (1 - p[K]): what an ACCEPTED arrival
+    finds (PASTA, conditioned on not being turned away) and the n + more exponential stages it then sits through;
+    P(Erlang(m, mu) > t) = sum over j < m of exp(-mu t) (mu t)**j / j!  (0 for m = 0)."""
+    p = mm1k(lam, mu, queue_cap)["p"]
+    k = len(p) - 1
+    q = p[:k] / (1.0 - p[k])
+    x = float(mu) * np.asarray(t, dtype=np.float64)
+    if (x < 0).any():
+        raise ValueError("mm1k waiting-time tails: t >= 0 is required")
+    term = [np.exp(-x) * x ** j / math.factorial(j) for j in range(k - 1 + more)]
+    out = np.zeros_like(x)
+    for n in range(k):
+        for j in range(n + more):
+            out = out + q[n] * term[j]
+    return out
+
+
+def mm1k_wait_tail(lam, mu, queue_cap, t):
+    """P(Wq > t) of a customer ADMITTED to M/M/1/K (FIFO), K = queue_cap + 1, for t >= 0 (a scalar or an array -> the
+    same shape): sum over n = 1 .. K - 1 of q[n] * sum over j < n of exp(-mu t) (mu t)**j / j!, q[n] = p[n] / (1 - p[K])
+    with ``mm1k``'s p -- an arrival that finds n customers waits for n exponential completions (the one in service is
+    memoryless), a mixture of Erlang laws (e.g. Gross & Harris, section 2.5, the waiting-time distribution of the
+    finite queue).  At t = 0 it is 1 - q[0], the chance of waiting at all.  The simulated counterpart is
+    ``simulation_v3.mm1k_wait_sweep``."""
+    return _mm1k_erlang_mixture(lam, mu, queue_cap, t, 0)
+
+
+def mm1k_sojourn_tail(lam, mu, queue_cap, t):
+    """P(W > t) of an admitted customer's whole time in the station: ``mm1k_wait_tail`` with one more stage, the
+    customer's own service -- sum over n = 0 .. K - 1 of q[n] * sum over j <= n of exp(-mu t) (mu t)**j / j!."""
+    return _mm1k_erlang_mixture(lam, mu, queue_cap, t, 1)
+
+
 def mmck_blocking(lam, mu, c, queue_cap):
     """The blocking probability of M/M/c/N, N = c + queue_cap: p[N] with p[n] ~ a**n / n! for n <= c and
     a**n / (c! c**(n - c)) beyond, a = lam / mu.  c = 1 is ``mm1k(...)["blocking"]``.  The simulated counterpart is a

@@ -90,6 +90,17 @@ Differences, on purpose:
     ``warmup=`` on ``replicate`` / ``mm1k_sweep`` / ``mmck_sweep`` leaves the empty-system start out.  These run on the
     host mirror; there is no kernel for them, and a device is refused by name.
 
+  * the log customer by customer: an ``event_id`` is a customer and keeps its id from node to node, so a 'Music' log
+    holds what happened to every one of them, which no per-node accumulator says.  ``log_visits``
+    (``gdm_des_log_visits_host``, the walk of csrc/des_visits.h) turns the logs of a BatchLog into two tables, one row
+    per VISIT (a customer's stay at one node: its arrival, service-start and departure records and their clocks) and
+    one row per CUSTOMER (its visits, when it entered and left, whether it left or was turned away) -> LogVisits;
+    ``visit_stats`` sums them per node (``started`` IS the statistics run's ``served``, ``service_sum`` its
+    ``time_in_service`` and ``wait_sum`` its ``time_in_queue``, bit for bit on nets without queue nodes),
+    ``waiting_times`` / ``sojourn_times`` / ``wait_tail`` are the distributions, and ``mm1k_wait_sweep`` puts the
+    waiting-time law of simulated M/M/1/K beside ``queueing_theory.mm1k_wait_tail``.  The walk runs on the host; a
+    BatchLog of device tensors is read back once, and there is no kernel for it.
+
   * shortest-queue routing is not built: ``FlowBranchOperator.shortest_queue`` (49-52) is set from the probabilities
     AFTER they were normalised, so it can be true only for a node without children, which the table above covers;
     ``use_next_available_server`` (731-736) is read on that path only.  ``Sim.run`` accepts and ignores the argument.
@@ -1115,6 +1126,210 @@ def mmck_sweep(cs, lams, mus, queue_caps, seeds, *, customers, device=None, max_
     mean, sem, n, z = _sweep_summary(values, np.stack(rows["valid"]), theory)
     stats = BatchStats(*(np.concatenate(rows[name]) for name in BatchStats._fields))
     return MmckSweep(cs, lams, mus, caps, np.asarray(seeds, dtype=np.int64), stats, values, mean, sem, n, theory, z)
+
+
+# ---- the log customer by customer: per-visit and per-customer tables ---------------------------------------------------
+VISIT_UNSERVED, VISIT_IN_SERVICE, VISIT_DEPARTED = 0, 1, 2                      # GDM_DES_VISIT_*
+CUST_ABSENT, CUST_UNSERVED, CUST_IN_NET, CUST_EXITED = -1, 0, 1, 2              # GDM_DES_CUST_*
+VISITS_ERECORD, VISITS_EPTR = 1, 2                                              # GDM_DES_VISITS_*
+_VISIT_I32 = ("node", "n_departures", "outcome")
+_VISIT_I64 = ("event_id", "rec_arrival", "rec_start", "rec_first_depart", "rec_depart", "prev_visit", "next_visit")
+_VISIT_F64 = ("t_arrival", "t_start", "service", "t_first_depart", "t_depart")
+_CUST_I32 = ("cust_n_visits", "cust_outcome")
+_CUST_I64 = ("cust_first_visit", "cust_last_visit")
+_CUST_F64 = ("cust_t_enter", "cust_t_exit", "cust_service_sum", "cust_wait_sum")
+LogVisits = collections.namedtuple("LogVisits", _VISIT_I32 + _VISIT_I64 + _VISIT_F64 + ("visit_ptr",) + _CUST_I32 +
+                                   _CUST_I64 + _CUST_F64 + ("cust_ptr", "status"))
+LogVisits.__doc__ = """``log_visits``'s result (``gdm_des_log_visits_host``, include/gdm.h; numpy arrays).  One row per VISIT
+-- a customer's stay at one node, opened by every ``arrival`` record --, sample b's at [visit_ptr[b], visit_ptr[b+1]),
+every index relative to the sample (records to its first record, visits to its first visit), -1 / NaN = none:
+``node``, ``n_departures``, ``outcome`` (int32; VISIT_DEPARTED: a departure was logged, VISIT_IN_SERVICE: started and no
+departure, VISIT_UNSERVED: never started), ``event_id``, ``rec_arrival``, ``rec_start``, ``rec_first_depart``,
+``rec_depart``, ``prev_visit``, ``next_visit`` (int64), ``t_arrival``, ``t_start``, ``service``, ``t_first_depart``,
+``t_depart`` (float64, copies of log values: ``t_start`` is the value of the latest arrival or departure record before
+the visit's ``processing`` record, ``t_depart`` that of its LAST departure record -- a 'queue' node's delayed departures
+are several).  One row per CUSTOMER, sample b's at [cust_ptr[b], cust_ptr[b+1]), row = event id, 0 .. the largest id
+seen: ``cust_n_visits`` (0: the id has no record), ``cust_outcome`` (int32; from the last visit: CUST_EXITED,
+CUST_IN_NET, CUST_UNSERVED; CUST_ABSENT without records), ``cust_first_visit``, ``cust_last_visit`` (int64),
+``cust_t_enter``, ``cust_t_exit`` (the last visit's ``t_depart`` when it departed), ``cust_service_sum`` and
+``cust_wait_sum`` (float64: service and ``t_start - t_arrival`` summed over the started visits in visit order).
+``status`` (B) int32: 0, VISITS_ERECORD or VISITS_EPTR; such a sample has no rows (``raise_for_visits``).
+What a log cannot tell: an UNSERVED visit was turned away or was still waiting when the log ended; a queue node's
+customer whose last logged departure was a delayed one reads as DEPARTED at that clock (at most one per queue node and
+log); EXITED says that no later arrival was logged."""
+
+
+def log_visits(log, *, dim):
+    """The 'Music' logs of B runs over ``dim`` nodes, customer by customer -> LogVisits.  ``log``: a host BatchLog; a
+    BatchLog of device tensors, which is read back once (there is no kernel: the walk runs on the host either way); or
+    ONE EVENT_DTYPE record array (``Sim.music_log``, ``sample_log(...)``), walked as B = 1.  A sample the walk refuses
+    has status != 0 and no rows; nothing is raised here (``raise_for_visits``)."""
+    if isinstance(log, np.ndarray) and log.dtype == EVENT_DTYPE:
+        cols = [log[name] for name in ("value", "event_id", "node", "kind")]
+        rec_ptr = np.array([0, len(log)], dtype=np.int64)
+    else:
+        host = [np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in (log.value, log.event_id, log.node, log.kind,
+                                                                         log.rec_ptr)]
+        cols, rec_ptr = host[:4], host[4]
+    value, eid, node, kind = (np.ascontiguousarray(a, dtype=dt)
+                              for a, dt in zip(cols, (np.float64, np.int64, np.int32, np.int32)))
+    rec_ptr = np.ascontiguousarray(rec_ptr, dtype=np.int64)
+    b = int(rec_ptr.shape[0]) - 1
+    n = min(a.size for a in (value, eid, node, kind))
+    entry = _lib.load().gdm_des_log_visits_host
+    visit_ptr, cust_ptr = np.zeros(b + 1, dtype=np.int64), np.zeros(b + 1, dtype=np.int64)
+    status = np.zeros(b, dtype=np.int32)
+    nv = nc = 0
+    while True:                                           # count, then fill
+        tables = [np.zeros((len(names), cap), dtype=dt) for names, cap, dt in
+                  ((_VISIT_I32, nv, np.int32), (_VISIT_I64, nv, np.int64), (_VISIT_F64, nv, np.float64),
+                   (_CUST_I32, nc, np.int32), (_CUST_I64, nc, np.int64), (_CUST_F64, nc, np.float64))]
+        ptrs = [t.ctypes.data if nv or nc else None for t in tables]
+        rc = entry(value.ctypes.data, eid.ctypes.data, node.ctypes.data, kind.ctypes.data, rec_ptr.ctypes.data, n, b,
+                   int(dim), visit_ptr.ctypes.data, cust_ptr.ctypes.data, status.ctypes.data, *ptrs[:3], nv, *ptrs[3:], nc)
+        need = (int(visit_ptr[b]), int(cust_ptr[b]))
+        if rc not in (0, -3) or need == (nv, nc):         # (-3, GDM_EWORKSPACE: the pointers hold the counts needed)
+            _lib.check(rc, "gdm_des_log_visits_host")
+            break
+        nv, nc = need
+    vi32, vi64, vf64, ci32, ci64, cf64 = tables
+    return LogVisits(*vi32, *vi64, *vf64, visit_ptr, *ci32, *ci64, *cf64, cust_ptr, status)
+
+
+def raise_for_visits(status):
+    """ValueError for the first sample ``log_visits`` refused."""
+    for i, st in enumerate(np.asarray(status).tolist()):
+        if st == VISITS_ERECORD:
+            raise ValueError(f"log_visits: sample {i} holds a record the walk cannot place (a kind, node or event id out "
+                             "of range, or a processing or departure record without its customer's open visit at that "
+                             "node in the state it needs)")
+        if st:
+            raise ValueError(f"log_visits: sample {i}: record offsets outside the log (status {st})")
+
+
+VisitStats = collections.namedtuple("VisitStats", "started unserved departed wait_sum service_sum blocked_sum")
+VisitStats.__doc__ = """``visit_stats``'s result, (B, dim) arrays per node: ``started``, ``unserved``, ``departed`` (int64, the
+visits that were started / never started / have a departure record), ``wait_sum`` = the sum of ``t_start - t_arrival``
+and ``service_sum`` = the sum of ``service`` over the node's started visits, added one by one from 0.0 in ``rec_start``
+order -- the order and the terms of the statistics run's ``time_in_queue`` and ``time_in_service`` on a net without
+queue nodes --, and ``blocked_sum`` = the sum of ``t_depart - t_first_depart`` over its departed visits in the order of
+their first departures: the time a queue node's customers were held back after their first departure.  On a net with
+queue nodes ``wait_sum + blocked_sum`` is ``time_in_queue`` up to the order of the additions -- less one delay where the
+run ended while the queue node held a customer back: the statistics run counts a delay when it schedules it, the log
+shows it when it is over."""
+
+
+def _sum_in_order(x):
+    """x[0] + x[1] + .. one by one from the left (numpy's ``sum`` adds pairwise)."""
+    return float(np.add.accumulate(x)[-1]) if len(x) else 0.0
+
+
+def _per_node(node, key, dim, terms):
+    """Over one sample's visits with key >= 0, in key order: their number per node (dim), and for every array of
+    ``terms`` the sum of each node's entries, one by one."""
+    idx = np.flatnonzero(key >= 0)
+    idx = idx[np.argsort(key[idx], kind="stable")]
+    count = np.bincount(node[idx], minlength=dim)
+    sums = np.zeros((len(terms), dim), dtype=np.float64)
+    for j in np.flatnonzero(count):
+        at = idx[node[idx] == j]
+        for k, x in enumerate(terms):
+            sums[k, j] = _sum_in_order(x[at])
+    return count, sums
+
+
+def visit_stats(v, dim):
+    """A LogVisits per node -> VisitStats of (B, dim) arrays: what ties the log run to the statistics run
+    (``served``, ``time_in_service``, ``time_in_queue``, and ``reneges`` from below and above)."""
+    b = len(v.visit_ptr) - 1
+    started, unserved, departed = (np.zeros((b, dim), dtype=np.int64) for _ in range(3))
+    wait_sum, service_sum, blocked_sum = (np.zeros((b, dim), dtype=np.float64) for _ in range(3))
+    for s in range(b):
+        sl = slice(int(v.visit_ptr[s]), int(v.visit_ptr[s + 1]))
+        node, rec_start = v.node[sl], v.rec_start[sl]
+        unserved[s] = np.bincount(node[rec_start < 0], minlength=dim)
+        started[s], (wait_sum[s], service_sum[s]) = _per_node(node, rec_start, dim, (v.t_start[sl] - v.t_arrival[sl],
+                                                                                   v.service[sl]))
+        departed[s], (blocked_sum[s],) = _per_node(node, v.rec_first_depart[sl], dim,
+                                                   (v.t_depart[sl] - v.t_first_depart[sl],))
+    return VisitStats(started, unserved, departed, wait_sum, service_sum, blocked_sum)
+
+
+def waiting_times(v, b, node, skip=0):
+    """``t_start - t_arrival`` of the started visits of sample b at ``node``, in start order (``rec_start``), the first
+    ``skip`` of them left out (a warm-up)."""
+    sl = slice(int(v.visit_ptr[b]), int(v.visit_ptr[b + 1]))
+    idx = np.flatnonzero((v.node[sl] == node) & (v.rec_start[sl] >= 0))
+    idx = idx[np.argsort(v.rec_start[sl][idx], kind="stable")][int(skip):]
+    return v.t_start[sl][idx] - v.t_arrival[sl][idx]
+
+
+def sojourn_times(v, b):
+    """``cust_t_exit - cust_t_enter`` of sample b's EXITED customers, by event id: the time from the first arrival record
+    to the last departure record."""
+    sl = slice(int(v.cust_ptr[b]), int(v.cust_ptr[b + 1]))
+    out = v.cust_outcome[sl] == CUST_EXITED
+    return v.cust_t_exit[sl][out] - v.cust_t_enter[sl][out]
+
+
+def wait_tail(v, node, ts, skip=0):
+    """(B, len(ts)): per sample the fraction of ``waiting_times(v, b, node, skip)`` that are > t, for every t of ``ts``;
+    NaN for a sample without such a visit."""
+    ts = np.asarray(ts, dtype=np.float64).reshape(-1)
+    out = np.full((len(v.visit_ptr) - 1, len(ts)), np.nan)
+    for b in range(out.shape[0]):
+        w = waiting_times(v, b, node, skip)
+        if len(w):
+            out[b] = (w[:, None] > ts[None, :]).sum(axis=0) / float(len(w))
+    return out
+
+
+Mm1kWaitSweep = collections.namedtuple("Mm1kWaitSweep", "lam mu queue_cap seeds ts visits stop_reason values mean sem n "
+                                                        "theory z")
+Mm1kWaitSweep.__doc__ = """``mm1k_wait_sweep``'s result for C configurations x R seeds x T times: lam, mu, queue_cap (C), seeds
+(R), ts (T); the LogVisits and the stop reasons of the C * R runs (configuration-major: run c * R + r); ``values``
+(C, R, T), per run the fraction of the server's waits that are > ts[t]; their ``mean``, ``sem`` (std with ddof 1 /
+sqrt(n)) and ``n`` (C, T) over the runs that neither errored nor ran out of draws; ``theory`` (C, T),
+``queueing_theory.mm1k_wait_tail``; and ``z`` = (mean - theory) / sem (0 where the difference is 0)."""
+
+
+def mm1k_wait_sweep(lams, mus, queue_caps, seeds, ts, *, customers, skip, device=None, math=1):
+    """The waiting-time LAW of simulated M/M/1/K beside ``queueing_theory.mm1k_wait_tail``, shaped like ``mm1k_sweep``:
+    configuration c = (lams[c], mus[c], queue_caps[c]) on the net of ``mm1k_spec``, every configuration with every seed
+    from the global stream ``replication_states(seeds)[r]``, ALL of them one batch.  The log comes from
+    ``run_batch_host(..., max_records=0)`` (``math`` is the host mirror's) or, with a ``device``, from one launch of
+    ``run_batch_device`` with a record cap no run reaches (four records per event); ``log_visits`` walks it on the host
+    either way.  Per run: the fraction of the server's started visits -- the accepted customers, in start order, the
+    first ``skip`` left out -- that waited longer than each t of ``ts`` -> Mm1kWaitSweep."""
+    from . import ops, queueing_theory as qt
+    lams, mus = np.asarray(lams, dtype=np.float64).reshape(-1), np.asarray(mus, dtype=np.float64).reshape(-1)
+    caps = np.asarray(queue_caps, dtype=np.int64).reshape(-1)
+    seeds = [int(s) for s in np.asarray(seeds).reshape(-1)]
+    ts = np.asarray(ts, dtype=np.float64).reshape(-1)
+    c, r = len(lams), len(seeds)
+    if c == 0 or r == 0 or len(mus) != c or len(caps) != c or len(ts) == 0:
+        raise ValueError("mm1k_wait_sweep: lams, mus and queue_caps must have one entry per configuration, and seeds and "
+                         "ts be given")
+    if (caps < 1).any():
+        raise ValueError("mm1k_wait_sweep: queue_cap >= 1 (the simulator's rings hold at least one customer)")
+    max_events = 4 * int(customers) + 64                  # which no run reaches (an arrival and a departure per customer)
+    specs = [mm1k_spec(lams[i], mus[i], caps[i], customers, s) for i in range(c) for s in seeds]
+    states = replication_states(seeds) * c
+    adj, kind, *rest = dist_arrays(specs)
+    if device is None:
+        log = run_batch_host(adj, *rest, states, math=math, max_events=max_events, max_records=0, kind=kind)
+    else:
+        log = run_batch_device(adj, *rest, states, device=device, max_events=max_events,
+                               max_records=4 * max_events + 4 * adj.shape[1] + 64, kind=kind)
+    visits = log_visits(log, dim=adj.shape[1])
+    raise_for_visits(visits.status)
+    stop = np.asarray(log.stop_reason.cpu() if hasattr(log.stop_reason, "cpu") else log.stop_reason)
+    valid = ((stop != ops.DES_STOP_ERROR) & (stop != ops.DES_STOP_BUDGET)).reshape(c, r)
+    values = wait_tail(visits, 1, ts, skip).reshape(c, r, len(ts))
+    theory = np.stack([qt.mm1k_wait_tail(lams[i], mus[i], caps[i], ts) for i in range(c)])
+    mean, sem, n, z = _sweep_summary({"w": values}, valid, {"w": theory})
+    return Mm1kWaitSweep(lams, mus, caps, np.asarray(seeds, dtype=np.int64), ts, visits, stop, values, mean["w"], sem["w"],
+                         n["w"], theory, z["w"])
 
 
 def math_probe_host(x):

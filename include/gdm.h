@@ -687,6 +687,58 @@ int gdm_des_log_tracks_host(const int32_t* node, const int32_t* kind, const int6
                             int dim, const int32_t* col_of_node, int S, int64_t max_lines, int64_t* n_rows,
                             int64_t* row_ptr, int32_t* status, int32_t* tracks, int64_t n_rows_cap);
 
+/* ---- log -> per-visit and per-customer tables (csrc/des_visits.hip, the walk in csrc/des_visits.h; host code only) ----
+ * An event_id is a customer and keeps its id from node to node.  Per sample b, over its records [rec_ptr[b],
+ * rec_ptr[b + 1]), with i the index of a record relative to the sample's first:
+ *   arrival (kind 0) at node n, id e, value t: opens visit v (node, event_id, rec_arrival = i, t_arrival = t); prev_visit
+ *     = the customer's visit before (-1: none), whose next_visit becomes v; a customer's OPEN visit is its latest one;
+ *   processing (kind 2) at n, e, value s: starts e's open visit, which must be at n and not started: rec_start = i,
+ *     service = s, t_start = the value of the latest arrival or departure record before it;
+ *   departure (kind 1) at n, e, value t: ends e's open visit, which must be at n and started: n_departures + 1; the first
+ *     one sets rec_first_depart / t_first_depart, every one rec_depart / t_depart -- the last one wins (a 'queue' node's
+ *     delayed departures are several departure records of one visit).
+ * Visit rows, CSR over samples by visit_ptr (B + 1), indices relative to the sample; column k of a block of n_visits_cap
+ * rows starts at k * n_visits_cap; -1 / NaN = none; the doubles are copies of log values:
+ *   visit_i32 (3, cap): node, n_departures, outcome (GDM_DES_VISIT_DEPARTED: a departure was logged; _IN_SERVICE:
+ *     started, no departure; _UNSERVED: never started -- turned away, or still waiting when the log ended: the log alone
+ *     cannot tell.  A queue node's customer whose last logged departure was a delayed one reads as DEPARTED at that
+ *     clock: at most one per queue node and log)
+ *   visit_i64 (7, cap): event_id, rec_arrival, rec_start, rec_first_depart, rec_depart, prev_visit, next_visit
+ *   visit_f64 (5, cap): t_arrival, t_start, service, t_first_depart, t_depart
+ * Customer rows, CSR by cust_ptr (B + 1); row = event id, 0 .. the largest id seen; blocks of n_customers_cap rows:
+ *   cust_i32 (2, cap): n_visits (0: the id has no record; then outcome GDM_DES_CUST_ABSENT, visits -1, times NaN, sums
+ *     0), outcome (from the last visit: GDM_DES_CUST_EXITED, _IN_NET or _UNSERVED; EXITED means no later arrival was
+ *     logged)
+ *   cust_i64 (2, cap): first_visit, last_visit
+ *   cust_f64 (4, cap): t_enter (t_arrival of the first visit), t_exit (t_depart of the last visit when it DEPARTED, else
+ *     NaN), service_sum and wait_sum: the sums of service and of (t_start - t_arrival) over the customer's started
+ *     visits, from 0.0 in visit order (first_visit, then next_visit)
+ * status (B) i32; a refused sample has ZERO visits and ZERO customers and its neighbours are what they are without it:
+ *   GDM_DES_VISITS_ERECORD  a kind outside 0..2; a node outside 0..dim-1; an event_id < 0 or > n + dim, n the sample's
+ *     record count (an id is handed out at the latest when an earlier arrival of its source is processed); a processing
+ *     or departure record whose customer has no open visit at that node; a second processing for one visit; a departure
+ *     before its processing; a processing record with no clock record before it (which the open visit's arrival rules out)
+ *   GDM_DES_VISITS_EPTR     offsets outside the record arrays
+ * The six tables NULL with both caps 0 only counts (visit_ptr, cust_ptr, status); GDM_EWORKSPACE when a cap is too
+ * small: visit_ptr[B] / cust_ptr[B] then hold the counts needed and the tables' contents are not defined.
+ * There is NO device entry and no kernel: a log on the device is read back once.           */
+#define GDM_DES_VISITS_ERECORD 1
+#define GDM_DES_VISITS_EPTR 2
+#define GDM_DES_VISIT_UNSERVED 0
+#define GDM_DES_VISIT_IN_SERVICE 1
+#define GDM_DES_VISIT_DEPARTED 2
+#define GDM_DES_CUST_ABSENT (-1)
+#define GDM_DES_CUST_UNSERVED 0
+#define GDM_DES_CUST_IN_NET 1
+#define GDM_DES_CUST_EXITED 2
+#define GDM_DES_VISITS_MAX_DIM 4096
+#define GDM_DES_VISITS_MAX_RECORDS ((int64_t)1 << 40)
+int gdm_des_log_visits_host(const double* value, const int64_t* event_id, const int32_t* node, const int32_t* kind,
+                            const int64_t* rec_ptr, int64_t n_records, int B, int dim, int64_t* visit_ptr,
+                            int64_t* cust_ptr, int32_t* status, int32_t* visit_i32, int64_t* visit_i64,
+                            double* visit_f64, int64_t n_visits_cap, int32_t* cust_i32, int64_t* cust_i64,
+                            double* cust_f64, int64_t n_customers_cap);
+
 /* ---- generic convolution lowering helpers (model 2 discriminator, model 1 generator) ----------------------------
  * im2col for Conv2d fwd / dW and col2im (gather form, deterministic) for Conv2d dX and ConvTranspose2d fwd.
  * Activations are channels-last (B,H,W,C) unless `src_planar` (NCHW fp32 input planes, e.g. the piano-roll).
